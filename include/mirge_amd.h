@@ -708,6 +708,44 @@ int mrg_write_isomir_tables(const char *isomirs_path, const char *samples_path, 
                             const int32_t *group_of_entry, uint64_t n_entries, const char *const *group_names,
                             uint32_t n_groups, const double *filtered, uint64_t *rows);
 
+/*
+ * -trf: density-peak clustering (Rodriguez-Laio) of the per-sample tRF reports, the O(n^2) parts of
+ * utils/writeDataToCSV.py (W2C) :802-1088 for every (sample, tRNA) group of one run at once.
+ * Group g owns rows [off[g], off[g+1]) (off: HOST array of n_groups + 1, off[0] = 0), in the order of its
+ * block of `<sample>.potential_tRFs.report`: row k is the reference's index k + 1.  A row is its read in
+ * the template frame:
+ *   d_span   uint16 per row: first | last << 8, 1-based template positions;
+ *   d_codes  [W][n] uint64 (W = ceil(max_len / 32)): base at position p in bits 2(p-1), 2(p-1)+1 of word
+ *            (p-1) / 32, A=0 C=1 G=2 T=3 (N = 0), as the read encoding above;
+ *   d_nmask  same shape, bit 2(p-1) set = N, or NULL when no row has an N.
+ * max_len is the longest template of the batch, 1..255 (a longer one is MRG_ERR_ARG).  The distance of two
+ * rows is getDistance's (W2C:417-449): |first_i - first_j| + |last_i - last_j| + overlapping positions whose
+ * characters differ (N = N, N != base); no n^2 matrix is stored.  Each call synchronises `stream`.
+ *
+ * mrg_trf_rho     local_density (W2C:470-499, gaussian): d_rho[i] = float32 of the left-to-right double sum
+ *                 over j != i in row order of ktab[d_ij] * d_rpm[j] (each product rounded), plus d_rpm[i];
+ *                 ktab = HOST table of K[d] = exp(-(d / dc)^2) for d < n_ktab (1..256; K = 0 beyond).
+ *                 d_max_dis[g] = the group's largest pairwise distance (getDistance's max_dis; 0 for one row).
+ * mrg_trf_delta   min_distance (W2C:509-533): d_rank lists each group's rows (group-local, 0-based) in rank
+ *                 order (d_rank[off[g] + p] = row at position p).  For the row at position p > 0: d_delta =
+ *                 min(max_dis, distance to any row at a position q < p), d_nneigh = that row (group-local), of
+ *                 equally near rows the one at the largest q; the top row gets -1 in both.
+ * mrg_trf_border  the border densities (W2C:951-961): d_label = each row's cluster label (-1 or 1..NCLUST);
+ *                 bord_off = HOST array of n_groups + 1 offsets into d_bord, NCLUST + 1 slots per group (groups
+ *                 with fewer than 3 slots, NCLUST <= 1, are skipped).  d_bord[bord_off[g] + c] = max over pairs
+ *                 of rows with different labels and distance <= 3 of float32 (rho_i + rho_j) / 2 with label c
+ *                 among them, 0 if none; label -1 is slot NCLUST (Python's bord_rho[-1]).  d_bord is zeroed first.
+ */
+int mrg_trf_rho(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, uint32_t max_len, const uint64_t *d_codes,
+                const uint64_t *d_nmask, const uint16_t *d_span, const double *d_rpm, const double *ktab, uint32_t n_ktab,
+                float *d_rho, uint32_t *d_max_dis, void *stream);
+int mrg_trf_delta(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, uint32_t max_len, const uint64_t *d_codes,
+                  const uint64_t *d_nmask, const uint16_t *d_span, const uint32_t *d_rank, const uint32_t *d_max_dis,
+                  int32_t *d_delta, int32_t *d_nneigh, void *stream);
+int mrg_trf_border(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, uint32_t max_len, const uint64_t *d_codes,
+                   const uint64_t *d_nmask, const uint16_t *d_span, const float *d_rho, const int32_t *d_label,
+                   const uint32_t *bord_off, float *d_bord, void *stream);
+
 /* Packing helper used by hosts without numpy: ASCII reads -> SoA words. */
 int mrg_pack_reads(const char *const *seqs, uint64_t n, uint32_t words_per_read,
                    uint64_t *reads, uint8_t *lens, uint64_t *nmask, int *has_n);

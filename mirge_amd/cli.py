@@ -13,9 +13,9 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     cutadapt's 3' adapter search restated, 16-nt minimum);
   * `-ai` reads the genome from `<sp>_genome.mrgfm` / `.fa` or `<sp>_genome.partNNN.mrgfm`
     (`build_index --max-bases 500000000`) and answers the two genome bowtie runs on the GPU;
-  * `-trf` writes `tRFs.potential.report.tsv`, `tRF.Counts.csv`, `tRF.RP100K.csv` and
-    `discarded.reads.summary.assigningtRFs.csv`; the per-sample clustering reports
-    (`tRFs.samples.tmp/`) and the PDF report are not produced.
+  * `-trf` writes `tRFs.potential.report.tsv`, `tRF.Counts.csv`, `tRF.RP100K.csv`,
+    `discarded.reads.summary.assigningtRFs.csv` and the per-sample reports and density-peak clusters
+    of `tRFs.samples.tmp/` (mirge_amd.trf_samples, clustered on the GPU); the PDF report is not produced.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -477,6 +477,9 @@ def annotate_main(args, engine_factory=None, materialize=False):
         trf.collect_trf_content(trf_content, sub, sample_list, trf_tables["trnaStruDic"], pre_seqs,
                                 trf.engine_lister(engine))
         trf.write_trf_tables(outdir, sample_list, log_dic, trf_content, trf_tables, pre_seqs)
+        from . import trf_samples   # W2C:802-1088: tRFs.samples.tmp/, density peaks on the GPU
+        trf_samples.write_trf_samples(outdir, sample_list, trf_content, trf_tables, pre_seqs,
+                                      trf_samples.engine_peaks(engine))
     if args.diff_isomirs and not long_mirna:
         columnar.write_isomir_tables(os.path.join(outdir, "isomirs.csv"), os.path.join(outdir, "isomirs.samples.csv"), sample_list,
                                      h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, npp[CANON_PASS], log_dic)

@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enums only: the library is bound at run time (see RcclApi)
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include "fm_index.hpp"
 #include "kernels.hpp"
 #include "tables.hpp"
+#include "trf_peaks.hpp"
 
 struct mrg_index {
   mutable mrg::FmIndex ix;
@@ -3110,6 +3112,119 @@ int mrg_fastq_copy_long(const mrg_fastq* fq, uint64_t* words, uint64_t* nmask, u
   std::vector<const char*> ptrs(lr.size());
   for (size_t i = 0; i < lr.size(); ++i) ptrs[i] = lr[i].c_str();
   return pack_ragged(ptrs.data(), lr.size(), words, nmask, word_off, lens, has_n);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- -trf density peaks (csrc/trf_peaks.hip)
+namespace {
+
+// Checks what the three calls share and uploads the launch metadata -- row offsets, the block list (most work
+// first: a rho / border block scans its whole group, a delta block the rank positions before its end), bord_off
+// and the rho call's kernel table -- in one device buffer, *meta, that trf_finish frees.
+int trf_prepare(const char* fn, mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_t max_len,
+                const uint64_t* d_codes, const uint64_t* d_nmask, const uint16_t* d_span, bool by_rank,
+                const uint32_t* bord_off, const double* ktab, uint32_t n_ktab, mrg::TrfLaunch* L, void** meta,
+                const void** extra) {
+  if (!ctx || !off || !n_groups) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (max_len < 1 || max_len > 255)
+    return fail(MRG_ERR_ARG, "%s: templates of 1..255 nt (got %u): a longer tRNA cannot be clustered", fn, max_len);
+  if (n_groups > (1u << 24) || off[0] != 0) return fail(MRG_ERR_ARG, "%s: 1..2^24 groups, off[0] = 0", fn);
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (off[g + 1] < off[g] || (bord_off && bord_off[g + 1] < bord_off[g]))
+      return fail(MRG_ERR_ARG, "%s: offsets decrease at group %u", fn, g);
+  if (off[n_groups] && (!d_codes || !d_span)) return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
+  const uint32_t T = mrg::kTrfTile;
+  std::vector<uint2> blocks;
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (!bord_off || bord_off[g + 1] - bord_off[g] >= 3)  // (border pass: only NCLUST > 1)
+      for (uint32_t t = 0; t < off[g + 1] - off[g]; t += T) blocks.push_back(make_uint2(g, t));
+  auto work = [&](const uint2& b) {
+    const uint64_t n = off[b.x + 1] - off[b.x];
+    return by_rank ? std::min<uint64_t>(n, (uint64_t)b.y + T) : n;
+  };
+  std::stable_sort(blocks.begin(), blocks.end(), [&](const uint2& a, const uint2& b) { return work(a) > work(b); });
+  const size_t n_off = (n_groups + 1) * sizeof(uint32_t), at_bl = (n_off + 15) & ~(size_t)15;
+  const size_t at_x = at_bl + ((blocks.size() * sizeof(uint2) + 15) & ~(size_t)15);
+  const size_t n_x = bord_off ? n_off : n_ktab * sizeof(double);
+  std::vector<uint8_t> host(at_x + n_x);
+  std::memcpy(host.data(), off, n_off);
+  if (!blocks.empty()) std::memcpy(host.data() + at_bl, blocks.data(), blocks.size() * sizeof(uint2));
+  if (n_x) std::memcpy(host.data() + at_x, bord_off ? (const void*)bord_off : (const void*)ktab, n_x);
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMalloc(meta, host.size()));
+  const hipError_t e = hipMemcpy(*meta, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) (void)hipFree(*meta);
+  HIP_TRY(e);
+  const uint8_t* m = (const uint8_t*)*meta;
+  *L = mrg::TrfLaunch{(const uint32_t*)m, (const uint2*)(m + at_bl), (uint32_t)blocks.size(), off[n_groups],
+                      (max_len + 31) / 32, d_codes, d_nmask, d_span, nullptr};
+  *extra = m + at_x;
+  return MRG_OK;
+}
+
+int trf_finish(void* meta, hipError_t e, hipStream_t st) {
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(meta);
+  HIP_TRY(e);
+  return MRG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrg_trf_rho(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_t max_len, const uint64_t* d_codes,
+                const uint64_t* d_nmask, const uint16_t* d_span, const double* d_rpm, const double* ktab, uint32_t n_ktab,
+                float* d_rho, uint32_t* d_max_dis, void* stream) {
+  if (!ktab || !n_ktab || n_ktab > mrg::kTrfKtabMax)
+    return fail(MRG_ERR_ARG, "mrg_trf_rho: a kernel table of 1..%u entries is required", mrg::kTrfKtabMax);
+  if (!d_max_dis || (off && n_groups && off[n_groups] && (!d_rpm || !d_rho)))
+    return fail(MRG_ERR_ARG, "mrg_trf_rho: null output buffers");
+  mrg::TrfLaunch L;
+  void* meta = nullptr;
+  const void* kt = nullptr;
+  int rc = trf_prepare("mrg_trf_rho", ctx, off, n_groups, max_len, d_codes, d_nmask, d_span, false, nullptr, ktab,
+                       n_ktab, &L, &meta, &kt);
+  if (rc != MRG_OK) return rc;
+  L.rpm = d_rpm;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(d_max_dis, 0, n_groups * sizeof(uint32_t), st);
+  if (e == hipSuccess) e = mrg::trf_rho_launch(L, (const double*)kt, n_ktab, d_rho, d_max_dis, st);
+  return trf_finish(meta, e, st);
+}
+
+int mrg_trf_delta(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_t max_len, const uint64_t* d_codes,
+                  const uint64_t* d_nmask, const uint16_t* d_span, const uint32_t* d_rank, const uint32_t* d_max_dis,
+                  int32_t* d_delta, int32_t* d_nneigh, void* stream) {
+  if (!d_max_dis || (off && n_groups && off[n_groups] && (!d_rank || !d_delta || !d_nneigh)))
+    return fail(MRG_ERR_ARG, "mrg_trf_delta: null rank / output buffers");
+  mrg::TrfLaunch L;
+  void* meta = nullptr;
+  const void* unused = nullptr;
+  int rc = trf_prepare("mrg_trf_delta", ctx, off, n_groups, max_len, d_codes, d_nmask, d_span, true, nullptr, nullptr,
+                       0, &L, &meta, &unused);
+  if (rc != MRG_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  return trf_finish(meta, mrg::trf_delta_launch(L, d_rank, d_max_dis, d_delta, d_nneigh, st), st);
+}
+
+int mrg_trf_border(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_t max_len, const uint64_t* d_codes,
+                   const uint64_t* d_nmask, const uint16_t* d_span, const float* d_rho, const int32_t* d_label,
+                   const uint32_t* bord_off, float* d_bord, void* stream) {
+  if (!bord_off) return fail(MRG_ERR_ARG, "mrg_trf_border: null argument");
+  if (off && n_groups && (bord_off[0] != 0 || (off[n_groups] && (!d_rho || !d_label)) || (bord_off[n_groups] && !d_bord)))
+    return fail(MRG_ERR_ARG, "mrg_trf_border: bord_off[0] != 0, or null rho / label / output buffers");
+  mrg::TrfLaunch L;
+  void* meta = nullptr;
+  const void* bo = nullptr;
+  int rc = trf_prepare("mrg_trf_border", ctx, off, n_groups, max_len, d_codes, d_nmask, d_span, false, bord_off,
+                       nullptr, 0, &L, &meta, &bo);
+  if (rc != MRG_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = bord_off[n_groups] ? hipMemsetAsync(d_bord, 0, bord_off[n_groups] * sizeof(float), st) : hipSuccess;
+  if (e == hipSuccess) e = mrg::trf_border_launch(L, d_rho, d_label, (const uint32_t*)bo, d_bord, st);
+  return trf_finish(meta, e, st);
 }
 
 }  // extern "C"

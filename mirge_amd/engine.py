@@ -520,6 +520,34 @@ class Engine:
         order = np.lexsort((pos_h, ref_h, owner))
         return mm.cpu().numpy(), off_h, ref_h[order], pos_h[order]
 
+    def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
+        """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
+        mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask
+        None without N), span[n] uint16 (first | last << 8), rpm[n] float64, ktab = K[d] (float64, d < len).
+        Runs the rho pass now and returns a TrfPeaks: .rho (float32[n]) and .max_dis (uint32[G]) on the host,
+        .min_distance(rank) and .border(labels, bord_off) for the two later passes."""
+        torch = _torch()
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        G, n = len(off) - 1, int(off[-1])
+        signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint16): np.int16}  # (same bits; torch copies them)
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(signed.get(np.dtype(dt), dt))).to(self.device)
+        t = TrfPeaks(self, off, max_len)
+        t.codes = dev(np.asarray(codes).reshape(-1) if n else np.zeros(1), np.uint64)
+        t.nmask = dev(np.asarray(nmask).reshape(-1), np.uint64) if nmask is not None and n else None
+        t.span = dev(span if n else np.zeros(1), np.uint16)
+        rpm_d = dev(rpm if n else np.zeros(1), np.float64)
+        kt = np.ascontiguousarray(ktab, dtype=np.float64)
+        rho = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+        t.max_dis_d = torch.empty(max(G, 1), dtype=torch.int32, device=self.device)
+        check(self._lib.mrg_trf_rho(self._h, t.off_c, G, int(max_len), t.codes.data_ptr(), t.nmask_ptr(),
+                                    t.span.data_ptr(), rpm_d.data_ptr(),
+                                    kt.ctypes.data_as(C.POINTER(C.c_double)), len(kt), rho.data_ptr(),
+                                    t.max_dis_d.data_ptr(), self._stream_ptr()))
+        t.rho_d = rho
+        t.rho = rho.cpu().numpy()[:n]
+        t.max_dis = t.max_dis_d.cpu().numpy()[:G].view(np.uint32)
+        return t
+
     # ------------------------------------------------------------------
     def annotate_host(self, words, lens, nmask, passes, quant=None, n_mirna=0,
                       canon_pass=CANON_PASS, isomir_pass=ISOMIR_PASS):
@@ -558,6 +586,47 @@ class Engine:
 
 
 PACKED_REF_SAT, PACKED_POS_SAT = 0x3FFFF, 0xFF
+
+
+class TrfPeaks:
+    """Device state of one Engine.trf_peaks batch (see there)."""
+
+    def __init__(self, engine, off, max_len):
+        self.engine, self.off, self.max_len = engine, off, int(max_len)
+        self.off_c = off.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.G, self.n = len(off) - 1, int(off[-1])
+
+    def nmask_ptr(self):
+        return self.nmask.data_ptr() if self.nmask is not None else None
+
+    def min_distance(self, rank):
+        """min_distance (W2C:509-533): rank = each group's rows (group-local) in rank order, flat like the rows.
+        Returns (delta, nneigh) int32[n]: distance to / group-local row of the nearest row ranked above, -1 for
+        the top row of a group."""
+        torch = _torch()
+        e = self.engine
+        rank_d = torch.from_numpy(np.ascontiguousarray(rank if self.n else np.zeros(1), dtype=np.uint32)
+                                  .view(np.int32)).to(e.device)
+        delta = torch.empty(max(self.n, 1), dtype=torch.int32, device=e.device)
+        nneigh = torch.empty(max(self.n, 1), dtype=torch.int32, device=e.device)
+        check(e._lib.mrg_trf_delta(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),
+                                   self.span.data_ptr(), rank_d.data_ptr(), self.max_dis_d.data_ptr(),
+                                   delta.data_ptr(), nneigh.data_ptr(), e._stream_ptr()))
+        return delta.cpu().numpy()[:self.n], nneigh.cpu().numpy()[:self.n]
+
+    def border(self, labels, bord_off):
+        """Border densities (W2C:951-961): labels int32[n] (-1 or 1..NCLUST), bord_off[G+1] (NCLUST + 1 slots
+        per group, none where NCLUST <= 1).  Returns float32[bord_off[-1]]."""
+        torch = _torch()
+        e = self.engine
+        bo = np.ascontiguousarray(bord_off, dtype=np.uint32)
+        nb = int(bo[-1])
+        lab = torch.from_numpy(np.ascontiguousarray(labels if self.n else np.zeros(1), dtype=np.int32)).to(e.device)
+        bord = torch.empty(max(nb, 1), dtype=torch.float32, device=e.device)
+        check(e._lib.mrg_trf_border(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),
+                                    self.span.data_ptr(), self.rho_d.data_ptr(), lab.data_ptr(),
+                                    bo.ctypes.data_as(C.POINTER(C.c_uint32)), bord.data_ptr(), e._stream_ptr()))
+        return bord.cpu().numpy()[:nb]
 
 
 def unpack_assignments(packed):

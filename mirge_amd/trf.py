@@ -14,8 +14,8 @@ Restates, on small host data:
 The listings come from the GPU (`Engine.list_best` = mrg_list_best_count/fill); tests can pass
 any `lister(reads, library_key, max_mismatches) -> [[(entry name, 0-based offset), ...], ...]`.
 
-Not built (SURVEY.md section 2 row 9 marks it out of scope): the per-sample
-`tRFs.samples.tmp/*` reports and their density-peak clustering (W2C:802-1088).
+The per-sample `tRFs.samples.tmp/*` reports and their density-peak clustering (W2C:802-1088), which
+start from the trfContentDic that write_trf_tables leaves, are mirge_amd.trf_samples.
 
 Where the reference is not deterministic it is pinned here:
   * `random.choice(candidatetRNAUniquelist)` (W2C:708) -> `choose`, default the
