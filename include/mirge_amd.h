@@ -508,6 +508,40 @@ int mrg_list_best_fill(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per
                        int32_t *d_ref, int32_t *d_pos, void *stream);
 
 /*
+ * Every valid alignment of each read against one library, on the forward strand (strands = 1,
+ * bowtie's --norc) or on both (strands = 2: the reverse complement is searched in the same launch,
+ * from the same packed reads): the listing behind the bowtie front end (mirge_amd/bowtie.py),
+ * whose `-a` runs without --strata need every stratum on both strands -- the -ai genome runs
+ * (utils/writeDataToCSV.py:1263 `-n 1 -f -a -3 2`, :1488) and predict mode's genome mapping
+ * (miRge2.0.py:538 `-n 0 -m 3 -l 25 -a --best`).  Validity: <= max_mm_seed mismatches in the
+ * seed (the read's first seed_len bases -- its 5' end on either strand), <= max_mm_total (<= 3)
+ * overall, an N mismatches everything.  No seed interval is cut short: a 10^4-copy element lists
+ * every copy.  Two sweeps, so that a caller can sum the counts of several libraries (the parts of
+ * one genome) before it decides what is written:
+ *   mrg_list_valid_count  d_counts[mm * n + r] (uint32, 4 * n) = exact number of valid alignments
+ *                         of read r with exactly mm = 0..3 mismatches, both strands summed;
+ *                         asynchronous;
+ *   mrg_list_valid_fill   for every read with d_best_mm[r] != 255: its alignments with exactly
+ *                         d_best_mm[r] mismatches (MRG_STRATUM_BEST, `--best --strata`) or all of
+ *                         them (MRG_STRATUM_ALL, `-a`) at d_offsets[r] + k: entry index, 0-based
+ *                         offset in the entry, strand (0 = +, 1 = -), mismatches; order within a
+ *                         read unspecified; slots >= cap are not written.  d_best_mm[r] = 255 (no
+ *                         alignment, or suppressed by -m) writes nothing.  Asynchronous.
+ */
+#define MRG_STRATUM_BEST 0
+#define MRG_STRATUM_ALL 1
+int mrg_list_valid_count(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read,
+                         const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n, int32_t lib,
+                         int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                         int32_t max_mm_total, uint32_t *d_counts, void *stream);
+int mrg_list_valid_fill(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read,
+                        const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n, int32_t lib,
+                        int32_t strands, int32_t stratum_mode, int32_t seed_len,
+                        int32_t max_mm_seed, int32_t max_mm_total, const uint8_t *d_best_mm,
+                        const uint64_t *d_offsets, uint64_t cap, int32_t *d_ref, int32_t *d_pos,
+                        uint8_t *d_strand, uint8_t *d_mm, void *stream);
+
+/*
  * Host-buffer convenience for a caller without its own device allocator (the
  * ctypes stub of INTEGRATION.md): H2D, cascade, tally, D2H in one call.
  * counts may be NULL (then quant/n_samples are ignored).
@@ -691,6 +725,27 @@ int mrg_write_read_table(const char *path, int32_t mapped, const char *header, i
                          const int32_t *ref_id, const uint32_t *quant, uint32_t n_samples,
                          uint32_t n_slots, const char *const *names, const uint64_t *names_off,
                          uint64_t *rows);
+
+/*
+ * bowtie 1.1.2's text output for the bowtie front end (mirge_amd/bowtie.py), from HOST arrays:
+ * read r (input order) is names[names_off[r] .. names_off[r+1]) and its trimmed sequence
+ * seqs[seqs_off[r] .. seqs_off[r+1]) (ASCII, as printed); its alignments are entries
+ * offsets[r] .. offsets[r+1] of entry / offset / strand (0 = +, 1 = -) / mm, printed in that
+ * order; entry numbers run over the parts in order (the parts of one genome are one index).
+ * suppressed[r] != 0 (may be NULL): the read exceeded -m m.  sam != 0:
+ *   @HD, one @SQ per entry (its full length), @PG with CL:"<cmdline>"; aligned lines FLAG 0 / 16,
+ *   MAPQ 255, SEQ / QUAL in reference orientation, XA:i / MD:Z / NM:i (the reference bases come
+ *   from the index text); unaligned FLAG 4 with XM:i:0, suppressed FLAG 4 with XM:i:<m+1>;
+ * sam == 0: bowtie's default format, aligned reads only: name, strand, entry, 0-based offset,
+ *   sequence and qualities in reference orientation, 0, mismatch descriptors offset:ref>read.
+ * Formatted by worker threads in blocks of reads, written in order.  path NULL = standard output.
+ * summary[4] = reads processed, reads with an alignment printed, reads suppressed, alignments printed.
+ */
+int mrg_write_bowtie(const char *path, int32_t sam, const char *cmdline, const mrg_index *const *parts,
+                     uint32_t n_parts, uint64_t n_reads, const char *names, const uint64_t *names_off,
+                     const char *seqs, const uint64_t *seqs_off, const uint64_t *offsets,
+                     const int32_t *entry, const int32_t *offset, const uint8_t *strand,
+                     const uint8_t *mm, const uint8_t *suppressed, int32_t m, uint64_t *summary);
 
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same

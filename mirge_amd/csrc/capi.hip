@@ -2580,6 +2580,89 @@ int mrg_list_best_fill(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per
   return MRG_OK;
 }
 
+namespace {
+
+int fill_valid_params(mrg_ctx* ctx, const char* who, const uint64_t* d_reads, uint32_t words_per_read, const uint8_t* d_lens,
+                      const uint64_t* d_nmask, uint64_t n, int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                      int32_t max_mm_total, mrg::ValidParams* p, uint32_t* grid, uint32_t* lds_bytes) {
+  std::memset(p, 0, sizeof(*p));
+  int rc = fill_count_params(ctx, who, d_reads, words_per_read, d_lens, d_nmask, n, lib, seed_len, max_mm_seed, max_mm_total,
+                             &p->c, grid, lds_bytes);
+  if (rc != MRG_OK) return rc;
+  if (strands != 1 && strands != 2) return fail(MRG_ERR_ARG, "%s: strands must be 1 (forward) or 2 (both)", who);
+  if (max_mm_total > 3) return fail(MRG_ERR_ARG, "%s: at most 3 mismatches", who);
+  p->strands = (uint32_t)strands;
+  p->c.max_rows = 0xFFFFFFFFu;  // (valid_kernel walks every row of a seed interval)
+  return MRG_OK;
+}
+
+}  // namespace
+
+int mrg_list_valid_count(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, const uint8_t* d_lens,
+                         const uint64_t* d_nmask, uint64_t n, int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                         int32_t max_mm_total, uint32_t* d_counts, void* stream) {
+  mrg::ValidParams p;
+  uint32_t grid = 0, lds = 0;
+  int rc = fill_valid_params(ctx, "mrg_list_valid_count", d_reads, words_per_read, d_lens, d_nmask, n, lib, strands, seed_len,
+                             max_mm_seed, max_mm_total, &p, &grid, &lds);
+  if (rc != MRG_OK) return rc;
+  if (n && !d_counts) return fail(MRG_ERR_ARG, "mrg_list_valid_count: null buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (n == 0) return MRG_OK;
+  p.counts = d_counts;
+  HIP_TRY(mrg::launch_valid(p, false, words_per_read, grid, lds, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_list_valid_fill(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, const uint8_t* d_lens,
+                        const uint64_t* d_nmask, uint64_t n, int32_t lib, int32_t strands, int32_t stratum_mode, int32_t seed_len,
+                        int32_t max_mm_seed, int32_t max_mm_total, const uint8_t* d_best_mm, const uint64_t* d_offsets, uint64_t cap,
+                        int32_t* d_ref, int32_t* d_pos, uint8_t* d_strand, uint8_t* d_mm, void* stream) {
+  mrg::ValidParams p;
+  uint32_t grid = 0, lds = 0;
+  int rc = fill_valid_params(ctx, "mrg_list_valid_fill", d_reads, words_per_read, d_lens, d_nmask, n, lib, strands, seed_len,
+                             max_mm_seed, max_mm_total, &p, &grid, &lds);
+  if (rc != MRG_OK) return rc;
+  if (stratum_mode != MRG_STRATUM_BEST && stratum_mode != MRG_STRATUM_ALL)
+    return fail(MRG_ERR_ARG, "mrg_list_valid_fill: stratum_mode must be MRG_STRATUM_BEST or MRG_STRATUM_ALL");
+  if (n && (!d_best_mm || !d_offsets)) return fail(MRG_ERR_ARG, "mrg_list_valid_fill: null buffers");
+  if (cap && (!d_ref || !d_pos || !d_strand || !d_mm)) return fail(MRG_ERR_ARG, "mrg_list_valid_fill: null output buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (n == 0 || cap == 0) return MRG_OK;
+  p.all = stratum_mode == MRG_STRATUM_ALL ? 1u : 0u;
+  p.c.best_mm = const_cast<uint8_t*>(d_best_mm);
+  p.c.offsets = d_offsets;
+  p.c.out_ref = d_ref;
+  p.c.out_pos = d_pos;
+  p.c.out_cap = cap;
+  p.out_strand = d_strand;
+  p.out_mm = d_mm;
+  HIP_TRY(mrg::launch_valid(p, true, words_per_read, grid, lds, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_write_bowtie(const char* path, int32_t sam, const char* cmdline, const mrg_index* const* parts, uint32_t n_parts,
+                     uint64_t n_reads, const char* names, const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off,
+                     const uint64_t* offsets, const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm,
+                     const uint8_t* suppressed, int32_t m, uint64_t* summary) {
+  if ((n_parts && !parts) || (n_reads && (!names || !names_off || !seqs || !seqs_off || !offsets)) || !summary)
+    return fail(MRG_ERR_ARG, "mrg_write_bowtie: null argument");
+  if (n_reads && offsets[n_reads] && (!entry || !offset || !strand || !mm))
+    return fail(MRG_ERR_ARG, "mrg_write_bowtie: null alignment arrays");
+  std::vector<const mrg::FmIndex*> ix(n_parts);
+  for (uint32_t i = 0; i < n_parts; ++i) {
+    if (!parts[i]) return fail(MRG_ERR_ARG, "mrg_write_bowtie: null index");
+    ix[i] = &parts[i]->ix;
+  }
+  try {
+    mrg::write_bowtie(path, sam != 0, cmdline, ix, n_reads, names, names_off, seqs, seqs_off, offsets, entry, offset, strand, mm,
+                      suppressed, m, summary);
+    return MRG_OK;
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_bowtie: %s", e.what());
+  }
+}
+
 // ----------------------------------------------------- host convenience
 int mrg_annotate_host(mrg_ctx* ctx, const uint64_t* reads, uint32_t words_per_read,
                       const uint8_t* lens, const uint64_t* nmask, uint64_t n,

@@ -1821,6 +1821,192 @@ __global__ void __launch_bounds__(kCountThreads) count_kernel(const CountParams 
 }
 
 // ---------------------------------------------------------------------------
+// valid_kernel: every valid alignment of every read against one library, on the forward strand
+// and (strands == 2) on the reverse complement, which the lane builds from the read in its own
+// registers -- the listing behind the shim's `bowtie -a` runs (mirge_amd/bowtie.py: the genome runs
+// of the -ai path, W2C:1263/:1488, and predict's MAIN:538).  Same seed-and-verify and the same
+// "counted at the first piece whose searched bases it matches exactly" rule as count_kernel, but
+// no seed interval is ever cut short: a 10^4-copy element lists all of its copies.
+// On the reverse strand the seed is the read's 5' end, i.e. the LAST seed bases of the reverse
+// complement (bowtie's `-n` seed follows the read, not the reference).
+// COUNT sweep (!FILL): counts[mm * n + r] = alignments of read r with exactly mm mismatches.
+// FILL sweep: best_mm[r] = 255 -> nothing; else the alignments with mm == best_mm[r] (or every one
+// with ALL) go to offsets[r] + k, k in the lane's own (deterministic) discovery order.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t reverse_pairs(uint64_t v) {
+  const uint64_t r = __brevll(v);  // 2-bit groups reversed, the two bits of each group swapped back below
+  return ((r >> 1) & kOdd) | ((r & kOdd) << 1);
+}
+
+// Base i of `out` = base L - 1 - i of `in` (complemented when COMP), bases from L on zero.
+template <int W, bool COMP>
+__device__ __forceinline__ void reverse_read(const uint64_t (&in)[W], uint64_t (&out)[W], int32_t L) {
+  uint64_t t[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) t[k] = COMP ? ~reverse_pairs(in[W - 1 - k]) : reverse_pairs(in[W - 1 - k]);
+  // the reversed read sits at the top of the W-word number: shift it down by 64 W - 2 L bits
+  const uint32_t sh = 64u * W - 2u * (uint32_t)L, ws = sh >> 6, bs = sh & 63u;
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    const uint32_t a = (uint32_t)k + ws, b = a + 1u;
+    const uint64_t lo = a < (uint32_t)W ? pick_word<W>(t, a) : 0ull;
+    const uint64_t hi = b < (uint32_t)W ? pick_word<W>(t, b) : 0ull;
+    out[k] = bs ? ((lo >> bs) | (hi << (64u - bs))) : lo;
+  }
+#pragma unroll
+  for (int k = 0; k < W; ++k) out[k] &= low_bits((uint32_t)min(max(2 * L - 64 * k, 0), 64));
+}
+
+template <int W, bool FILL>
+__global__ void __launch_bounds__(kCountThreads) valid_kernel(const ValidParams vp) {
+  const CountParams& p = vp.c;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(p.super);
+    uint4* dst = reinterpret_cast<uint4*>(smem);
+    for (uint32_t i = threadIdx.x; i < p.nsup; i += kCountThreads) dst[i] = src[i];
+  }
+  __syncthreads();
+  Lib<false, false> lib;
+  lib.gblocks = p.blocks;
+  lib.gtext = p.text;
+  lib.sblocks = nullptr;
+  lib.stext = nullptr;
+  lib.ssuper = smem;
+  lib.primary = p.primary;
+
+  for (uint64_t r = (uint64_t)blockIdx.x * kCountThreads + threadIdx.x; r < p.n_reads;
+       r += (uint64_t)gridDim.x * kCountThreads) {
+    const int32_t L = (int32_t)p.lens[r];
+    const uint32_t want_mm = FILL ? (uint32_t)p.best_mm[r] : 0u;
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+    uint64_t slot = FILL ? p.offsets[r] : 0ull;
+    if (L > p.max_mm_seed && (!FILL || want_mm != 255u)) {
+      uint64_t fw[W], fn[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        fw[k] = p.reads[(size_t)k * p.n_reads + r];
+        fn[k] = p.nmask ? p.nmask[(size_t)k * p.n_reads + r] : 0ull;
+      }
+      const int32_t R = min(L, p.seed_len);
+      const int32_t K = p.max_mm_seed + 1;
+      for (uint32_t strand = 0; strand < vp.strands; ++strand) {
+        uint64_t rd[W], nm[W];
+        if (strand) {
+          reverse_read<W, true>(fw, rd, L);
+          reverse_read<W, false>(fn, nm, L);
+        } else {
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            rd[k] = fw[k];
+            nm[k] = fn[k];
+          }
+        }
+        const int32_t seed_lo = strand ? L - R : 0;  // the read's 5' end
+        int32_t stop_[3] = {0, 0, 0}, end_[3] = {0, 0, 0};
+        bool listed[3] = {false, false, false};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (k >= K) continue;
+          const int32_t a = seed_lo + div_pieces(R * k, K), b = seed_lo + div_pieces(R * (k + 1), K);
+          bool has_n = false;
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            const int32_t lo_b = max(a - 32 * w, 0), hi_b = min(b - 32 * w, 32);
+            if (hi_b > lo_b) has_n |= (nm[w] & low_bits(2 * hi_b) & ~low_bits(2 * lo_b)) != 0ull;
+          }
+          if (has_n) continue;
+          uint32_t lo = 0, hi = p.n + 1;
+          int32_t j = b;
+          uint32_t tab_off = 0;
+          const uint32_t kk = p.tabs.k[0] ? pick_table(p.tabs, b - a, tab_off) : 0u;
+          if (kk) {
+            j = b - (int32_t)kk;
+            uint64_t code = pick_word<W>(rd, (uint32_t)j >> 5) >> ((j & 31) * 2);
+            if (W > 1 && (j & 31) + (int32_t)kk > 32)
+              code |= pick_word<W>(rd, ((uint32_t)j >> 5) + 1) << (64 - (j & 31) * 2);
+            code &= (1ull << (2 * kk)) - 1ull;
+            const uint32_t* tab = p.ftab + tab_off + lex_code(code, kk);
+            lo = tab[0];
+            hi = tab[1];
+          }
+          while (j > a && hi > lo && (hi - lo) > p.wstop) {
+            --j;
+            const uint32_t c = (uint32_t)(pick_word<W>(rd, (uint32_t)j >> 5) >> ((j & 31) * 2)) & 3u;
+            const uint4 vl = lib.block(lo >> 5);
+            uint4 vh = vl;
+            if ((hi >> 5) != (lo >> 5)) vh = lib.block(hi >> 5);
+            lo = lib.lf(c, lo, vl);
+            hi = lib.lf(c, hi, vh);
+          }
+          stop_[k] = j;
+          end_[k] = b;
+          listed[k] = true;
+          const uint32_t need_before = (uint32_t)j, need_after = (uint32_t)(L - j);
+          const bool prefilter = p.ctx && hi - lo >= kCtxMinRows;
+          const uint2 probe = prefilter ? context_probe<W>(rd, need_before, need_after) : make_uint2(0u, 0u);
+          for (uint32_t i = lo; i < hi; ++i) {
+            if (prefilter && (int32_t)context_mismatches(p.ctx[i], probe) > p.max_mm_total) continue;
+            const uint64_t row = p.sa[i];
+            const uint32_t before = (uint32_t)(row >> 32) & 255u, after = (uint32_t)(row >> 40) & 255u;
+            if ((need_before > before) | (need_after > after)) continue;
+            const uint32_t s = (uint32_t)row - need_before;
+            uint64_t m[W];
+            uint32_t mm_total = 0, mm_seed = 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+              m[w] = 0ull;
+              const int32_t nb = min(32, L - 32 * w);
+              if (nb > 0) {
+                const uint64_t x = lib.window(s + 32u * w) ^ rd[w];
+                m[w] = (((x | (x >> 1)) & kOdd) | nm[w]) & low_bits(2 * nb);
+                mm_total += (uint32_t)__popcll(m[w]);
+                const int32_t sl = min(max(seed_lo - 32 * w, 0), 32), sh = min(max(seed_lo + R - 32 * w, 0), 32);
+                mm_seed += (uint32_t)__popcll(m[w] & low_bits(2 * sh) & ~low_bits(2 * sl));
+              }
+            }
+            if (((int32_t)mm_seed > p.max_mm_seed) | ((int32_t)mm_total > p.max_mm_total)) continue;
+            bool seen = false;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+              if (q >= k || !listed[q]) continue;
+              bool exact = true;
+#pragma unroll
+              for (int w = 0; w < W; ++w) {
+                const int32_t lo_b = max(stop_[q] - 32 * w, 0), hi_b = min(end_[q] - 32 * w, 32);
+                if (hi_b > lo_b) exact &= (m[w] & low_bits(2 * hi_b) & ~low_bits(2 * lo_b)) == 0ull;
+              }
+              seen |= exact;
+            }
+            if (seen) continue;
+            if (!FILL) {
+              ++cnt[min(mm_total, 3u)];
+              continue;
+            }
+            if (!vp.all && mm_total != want_mm) continue;
+            const uint64_t at = slot++;
+            if (at >= p.out_cap) continue;
+            uint32_t sg = (uint32_t)(row >> 48);
+            if (sg == 0xFFFFu) {
+              sg = p.chunk_seg[s >> 5];
+              while (p.seg_start[sg + 1] <= s) ++sg;
+            }
+            p.out_ref[at] = (int32_t)p.seg_ref[sg];
+            p.out_pos[at] = (int32_t)(s - p.seg_start[sg] + p.seg_off[sg]);
+            vp.out_strand[at] = (uint8_t)strand;
+            vp.out_mm[at] = (uint8_t)mm_total;
+          }
+        }
+      }
+    }
+    if (!FILL) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) vp.counts[(size_t)q * p.n_reads + r] = cnt[q];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // count_variants_kernel (round 6): the one-mismatch genome run (`-n 1 -a -3 2`, writeDataToCSV.py:1263) for one-word reads
 // without N whose whole length is seed region (L <= seed_len), through the library's LARGEST jump table instead of
 // the pigeonhole pieces.  count_kernel halves a 20-nt read into pieces of 10 bases; in a 300 Mbp part a 10-mer has
@@ -2479,6 +2665,34 @@ hipError_t launch_count(const CountParams& p, uint32_t words_per_read, uint32_t 
     default: return hipErrorInvalidValue;
   }
 #undef MRG_COUNT
+  return hipGetLastError();
+}
+
+hipError_t launch_valid(const ValidParams& p, bool fill, uint32_t words_per_read, uint32_t grid, uint32_t lds_bytes,
+                        hipStream_t stream) {
+  if (lds_bytes > 48 * 1024) {  // (a genome part beyond ~200 Mbp, as launch_count)
+    const void* kerns[8] = {reinterpret_cast<const void*>(valid_kernel<1, true>), reinterpret_cast<const void*>(valid_kernel<1, false>),
+                            reinterpret_cast<const void*>(valid_kernel<2, true>), reinterpret_cast<const void*>(valid_kernel<2, false>),
+                            reinterpret_cast<const void*>(valid_kernel<4, true>), reinterpret_cast<const void*>(valid_kernel<4, false>),
+                            reinterpret_cast<const void*>(valid_kernel<8, true>), reinterpret_cast<const void*>(valid_kernel<8, false>)};
+    for (const void* k : kerns) {
+      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+  }
+#define MRG_VALID(W_)                                                                                     \
+  if (fill)                                                                                              \
+    hipLaunchKernelGGL((valid_kernel<W_, true>), dim3(grid), dim3(kCountThreads), lds_bytes, stream, p); \
+  else                                                                                                   \
+    hipLaunchKernelGGL((valid_kernel<W_, false>), dim3(grid), dim3(kCountThreads), lds_bytes, stream, p);
+  switch (words_per_read) {
+    case 1: MRG_VALID(1) break;
+    case 2: MRG_VALID(2) break;
+    case 4: MRG_VALID(4) break;
+    case 8: MRG_VALID(8) break;
+    default: return hipErrorInvalidValue;
+  }
+#undef MRG_VALID
   return hipGetLastError();
 }
 

@@ -473,6 +473,19 @@ struct CountParams {
   uint32_t only_todo;  // round 6: count_variants_kernel ran first; count_kernel takes the reads it marked (best_mm 254) only
 };
 
+// valid_kernel (the bowtie shim's listing, mrg_list_valid_count / _fill): CountParams' library, reads and policy
+// (c.best_mm, c.offsets, c.out_ref / out_pos / out_cap for the fill sweep), plus
+struct ValidParams {
+  CountParams c;
+  uint32_t strands;     // 1 = forward only (--norc), 2 = forward and reverse complement
+  uint32_t all;         // fill sweep: 1 = every valid alignment, 0 = only those with c.best_mm[r] mismatches
+  uint32_t* counts;     // count sweep: [4][n] alignments with exactly 0..3 mismatches
+  uint8_t* out_strand;  // fill sweep: 0 = +, 1 = -
+  uint8_t* out_mm;
+};
+hipError_t launch_valid(const ValidParams& p, bool fill, uint32_t words_per_read, uint32_t grid, uint32_t lds_bytes,
+                        hipStream_t stream);
+
 struct TallyParams {
   const uint32_t* packed;  // non-null: pass and entry come from the packed words (pass_id / ref_id unused)
   const int8_t* pass_id;

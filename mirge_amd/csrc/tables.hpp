@@ -1,6 +1,7 @@
 // Streaming writers of mapped.csv / unmapped.csv from columnar arrays (internal header).
 #pragma once
 #include <cstdint>
+#include <vector>
 
 namespace mrg {
 
@@ -18,5 +19,12 @@ uint64_t write_isomir_tables(const char* isomirs_path, const char* samples_path,
                              uint64_t n, const int8_t* pass_id, const int32_t* ref_id, const uint32_t* quant, uint32_t S,
                              int32_t canon_pass, int32_t isomir_pass, const int32_t* group_of_entry, uint64_t n_entries,
                              const char* const* group_names, uint32_t n_groups, const double* filtered);
+
+struct FmIndex;
+// bowtie 1.1.2's SAM / default text (mrg_write_bowtie, include/mirge_amd.h); bowtie_out.cpp.  Throws std::runtime_error.
+void write_bowtie(const char* path, bool sam, const char* cmdline, const std::vector<const FmIndex*>& parts, uint64_t n_reads,
+                  const char* names, const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, const uint64_t* offsets,
+                  const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
+                  int32_t m, uint64_t* summary);
 
 }  // namespace mrg

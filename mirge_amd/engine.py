@@ -36,6 +36,7 @@ MIRGE_PASS_TABLE = [
 EXACT_LIBS = frozenset(row[0] for row in MIRGE_PASS_TABLE if row[4] == 0)
 DICT_SMALL_BASES = 1 << 22   # csrc/dict_index.hpp: kDictSmallBases / kDictMaxBases
 DICT_MAX_BASES = 1 << 30
+STRATUM_BEST, STRATUM_ALL = 0, 1  # mrg_list_valid_fill: MRG_STRATUM_BEST / MRG_STRATUM_ALL
 CANON_PASS = 0   # annot slot 1 "exact miRNA"
 ISOMIR_PASS = 8  # annot slot 9 "isomiR miRNA"
 
@@ -519,6 +520,84 @@ class Engine:
         owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_h))
         order = np.lexsort((pos_h, ref_h, owner))
         return mm.cpu().numpy(), off_h, ref_h[order], pos_h[order]
+
+    def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
+                   max_mm_total=2, timings=None):
+        """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a
+        ReadSet against the libraries `libs` (keys or ids: the parts of one genome, whose entries are numbered on
+        across the parts in this order), on the forward strand (strands=1, --norc) or both (2).  stratum_mode:
+        STRATUM_BEST = the read's best stratum over all parts and strands (`--best --strata`), STRATUM_ALL = every
+        valid alignment (`-a`).  m > 0: a read whose reportable total (what that mode lists, summed over the parts)
+        exceeds m is suppressed and lists nothing (bowtie's -m).
+        Returns host arrays (offsets[n+1], entry, offset, strand (0 = +, 1 = -), mm, suppressed[n] bool); read r owns
+        [offsets[r], offsets[r+1]), ordered by mismatches ascending, then (entry, offset, strand) DESCENDING.
+        timings: a dict, or None; gets the synchronised wall seconds of the count and of the fill sweeps."""
+        import time
+        torch = _torch()
+        n = reads.n
+        dev = self.device
+        lids = [self.libs[k] if isinstance(k, str) else int(k) for k in libs]
+        keys = {v: k for k, v in self.libs.items()}
+        bases = np.cumsum([0] + [self.indexes[keys[l]].n_ref for l in lids])
+        nm = reads.nmask.data_ptr() if reads.nmask is not None else None
+        args = (reads.W, reads.lens.data_ptr(), nm, n)
+        per_lib = []
+        t0 = time.perf_counter()
+        for lid in lids:
+            cnt = torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev)
+            check(self._lib.mrg_list_valid_count(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(seed_len),
+                                                 int(max_mm_seed), int(max_mm_total), cnt.data_ptr(), self._stream_ptr()))
+            per_lib.append(cnt.cpu().numpy()[:, :n].view(np.uint32).astype(np.int64))
+        if timings is not None:
+            timings["count_s"] = time.perf_counter() - t0
+        tot = np.sum(per_lib, axis=0) if per_lib else np.zeros((4, n), dtype=np.int64)
+        aligned = tot.any(axis=0)
+        best = np.where(aligned, np.argmax(tot > 0, axis=0), 255)
+        cols = np.arange(n)
+        if stratum_mode == STRATUM_BEST:
+            reportable = np.where(aligned, tot[np.minimum(best, 3), cols], 0)
+        else:
+            reportable = tot.sum(axis=0)
+        suppressed = (reportable > m) if m > 0 else np.zeros(n, dtype=bool)
+        write = aligned & ~suppressed
+        best_w = np.where(write, best, 255).astype(np.uint8)
+        best_d = torch.from_numpy(best_w if n else np.full(1, 255, np.uint8)).to(dev)
+        got = []
+        t_fill = 0.0
+        for lid, c, base in zip(lids, per_lib, bases):
+            k = c[np.minimum(best, 3), cols] if stratum_mode == STRATUM_BEST else c.sum(axis=0)
+            k = np.where(write, k, 0)
+            off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(k, out=off[1:])
+            t = int(off[-1])
+            if t == 0:
+                continue
+            off_d = torch.from_numpy(off).to(dev)
+            ref = torch.empty(t, dtype=torch.int32, device=dev)
+            pos = torch.empty(t, dtype=torch.int32, device=dev)
+            strand = torch.empty(t, dtype=torch.uint8, device=dev)
+            mm = torch.empty(t, dtype=torch.uint8, device=dev)
+            t0 = time.perf_counter()
+            check(self._lib.mrg_list_valid_fill(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(stratum_mode),
+                                                int(seed_len), int(max_mm_seed), int(max_mm_total), best_d.data_ptr(),
+                                                off_d.data_ptr(), t, ref.data_ptr(), pos.data_ptr(), strand.data_ptr(),
+                                                mm.data_ptr(), self._stream_ptr()))
+            torch.cuda.current_stream(dev).synchronize()
+            t_fill += time.perf_counter() - t0
+            got.append((np.repeat(np.arange(n, dtype=np.int64), k), ref.cpu().numpy().astype(np.int64) + int(base),
+                        pos.cpu().numpy(), strand.cpu().numpy(), mm.cpu().numpy()))
+        if timings is not None:
+            timings["fill_s"] = t_fill
+        if got:
+            owner, entry, pos, strand, mm = (np.concatenate(x) for x in zip(*got))
+        else:
+            owner, entry = np.zeros(0, np.int64), np.zeros(0, np.int64)
+            pos, strand, mm = np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+        order = np.lexsort((-strand.astype(np.int64), -pos.astype(np.int64), -entry, mm, owner))
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(owner, minlength=n)[:n], out=offsets[1:])
+        return (offsets, entry[order].astype(np.int32), pos[order].astype(np.int32), strand[order], mm[order],
+                suppressed)
 
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
