@@ -748,6 +748,95 @@ int mrg_write_bowtie(const char *path, int32_t sam, const char *cmdline, const m
                      const uint8_t *mm, const uint8_t *suppressed, int32_t m, uint64_t *summary);
 
 /*
+ * Predict mode's location clusters (reference utils/cluster_basedon_location.py, called at miRge2.0.py:538-548 on the
+ * samtools-sorted SAM of the genome run) from the rows mrg_list_valid_fill left ON THE DEVICE: sorted by coordinate
+ * and merged where they overlap, without the SAM text, samtools or a Python loop (mirge_amd/predict.py,
+ * Engine.cluster_valid).  The rule, per (entry, strand) list in position order, rows at one position in read order:
+ * an alignment [s, e] (1-based, e = s + read length - 1) joins the cluster [S, E] in front of it iff s <= E and
+ * E - s + 1 >= threshold, else it opens a new one; a joining row with e > E appends SEQ[E - s + 1 :] (SEQ = the read,
+ * reverse-complemented on the - strand, N kept) and sets E = e.  All buffers are the caller's; `rows` < 2^32 - 1,
+ * positions < 2^pos_bits <= 2^31.
+ *   mrg_cluster_workspace_bytes  scratch (d_tmp) and per-row work area (d_work) sizes for `rows` rows;
+ *   mrg_cluster_keys    one call per genome part, after its mrg_list_valid_fill: 64-bit keys of the part's rows
+ *                       (d_ref / d_pos / d_strand [rows], d_offsets [n_reads + 1] as given to the fill) at
+ *                       row_base .. row_base + rows of d_keys, with the row number as value (d_vals) and the row's read
+ *                       in d_owner.  Entry = entry_base + d_ref.  MRG_CLUSTER_ORDER: (entry, strand, position);
+ *                       MRG_SAM_ORDER: (entry, position, strand) -- a coordinate-sorted SAM file, + before - at one
+ *                       position.  d_entry_keep (may be NULL) [n_entries]: rows of an entry with 0 (a name without
+ *                       "chr") get the entry number n_entries and sort behind all others.  Asynchronous;
+ *   mrg_cluster_sort    the library's stable LSD radix sort of the pairs over the low `bits` key bits (pos_bits + 1 +
+ *                       the bits of n_entries); *in_second = the result is in d_keys1 / d_vals1.  Equal keys keep row
+ *                       order, which is read order.  Asynchronous;
+ *   mrg_cluster_scan    over pairs sorted in MRG_CLUSTER_ORDER: a segmented inclusive max-scan of e over the lists,
+ *                       the cluster heads, their prefix sum; d_member[i] = the read of sorted row i.  *n_valid = rows on
+ *                       kept entries (the first n_valid), *n_clusters; synchronises the stream;
+ *   mrg_cluster_bounds  per cluster: entry, strand, start, end, first sorted row (d_member_off [n_clusters + 1]),
+ *                       sequence length (d_len [n_clusters + 1]) and its prefix sum (d_seq_off [n_clusters + 1]);
+ *                       *total_len = d_seq_off[n_clusters]; synchronises the stream;
+ *   mrg_cluster_assemble  every row writes the bases it contributes to d_seq [total_len] (ASCII) and adds its read's
+ *                       d_counts[read] to d_sum [n_clusters] (64-bit).  Asynchronous;
+ *   mrg_cluster_sorted_rows  sorted pairs of either order as columns: read, entry, 0-based offset, strand, and d_mm
+ *                       [rows, unsorted] gathered.  Asynchronous.
+ */
+#define MRG_CLUSTER_ORDER 0
+#define MRG_SAM_ORDER 1
+int mrg_cluster_workspace_bytes(uint64_t rows, uint64_t *tmp_bytes, uint64_t *work_bytes);
+int mrg_cluster_keys(mrg_ctx *ctx, const uint64_t *d_offsets, uint64_t n_reads, const int32_t *d_ref,
+                     const int32_t *d_pos, const uint8_t *d_strand, uint64_t rows, uint64_t row_base,
+                     uint64_t total_rows, uint32_t entry_base, uint32_t n_entries, uint32_t pos_bits,
+                     int32_t order, const uint8_t *d_entry_keep, uint64_t *d_keys, uint32_t *d_vals,
+                     uint32_t *d_owner, void *stream);
+int mrg_cluster_sort(mrg_ctx *ctx, uint64_t *d_keys0, uint64_t *d_keys1, uint32_t *d_vals0,
+                     uint32_t *d_vals1, uint64_t rows, uint32_t bits, void *d_tmp, uint64_t tmp_bytes,
+                     int32_t *in_second, void *stream);
+int mrg_cluster_scan(mrg_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_vals, uint64_t rows,
+                     const uint32_t *d_owner, const uint8_t *d_lens, uint32_t n_entries,
+                     uint32_t pos_bits, int32_t threshold, void *d_work, uint64_t work_bytes,
+                     void *d_tmp, uint64_t tmp_bytes, uint32_t *d_member, uint64_t *n_valid,
+                     uint64_t *n_clusters, void *stream);
+int mrg_cluster_bounds(mrg_ctx *ctx, const uint64_t *d_keys, uint64_t rows, uint64_t n_valid,
+                       uint64_t n_clusters, uint32_t pos_bits, void *d_work, uint64_t work_bytes,
+                       void *d_tmp, uint64_t tmp_bytes, uint32_t *d_entry, uint8_t *d_strand,
+                       uint32_t *d_start, uint32_t *d_end, uint32_t *d_member_off, uint32_t *d_len,
+                       uint64_t *d_seq_off, uint64_t *total_len, void *stream);
+int mrg_cluster_assemble(mrg_ctx *ctx, const uint64_t *d_keys, uint64_t rows, uint64_t n_valid,
+                         uint64_t n_clusters, uint32_t pos_bits, void *d_work, uint64_t work_bytes,
+                         const uint32_t *d_member, const uint64_t *d_reads, uint32_t words_per_read,
+                         const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n_reads,
+                         const uint32_t *d_counts, const uint32_t *d_start, const uint64_t *d_seq_off,
+                         char *d_seq, uint64_t *d_sum, void *stream);
+int mrg_cluster_sorted_rows(mrg_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_vals, uint64_t rows,
+                            uint32_t pos_bits, int32_t order, const uint32_t *d_owner,
+                            const uint8_t *d_mm, uint32_t *d_read, int32_t *d_entry, int32_t *d_pos,
+                            uint8_t *d_strand, uint8_t *d_mm_out, void *stream);
+
+/*
+ * Predict mode's two files from HOST arrays (reads and index parts as for mrg_write_bowtie), formatted by worker
+ * threads in blocks and written in order:
+ *   mrg_write_sorted_sam  `@HD VN:1.0 SO:coordinate`, the @SQ lines of mrg_write_bowtie, then the n_rows aligned lines
+ *                         in the order given (row k is read row_read[k]; the lines are mrg_write_bowtie's SAM lines),
+ *                         then the FLAG 4 line of every read without a row, in input order.  summary as there;
+ *   mrg_write_clusters    the header line and one line per cluster: <sample>:miRCluster_<i>_<len> (i from 1), entry
+ *                         name, strand, start, end, sequence, length, summed read count, member count, and the
+ *                         comma-joined names of reads members[member_off[c] .. member_off[c + 1]).  *rows = clusters;
+ *   mrg_read_counts_from_names  counts[r] = the integer between the first and the second `_` of read r's name
+ *                         (`mir<k>_<count>`, reference convert2Fasta.py:131); a name without one is MRG_ERR_FORMAT
+ *                         with *bad_read = r (else -1).
+ */
+int mrg_write_sorted_sam(const char *path, const mrg_index *const *parts, uint32_t n_parts,
+                         uint64_t n_reads, const char *names, const uint64_t *names_off, const char *seqs,
+                         const uint64_t *seqs_off, uint64_t n_rows, const uint32_t *row_read,
+                         const int32_t *entry, const int32_t *offset, const uint8_t *strand,
+                         const uint8_t *mm, const uint8_t *suppressed, int32_t m, uint64_t *summary);
+int mrg_write_clusters(const char *path, const char *sample, const mrg_index *const *parts,
+                       uint32_t n_parts, uint64_t n_clusters, const uint32_t *entry, const uint8_t *strand,
+                       const uint32_t *start, const uint32_t *end, const uint64_t *seq_off, const char *seq,
+                       const uint64_t *count_sum, const uint32_t *member_off, const uint32_t *members,
+                       uint64_t n_reads, const char *names, const uint64_t *names_off, uint64_t *rows);
+int mrg_read_counts_from_names(uint64_t n_reads, const char *names, const uint64_t *names_off,
+                               uint32_t *counts, int64_t *bad_read);
+
+/*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are
  * grouped by group_of_entry[ref_id] -- the caller's map from a miRNA library entry to its name with the ".SNP..." suffix

@@ -6,6 +6,10 @@
 // the columnar alignment arrays, never line by line in Python: worker threads format blocks of reads and hand them on
 // to the output in block order (write_read_table's scheme, tables.cpp, with ordered write(2) so that the target may be
 // a pipe).  What is formatted is documented at mrg_write_bowtie (include/mirge_amd.h).
+//
+// Predict mode's own route (mirge_amd/predict.py) ends here too: the coordinate-sorted SAM file (the same lines in the
+// order of the device's sort) and the cluster table of cluster_basedon_location.py, from the cluster arrays of
+// predict_cluster.hip (mrg_write_sorted_sam, mrg_write_clusters).
 #include <unistd.h>
 #include <fcntl.h>
 
@@ -133,113 +137,125 @@ struct BlockCounts {
   uint64_t aligned = 0, suppressed = 0, lines = 0;
 };
 
-void format_reads(const BowtieArgs& a, uint64_t lo, uint64_t hi, std::string& out, BlockCounts& c) {
+// scratch strings of a formatting thread
+struct LineScratch {
   std::string q, ref, qual;
+};
+
+// the FLAG 4 line of read r (SAM only): unaligned, or suppressed by -m
+void format_unaligned(const BowtieArgs& a, uint64_t r, std::string& out, LineScratch& t) {
+  const uint32_t L = (uint32_t)(a.seqs_off[r + 1] - a.seqs_off[r]);
+  t.qual.assign(L, 'I');
+  out.append(a.names + a.names_off[r], (size_t)(a.names_off[r + 1] - a.names_off[r]));
+  out += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+  out.append(a.seqs + a.seqs_off[r], L);
+  out += '\t';
+  out += t.qual;
+  out += "\tXM:i:";
+  put_u64(out, (a.suppressed && a.suppressed[r]) ? (uint64_t)a.m + 1 : 0u);
+  out += '\n';
+}
+
+// the line of alignment k (entry / offset / strand / mm [k]) of read r
+void format_aligned(const BowtieArgs& a, uint64_t r, uint64_t k, std::string& out, LineScratch& t) {
+  const char* name = a.names + a.names_off[r];
+  const size_t name_len = (size_t)(a.names_off[r + 1] - a.names_off[r]);
+  const char* seq = a.seqs + a.seqs_off[r];
+  const uint32_t L = (uint32_t)(a.seqs_off[r + 1] - a.seqs_off[r]);
+  std::string& q = t.q;
+  std::string& ref = t.ref;
+  t.qual.assign(L, 'I');
+  const bool minus = a.strand[k] != 0;
+  q.assign(seq, L);
+  if (minus) {
+    std::reverse(q.begin(), q.end());
+    for (char& ch : q) ch = complement(ch);
+  }
+  const uint64_t e = (uint64_t)(uint32_t)a.entry[k];
+  const uint32_t off = (uint32_t)a.offset[k];
+  a.entries->bases(e, off, L, ref);
+  const std::string& rname = a.entries->name(e);
+  out.append(name, name_len);
+  if (a.sam) {
+    out += minus ? "\t16\t" : "\t0\t";
+    out += rname;
+    out += '\t';
+    put_u64(out, (uint64_t)off + 1);
+    out += "\t255\t";
+    put_u64(out, L);
+    out += "M\t*\t0\t0\t";
+    out += q;
+    out += '\t';
+    out += t.qual;
+    out += "\tXA:i:";
+    put_u64(out, a.mm[k]);
+    out += "\tMD:Z:";
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < L; ++i) {
+      if (q[i] == ref[i]) {
+        ++run;
+        continue;
+      }
+      put_u64(out, run);
+      out += ref[i];
+      run = 0;
+    }
+    put_u64(out, run);
+    out += "\tNM:i:";
+    put_u64(out, a.mm[k]);
+  } else {
+    out += minus ? "\t-\t" : "\t+\t";
+    out += rname;
+    out += '\t';
+    put_u64(out, off);
+    out += '\t';
+    out += q;
+    out += '\t';
+    out += t.qual;
+    out += "\t0\t";
+    bool first = true;
+    for (uint32_t i = 0; i < L; ++i) {
+      if (q[i] == ref[i]) continue;
+      if (!first) out += ',';
+      first = false;
+      put_u64(out, i);
+      out += ':';
+      out += ref[i];
+      out += '>';
+      out += q[i];
+    }
+  }
+  out += '\n';
+}
+
+void format_reads(const BowtieArgs& a, uint64_t lo, uint64_t hi, std::string& out, BlockCounts& c) {
+  LineScratch t;
   for (uint64_t r = lo; r < hi; ++r) {
-    const char* name = a.names + a.names_off[r];
-    const size_t name_len = (size_t)(a.names_off[r + 1] - a.names_off[r]);
-    const char* seq = a.seqs + a.seqs_off[r];
-    const uint32_t L = (uint32_t)(a.seqs_off[r + 1] - a.seqs_off[r]);
     const uint64_t k0 = a.offsets[r], k1 = a.offsets[r + 1];
-    qual.assign(L, 'I');
     if ((a.suppressed && a.suppressed[r]) || k0 == k1) {
       if (a.suppressed && a.suppressed[r]) ++c.suppressed;
-      if (!a.sam) continue;
-      out.append(name, name_len);
-      out += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
-      out.append(seq, L);
-      out += '\t';
-      out += qual;
-      out += "\tXM:i:";
-      put_u64(out, (a.suppressed && a.suppressed[r]) ? (uint64_t)a.m + 1 : 0u);
-      out += '\n';
+      if (a.sam) format_unaligned(a, r, out, t);
       continue;
     }
     ++c.aligned;
     for (uint64_t k = k0; k < k1; ++k) {
-      const bool minus = a.strand[k] != 0;
-      q.assign(seq, L);
-      if (minus) {
-        std::reverse(q.begin(), q.end());
-        for (char& ch : q) ch = complement(ch);
-      }
-      const uint64_t e = (uint64_t)(uint32_t)a.entry[k];
-      const uint32_t off = (uint32_t)a.offset[k];
-      a.entries->bases(e, off, L, ref);
-      const std::string& rname = a.entries->name(e);
-      out.append(name, name_len);
-      if (a.sam) {
-        out += minus ? "\t16\t" : "\t0\t";
-        out += rname;
-        out += '\t';
-        put_u64(out, (uint64_t)off + 1);
-        out += "\t255\t";
-        put_u64(out, L);
-        out += "M\t*\t0\t0\t";
-        out += q;
-        out += '\t';
-        out += qual;
-        out += "\tXA:i:";
-        put_u64(out, a.mm[k]);
-        out += "\tMD:Z:";
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < L; ++i) {
-          if (q[i] == ref[i]) {
-            ++run;
-            continue;
-          }
-          put_u64(out, run);
-          out += ref[i];
-          run = 0;
-        }
-        put_u64(out, run);
-        out += "\tNM:i:";
-        put_u64(out, a.mm[k]);
-      } else {
-        out += minus ? "\t-\t" : "\t+\t";
-        out += rname;
-        out += '\t';
-        put_u64(out, off);
-        out += '\t';
-        out += q;
-        out += '\t';
-        out += qual;
-        out += "\t0\t";
-        bool first = true;
-        for (uint32_t i = 0; i < L; ++i) {
-          if (q[i] == ref[i]) continue;
-          if (!first) out += ',';
-          first = false;
-          put_u64(out, i);
-          out += ':';
-          out += ref[i];
-          out += '>';
-          out += q[i];
-        }
-      }
-      out += '\n';
+      format_aligned(a, r, k, out, t);
       ++c.lines;
     }
   }
 }
 
-}  // namespace
-
-void write_bowtie(const char* path, bool sam, const char* cmdline, const std::vector<const FmIndex*>& parts, uint64_t n_reads,
-                  const char* names, const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, const uint64_t* offsets,
-                  const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
-                  int32_t m, uint64_t* summary) {
-  const Entries entries(parts);
-  const int fd = path ? ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644) : 1;
-  if (fd < 0) throw std::runtime_error(std::string("cannot open ") + path);
-  struct Closer {
-    int fd;
-    bool own;
-    ~Closer() {
-      if (own && fd >= 0) ::close(fd);
-    }
-  } closer{fd, path != nullptr};
-  auto write_all = [&](const char* data, size_t len) {
+// An output file (path null = standard output) written with ordered write(2), so that the target may be a pipe.
+struct OutFile {
+  int fd;
+  const char* path;
+  explicit OutFile(const char* p) : fd(p ? ::open(p, O_WRONLY | O_CREAT | O_TRUNC, 0644) : 1), path(p) {
+    if (fd < 0) throw std::runtime_error(std::string("cannot open ") + p);
+  }
+  ~OutFile() {
+    if (path && fd >= 0) ::close(fd);
+  }
+  void write_all(const char* data, size_t len) {
     while (len) {
       const ssize_t w = ::write(fd, data, len);
       if (w < 0) {
@@ -249,30 +265,27 @@ void write_bowtie(const char* path, bool sam, const char* cmdline, const std::ve
       data += w;
       len -= (size_t)w;
     }
-  };
-  if (sam) {
-    std::string h = "@HD\tVN:1.0\tSO:unsorted\n";
-    for (const FmIndex* ix : parts)
-      for (size_t e = 0; e < ix->names.size(); ++e) {
-        h += "@SQ\tSN:";
-        h += ix->names[e];
-        h += "\tLN:";
-        put_u64(h, ix->ref_len[e]);
-        h += '\n';
-      }
-    h += "@PG\tID:Bowtie\tVN:1.1.2\tCL:\"";
-    h += cmdline ? cmdline : "";
-    h += "\"\n";
-    write_all(h.data(), h.size());
   }
-  const BowtieArgs a{sam, &entries, names, names_off, seqs, seqs_off, offsets, entry, offset, strand, mm, suppressed, m};
+  void close() {
+    if (!path) return;
+    const int f = fd;
+    fd = -1;
+    if (::close(f) != 0) throw std::runtime_error(std::string("cannot close ") + path);
+  }
+};
+
+unsigned writer_threads(uint64_t n_blocks) {
   unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
-  constexpr uint64_t kBlockReads = 1u << 16;
-  const uint64_t n_blocks = (n_reads + kBlockReads - 1) / kBlockReads;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
-  // turn = the block whose text goes out next: a worker formats its block, waits for its turn, writes, passes the turn on
-  std::atomic<uint64_t> next{0}, turn{0}, aligned{0}, supp{0}, lines{0};
+  return (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
+}
+
+// format(b, text) for every block b < n_blocks on worker threads; the texts go out in block order.
+// turn = the block whose text goes out next: a worker formats its block, waits for its turn, writes, passes the turn on
+template <class Format>
+void write_blocks_in_order(OutFile& file, uint64_t n_blocks, Format format) {
+  const unsigned n_threads = writer_threads(n_blocks);
+  std::atomic<uint64_t> next{0}, turn{0};
   std::atomic<bool> stop{false};
   std::vector<std::exception_ptr> failed(n_threads);
   auto worker = [&](unsigned t) {
@@ -282,17 +295,13 @@ void write_bowtie(const char* path, bool sam, const char* cmdline, const std::ve
         const uint64_t b = next.fetch_add(1, std::memory_order_relaxed);
         if (b >= n_blocks || stop.load(std::memory_order_relaxed)) break;
         text.clear();
-        BlockCounts c;
-        format_reads(a, b * kBlockReads, std::min(n_reads, (b + 1) * kBlockReads), text, c);
+        format(b, text);
         while (turn.load(std::memory_order_acquire) != b) {
           if (stop.load(std::memory_order_relaxed)) return;
           std::this_thread::yield();
         }
-        write_all(text.data(), text.size());
+        file.write_all(text.data(), text.size());
         turn.store(b + 1, std::memory_order_release);
-        aligned.fetch_add(c.aligned, std::memory_order_relaxed);
-        supp.fetch_add(c.suppressed, std::memory_order_relaxed);
-        lines.fetch_add(c.lines, std::memory_order_relaxed);
       }
     } catch (...) {
       failed[t] = std::current_exception();
@@ -320,14 +329,157 @@ void write_bowtie(const char* path, bool sam, const char* cmdline, const std::ve
   }
   for (unsigned t = 0; t < n_threads; ++t)
     if (failed[t]) std::rethrow_exception(failed[t]);
-  if (path) {
-    closer.own = false;
-    if (::close(fd) != 0) throw std::runtime_error(std::string("cannot close ") + path);
+}
+
+void sam_sq_lines(const std::vector<const FmIndex*>& parts, std::string& h) {
+  for (const FmIndex* ix : parts)
+    for (size_t e = 0; e < ix->names.size(); ++e) {
+      h += "@SQ\tSN:";
+      h += ix->names[e];
+      h += "\tLN:";
+      put_u64(h, ix->ref_len[e]);
+      h += '\n';
+    }
+}
+
+}  // namespace
+
+void write_bowtie(const char* path, bool sam, const char* cmdline, const std::vector<const FmIndex*>& parts, uint64_t n_reads,
+                  const char* names, const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, const uint64_t* offsets,
+                  const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
+                  int32_t m, uint64_t* summary) {
+  const Entries entries(parts);
+  OutFile file(path);
+  if (sam) {
+    std::string h = "@HD\tVN:1.0\tSO:unsorted\n";
+    sam_sq_lines(parts, h);
+    h += "@PG\tID:Bowtie\tVN:1.1.2\tCL:\"";
+    h += cmdline ? cmdline : "";
+    h += "\"\n";
+    file.write_all(h.data(), h.size());
   }
+  const BowtieArgs a{sam, &entries, names, names_off, seqs, seqs_off, offsets, entry, offset, strand, mm, suppressed, m};
+  constexpr uint64_t kBlockReads = 1u << 16;
+  const uint64_t n_blocks = (n_reads + kBlockReads - 1) / kBlockReads;
+  std::atomic<uint64_t> aligned{0}, supp{0}, lines{0};
+  write_blocks_in_order(file, n_blocks, [&](uint64_t b, std::string& text) {
+    BlockCounts c;
+    format_reads(a, b * kBlockReads, std::min(n_reads, (b + 1) * kBlockReads), text, c);
+    aligned.fetch_add(c.aligned, std::memory_order_relaxed);
+    supp.fetch_add(c.suppressed, std::memory_order_relaxed);
+    lines.fetch_add(c.lines, std::memory_order_relaxed);
+  });
+  file.close();
   summary[0] = n_reads;
   summary[1] = aligned.load();
   summary[2] = supp.load();
   summary[3] = lines.load();
+}
+
+void write_sorted_sam(const char* path, const std::vector<const FmIndex*>& parts, uint64_t n_reads, const char* names,
+                      const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, uint64_t n_rows, const uint32_t* row_read,
+                      const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
+                      int32_t m, uint64_t* summary) {
+  const Entries entries(parts);
+  OutFile file(path);
+  std::string h = "@HD\tVN:1.0\tSO:coordinate\n";
+  sam_sq_lines(parts, h);
+  file.write_all(h.data(), h.size());
+  const BowtieArgs a{true, &entries, names, names_off, seqs, seqs_off, nullptr, entry, offset, strand, mm, suppressed, m};
+  std::vector<uint8_t> has_row(n_reads, 0);
+  for (uint64_t k = 0; k < n_rows; ++k) {
+    if (row_read[k] >= n_reads) throw std::runtime_error("alignment row of an unknown read");
+    has_row[row_read[k]] = 1;
+  }
+  // the aligned rows in the order given, then the reads without one in input order
+  constexpr uint64_t kBlock = 1u << 16;
+  const uint64_t row_blocks = (n_rows + kBlock - 1) / kBlock, read_blocks = (n_reads + kBlock - 1) / kBlock;
+  std::atomic<uint64_t> supp{0}, unaligned{0};
+  write_blocks_in_order(file, row_blocks + read_blocks, [&](uint64_t b, std::string& text) {
+    LineScratch t;
+    if (b < row_blocks) {
+      for (uint64_t k = b * kBlock; k < std::min(n_rows, (b + 1) * kBlock); ++k) format_aligned(a, row_read[k], k, text, t);
+      return;
+    }
+    b -= row_blocks;
+    uint64_t n_supp = 0, n_un = 0;
+    for (uint64_t r = b * kBlock; r < std::min(n_reads, (b + 1) * kBlock); ++r) {
+      if (has_row[r]) continue;
+      ++n_un;
+      if (suppressed && suppressed[r]) ++n_supp;
+      format_unaligned(a, r, text, t);
+    }
+    supp.fetch_add(n_supp, std::memory_order_relaxed);
+    unaligned.fetch_add(n_un, std::memory_order_relaxed);
+  });
+  file.close();
+  summary[0] = n_reads;
+  summary[1] = n_reads - unaligned.load();
+  summary[2] = supp.load();
+  summary[3] = n_rows;
+}
+
+void write_clusters(const char* path, const char* sample, const std::vector<const FmIndex*>& parts, uint64_t n_clusters,
+                    const uint32_t* entry, const uint8_t* strand, const uint32_t* start, const uint32_t* end, const uint64_t* seq_off,
+                    const char* seq, const uint64_t* count_sum, const uint32_t* member_off, const uint32_t* members, uint64_t n_reads,
+                    const char* names, const uint64_t* names_off, uint64_t* rows) {
+  const Entries entries(parts);
+  OutFile file(path);
+  const std::string h = "miRClusterID\tChr\tStrand\tStart\tEnd\tSequence\tSequenceLenght\tCoutOfReads\tCountOfMembers\tMembers\n";
+  file.write_all(h.data(), h.size());
+  constexpr uint64_t kBlock = 1u << 13;
+  write_blocks_in_order(file, (n_clusters + kBlock - 1) / kBlock, [&](uint64_t b, std::string& text) {
+    for (uint64_t c = b * kBlock; c < std::min(n_clusters, (b + 1) * kBlock); ++c) {
+      const uint64_t len = seq_off[c + 1] - seq_off[c];
+      text += sample ? sample : "";
+      text += ":miRCluster_";
+      put_u64(text, c + 1);
+      text += '_';
+      put_u64(text, len);
+      text += '\t';
+      text += entries.name(entry[c]);
+      text += strand[c] ? "\t-\t" : "\t+\t";
+      put_u64(text, start[c]);
+      text += '\t';
+      put_u64(text, end[c]);
+      text += '\t';
+      text.append(seq + seq_off[c], (size_t)len);
+      text += '\t';
+      put_u64(text, len);
+      text += '\t';
+      put_u64(text, count_sum[c]);
+      text += '\t';
+      put_u64(text, member_off[c + 1] - member_off[c]);
+      text += '\t';
+      for (uint32_t k = member_off[c]; k < member_off[c + 1]; ++k) {
+        const uint32_t r = members[k];
+        if (r >= n_reads) throw std::runtime_error("cluster member of an unknown read");
+        if (k != member_off[c]) text += ',';
+        text.append(names + names_off[r], (size_t)(names_off[r + 1] - names_off[r]));
+      }
+      text += '\n';
+    }
+  });
+  file.close();
+  *rows = n_clusters;
+}
+
+// the integer between the first and the second '_' of every read name (`mir<k>_<count>`, reference convert2Fasta.py:131)
+int64_t read_counts_from_names(uint64_t n_reads, const char* names, const uint64_t* names_off, uint32_t* counts) {
+  for (uint64_t r = 0; r < n_reads; ++r) {
+    const char* p = names + names_off[r];
+    const char* e = names + names_off[r + 1];
+    while (p < e && *p != '_') ++p;
+    if (p == e || p + 1 == e || p[1] < '0' || p[1] > '9') return (int64_t)r;
+    uint64_t v = 0;
+    for (++p; p < e && *p != '_'; ++p) {
+      if (*p < '0' || *p > '9') return (int64_t)r;
+      v = v * 10 + (uint64_t)(*p - '0');
+      if (v > 0xffffffffull) return (int64_t)r;
+    }
+    counts[r] = (uint32_t)v;
+  }
+  return -1;
 }
 
 }  // namespace mrg

@@ -22,6 +22,8 @@
 #include "fastq.hpp"
 #include "fm_index.hpp"
 #include "kernels.hpp"
+#include "predict_cluster.hpp"
+#include "prims.hpp"
 #include "tables.hpp"
 #include "trf_peaks.hpp"
 
@@ -2661,6 +2663,202 @@ int mrg_write_bowtie(const char* path, int32_t sam, const char* cmdline, const m
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "mrg_write_bowtie: %s", e.what());
   }
+}
+
+// ------------------------------------------------- predict mode: clusters
+namespace {
+int cluster_check(const char* who, const mrg_ctx* ctx, uint64_t rows, uint32_t n_entries, uint32_t pos_bits) {
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", who);
+  if (rows >= 0xffffffffull) return fail(MRG_ERR_ARG, "%s: %llu alignment rows; the limit is 2^32 - 2", who, (unsigned long long)rows);
+  if (pos_bits < 1 || pos_bits > 31) return fail(MRG_ERR_ARG, "%s: positions must be below 2^31 (pos_bits %u)", who, pos_bits);
+  if ((uint64_t)n_entries + 1 > (1ull << (63u - pos_bits)) - 1)
+    return fail(MRG_ERR_ARG, "%s: %u entries do not fit the %u entry bits of the key", who, n_entries, 63u - pos_bits);
+  return MRG_OK;
+}
+size_t cluster_tmp_bytes(uint64_t rows) { return std::max(mrg::prims::radix_temp_bytes(rows + 1), mrg::prims::scan_temp_bytes(rows + 1)); }
+}  // namespace
+
+int mrg_cluster_workspace_bytes(uint64_t rows, uint64_t* tmp_bytes, uint64_t* work_bytes) {
+  if (!tmp_bytes || !work_bytes) return fail(MRG_ERR_ARG, "mrg_cluster_workspace_bytes: null argument");
+  *tmp_bytes = cluster_tmp_bytes(rows);
+  *work_bytes = mrg::cluster_work_bytes(rows);
+  return MRG_OK;
+}
+
+int mrg_cluster_keys(mrg_ctx* ctx, const uint64_t* d_offsets, uint64_t n_reads, const int32_t* d_ref, const int32_t* d_pos,
+                     const uint8_t* d_strand, uint64_t rows, uint64_t row_base, uint64_t total_rows, uint32_t entry_base,
+                     uint32_t n_entries, uint32_t pos_bits, int32_t order, const uint8_t* d_entry_keep, uint64_t* d_keys,
+                     uint32_t* d_vals, uint32_t* d_owner, void* stream) {
+  int rc = cluster_check("mrg_cluster_keys", ctx, total_rows, n_entries, pos_bits);
+  if (rc != MRG_OK) return rc;
+  if (order != MRG_CLUSTER_ORDER && order != MRG_SAM_ORDER) return fail(MRG_ERR_ARG, "mrg_cluster_keys: unknown key order %d", order);
+  if (row_base + rows > total_rows || n_reads >= 0xffffffffull) return fail(MRG_ERR_ARG, "mrg_cluster_keys: rows or reads out of range");
+  if (rows && (!n_reads || !d_offsets || !d_ref || !d_pos || !d_strand || !d_keys || !d_vals || !d_owner))
+    return fail(MRG_ERR_ARG, "mrg_cluster_keys: null buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  mrg::ClusterKeysArgs a{d_offsets, n_reads, d_ref, d_pos, d_strand, (uint32_t)rows, entry_base, (uint32_t)row_base, n_entries, pos_bits,
+                         order, d_entry_keep, d_keys, d_vals, d_owner};
+  HIP_TRY(mrg::cluster_keys_launch(a, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_cluster_sort(mrg_ctx* ctx, uint64_t* d_keys0, uint64_t* d_keys1, uint32_t* d_vals0, uint32_t* d_vals1, uint64_t rows,
+                     uint32_t bits, void* d_tmp, uint64_t tmp_bytes, int32_t* in_second, void* stream) {
+  if (!ctx || !in_second) return fail(MRG_ERR_ARG, "mrg_cluster_sort: null argument");
+  if (rows >= 0xffffffffull) return fail(MRG_ERR_ARG, "mrg_cluster_sort: %llu alignment rows; the limit is 2^32 - 2", (unsigned long long)rows);
+  if (bits > 64) return fail(MRG_ERR_ARG, "mrg_cluster_sort: %u key bits", bits);
+  if (rows && (!d_keys0 || !d_keys1 || !d_vals0 || !d_vals1 || !d_tmp)) return fail(MRG_ERR_ARG, "mrg_cluster_sort: null buffers");
+  if (tmp_bytes < cluster_tmp_bytes(rows)) return fail(MRG_ERR_ARG, "mrg_cluster_sort: scratch smaller than mrg_cluster_workspace_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  bool second = false;
+  HIP_TRY(mrg::prims::radix_sort_pairs_u64(d_keys0, d_keys1, d_vals0, d_vals1, (uint32_t)rows, bits, d_tmp, (hipStream_t)stream, &second));
+  *in_second = second ? 1 : 0;
+  return MRG_OK;
+}
+
+int mrg_cluster_scan(mrg_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_vals, uint64_t rows, const uint32_t* d_owner,
+                     const uint8_t* d_lens, uint32_t n_entries, uint32_t pos_bits, int32_t threshold, void* d_work, uint64_t work_bytes,
+                     void* d_tmp, uint64_t tmp_bytes, uint32_t* d_member, uint64_t* n_valid, uint64_t* n_clusters, void* stream) {
+  int rc = cluster_check("mrg_cluster_scan", ctx, rows, n_entries, pos_bits);
+  if (rc != MRG_OK) return rc;
+  if (!n_valid || !n_clusters) return fail(MRG_ERR_ARG, "mrg_cluster_scan: null argument");
+  if (threshold < 1) return fail(MRG_ERR_ARG, "mrg_cluster_scan: the overlap threshold must be at least 1 (got %d)", threshold);
+  *n_valid = *n_clusters = 0;
+  if (rows == 0) return MRG_OK;
+  if (!d_keys || !d_vals || !d_owner || !d_lens || !d_work || !d_tmp || !d_member) return fail(MRG_ERR_ARG, "mrg_cluster_scan: null buffers");
+  if (work_bytes < mrg::cluster_work_bytes(rows) || tmp_bytes < cluster_tmp_bytes(rows))
+    return fail(MRG_ERR_ARG, "mrg_cluster_scan: buffers smaller than mrg_cluster_workspace_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const mrg::ClusterWork w = mrg::cluster_work(d_work, rows);
+  HIP_TRY(mrg::cluster_rows_launch(d_keys, d_vals, (uint32_t)rows, d_owner, d_lens, n_entries, pos_bits, w, d_member, st));
+  HIP_TRY(mrg::prims::segmented_inclusive_max_u32(w.end, w.lhead, w.runmax, rows, d_tmp, st));
+  HIP_TRY(mrg::cluster_heads_launch(d_keys, (uint32_t)rows, n_entries, pos_bits, threshold, w, st));
+  HIP_TRY(mrg::prims::inclusive_sum_u32(w.chead, w.cinc, rows, d_tmp, st));
+  uint32_t last = 0;
+  HIP_TRY(hipMemcpyAsync(n_valid, w.n_valid, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&last, w.cinc + (rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *n_clusters = last;
+  return MRG_OK;
+}
+
+int mrg_cluster_bounds(mrg_ctx* ctx, const uint64_t* d_keys, uint64_t rows, uint64_t n_valid, uint64_t n_clusters, uint32_t pos_bits,
+                       void* d_work, uint64_t work_bytes, void* d_tmp, uint64_t tmp_bytes, uint32_t* d_entry, uint8_t* d_strand,
+                       uint32_t* d_start, uint32_t* d_end, uint32_t* d_member_off, uint32_t* d_len, uint64_t* d_seq_off,
+                       uint64_t* total_len, void* stream) {
+  int rc = cluster_check("mrg_cluster_bounds", ctx, rows, 0, pos_bits);
+  if (rc != MRG_OK) return rc;
+  if (!total_len) return fail(MRG_ERR_ARG, "mrg_cluster_bounds: null argument");
+  if (n_valid > rows || n_clusters > n_valid) return fail(MRG_ERR_ARG, "mrg_cluster_bounds: more clusters than rows");
+  if (!d_member_off || !d_len || !d_seq_off || (rows && (!d_keys || !d_work || !d_tmp)) ||
+      (n_clusters && (!d_entry || !d_strand || !d_start || !d_end)))
+    return fail(MRG_ERR_ARG, "mrg_cluster_bounds: null buffers");
+  if (work_bytes < mrg::cluster_work_bytes(rows) || tmp_bytes < cluster_tmp_bytes(rows))
+    return fail(MRG_ERR_ARG, "mrg_cluster_bounds: buffers smaller than mrg_cluster_workspace_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const mrg::ClusterWork w = mrg::cluster_work(d_work, rows);
+  const mrg::ClusterTable c{(uint32_t)n_clusters, (uint32_t)n_valid, d_entry, d_strand, d_start, d_end, d_member_off, d_len};
+  HIP_TRY(mrg::cluster_bounds_launch(d_keys, pos_bits, w, c, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(d_len, d_seq_off, n_clusters + 1, d_tmp, st));
+  HIP_TRY(hipMemcpyAsync(total_len, d_seq_off + n_clusters, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+int mrg_cluster_assemble(mrg_ctx* ctx, const uint64_t* d_keys, uint64_t rows, uint64_t n_valid, uint64_t n_clusters, uint32_t pos_bits,
+                         void* d_work, uint64_t work_bytes, const uint32_t* d_member, const uint64_t* d_reads, uint32_t words_per_read,
+                         const uint8_t* d_lens, const uint64_t* d_nmask, uint64_t n_reads, const uint32_t* d_counts,
+                         const uint32_t* d_start, const uint64_t* d_seq_off, char* d_seq, uint64_t* d_sum, void* stream) {
+  int rc = cluster_check("mrg_cluster_assemble", ctx, rows, 0, pos_bits);
+  if (rc != MRG_OK) return rc;
+  if (n_valid > rows || n_clusters > n_valid) return fail(MRG_ERR_ARG, "mrg_cluster_assemble: more clusters than rows");
+  if (n_clusters == 0) return MRG_OK;
+  if (!d_keys || !d_work || !d_member || !d_reads || !d_lens || !d_counts || !d_start || !d_seq_off || !d_seq || !d_sum)
+    return fail(MRG_ERR_ARG, "mrg_cluster_assemble: null buffers");
+  if (work_bytes < mrg::cluster_work_bytes(rows)) return fail(MRG_ERR_ARG, "mrg_cluster_assemble: buffer smaller than mrg_cluster_workspace_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const mrg::ClusterWork w = mrg::cluster_work(d_work, rows);
+  const mrg::ClusterTable c{(uint32_t)n_clusters, (uint32_t)n_valid, nullptr, nullptr, const_cast<uint32_t*>(d_start), nullptr, nullptr, nullptr};
+  HIP_TRY(hipMemsetAsync(d_sum, 0, n_clusters * sizeof(uint64_t), st));
+  const mrg::ClusterAssembleArgs a{d_keys, pos_bits, d_member, d_reads, words_per_read, d_nmask, d_lens, n_reads, d_counts, d_seq_off, d_seq,
+                                   reinterpret_cast<unsigned long long*>(d_sum)};
+  HIP_TRY(mrg::cluster_assemble_launch(a, w, c, st));
+  return MRG_OK;
+}
+
+int mrg_cluster_sorted_rows(mrg_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_vals, uint64_t rows, uint32_t pos_bits, int32_t order,
+                            const uint32_t* d_owner, const uint8_t* d_mm, uint32_t* d_read, int32_t* d_entry, int32_t* d_pos,
+                            uint8_t* d_strand, uint8_t* d_mm_out, void* stream) {
+  int rc = cluster_check("mrg_cluster_sorted_rows", ctx, rows, 0, pos_bits);
+  if (rc != MRG_OK) return rc;
+  if (order != MRG_CLUSTER_ORDER && order != MRG_SAM_ORDER) return fail(MRG_ERR_ARG, "mrg_cluster_sorted_rows: unknown key order %d", order);
+  if (rows && (!d_keys || !d_vals || !d_owner || !d_mm || !d_read || !d_entry || !d_pos || !d_strand || !d_mm_out))
+    return fail(MRG_ERR_ARG, "mrg_cluster_sorted_rows: null buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(mrg::cluster_gather_launch(d_keys, d_vals, (uint32_t)rows, pos_bits, order, d_owner, d_mm, d_read, d_entry, d_pos, d_strand,
+                                     d_mm_out, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+namespace {
+int index_list(const char* who, const mrg_index* const* parts, uint32_t n_parts, std::vector<const mrg::FmIndex*>* ix) {
+  if (n_parts && !parts) return fail(MRG_ERR_ARG, "%s: null argument", who);
+  ix->resize(n_parts);
+  for (uint32_t i = 0; i < n_parts; ++i) {
+    if (!parts[i]) return fail(MRG_ERR_ARG, "%s: null index", who);
+    (*ix)[i] = &parts[i]->ix;
+  }
+  return MRG_OK;
+}
+}  // namespace
+
+int mrg_write_sorted_sam(const char* path, const mrg_index* const* parts, uint32_t n_parts, uint64_t n_reads, const char* names,
+                         const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, uint64_t n_rows, const uint32_t* row_read,
+                         const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
+                         int32_t m, uint64_t* summary) {
+  if (!path || !summary || (n_reads && (!names || !names_off || !seqs || !seqs_off)))
+    return fail(MRG_ERR_ARG, "mrg_write_sorted_sam: null argument");
+  if (n_rows && (!row_read || !entry || !offset || !strand || !mm)) return fail(MRG_ERR_ARG, "mrg_write_sorted_sam: null alignment arrays");
+  std::vector<const mrg::FmIndex*> ix;
+  int rc = index_list("mrg_write_sorted_sam", parts, n_parts, &ix);
+  if (rc != MRG_OK) return rc;
+  try {
+    mrg::write_sorted_sam(path, ix, n_reads, names, names_off, seqs, seqs_off, n_rows, row_read, entry, offset, strand, mm, suppressed, m,
+                          summary);
+    return MRG_OK;
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_sorted_sam: %s", e.what());
+  }
+}
+
+int mrg_write_clusters(const char* path, const char* sample, const mrg_index* const* parts, uint32_t n_parts, uint64_t n_clusters,
+                       const uint32_t* entry, const uint8_t* strand, const uint32_t* start, const uint32_t* end, const uint64_t* seq_off,
+                       const char* seq, const uint64_t* count_sum, const uint32_t* member_off, const uint32_t* members, uint64_t n_reads,
+                       const char* names, const uint64_t* names_off, uint64_t* rows) {
+  if (!path || !sample || !rows) return fail(MRG_ERR_ARG, "mrg_write_clusters: null argument");
+  if (n_clusters && (!entry || !strand || !start || !end || !seq_off || !seq || !count_sum || !member_off || !members || !names || !names_off))
+    return fail(MRG_ERR_ARG, "mrg_write_clusters: null cluster arrays");
+  std::vector<const mrg::FmIndex*> ix;
+  int rc = index_list("mrg_write_clusters", parts, n_parts, &ix);
+  if (rc != MRG_OK) return rc;
+  try {
+    mrg::write_clusters(path, sample, ix, n_clusters, entry, strand, start, end, seq_off, seq, count_sum, member_off, members, n_reads,
+                        names, names_off, rows);
+    return MRG_OK;
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_clusters: %s", e.what());
+  }
+}
+
+int mrg_read_counts_from_names(uint64_t n_reads, const char* names, const uint64_t* names_off, uint32_t* counts, int64_t* bad_read) {
+  if (!bad_read || (n_reads && (!names || !names_off || !counts))) return fail(MRG_ERR_ARG, "mrg_read_counts_from_names: null argument");
+  *bad_read = mrg::read_counts_from_names(n_reads, names, names_off, counts);
+  if (*bad_read >= 0)
+    return fail(MRG_ERR_FORMAT, "mrg_read_counts_from_names: read %lld has no `_<count>` field below 2^32 in its name", (long long)*bad_read);
+  return MRG_OK;
 }
 
 // ----------------------------------------------------- host convenience

@@ -1,5 +1,5 @@
-// Device-wide prefix sums and a stable LSD radix sort, written for gfx950 (wave64) -- what collapse.hip, pairs.hip
-// and ingest.hip used to call a library for.
+// Device-wide prefix sums, a segmented max-scan and a stable LSD radix sort, written for gfx950 (wave64) -- what
+// collapse.hip, pairs.hip and ingest.hip used to call a library for.
 //
 // Prefix sum: tiles of 4096 elements (256 threads x 16 consecutive elements).  Level by level: tile sums -> the
 // same scan over the sums -> tile-local scan + the tile's offset.  Three levels cover 2^36 elements.
@@ -120,6 +120,116 @@ hipError_t scan_impl(const TIn* in, T* out, uint64_t n, T* tmp, hipStream_t stre
   PCK(hipGetLastError());
   PCK((scan_impl<T, T, false>(sums, sums, tiles, tmp + ((tiles + 63) & ~63ull), stream)));
   hipLaunchKernelGGL((scan_apply_kernel<TIn, T, INCLUSIVE>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, in, out, n, (const T*)sums);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- segmented max-scan
+// An element is (head flag, value) in one 64-bit word: bit 32 = "a segment starts here", low half = the value.
+//   (fa, a) o (fb, b) = (fa | fb, fb ? b : max(a, b))
+// is associative and 0 = (no head, 0) is its identity, so the scan is the sums' scheme with `o` in place of `+`:
+// every thread folds its 16 consecutive elements, the 64 lanes of a wave scan their folds with __shfl_up, the four
+// wave totals meet in LDS, and the tile aggregates go through the same scan one level up.
+constexpr uint64_t kSegHead = 1ull << 32;
+
+__device__ __forceinline__ uint64_t seg_max_op(uint64_t a, uint64_t b) {
+  const uint32_t av = (uint32_t)a, bv = (uint32_t)b;
+  return ((a | b) & kSegHead) | (uint64_t)((b & kSegHead) ? bv : (av > bv ? av : bv));
+}
+
+// PAIRS: the input is (flag, value) words already (the upper levels); else values and a byte of head flag each
+template <bool PAIRS>
+__device__ __forceinline__ uint64_t seg_load(const uint32_t* __restrict__ in, const uint8_t* __restrict__ head,
+                                             const uint64_t* __restrict__ pairs, uint64_t i) {
+  if (PAIRS) return pairs[i];
+  return (head[i] ? kSegHead : 0ull) | (uint64_t)in[i];
+}
+
+// exclusive prefix (under seg_max_op) of `v` over the workgroup's 256 threads; *total = the workgroup's fold
+__device__ __forceinline__ uint64_t seg_block_excl_scan(uint64_t v, uint64_t* wave_tot /* LDS, 4 entries */, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t incl = v;
+#pragma unroll
+  for (uint32_t off = 1; off < 64u; off <<= 1) {
+    const uint64_t o = __shfl_up(incl, off, 64);
+    if (lane >= off) incl = seg_max_op(o, incl);
+  }
+  uint64_t prev = __shfl_up(incl, 1, 64);
+  if (lane == 0u) prev = 0ull;
+  if (lane == 63u) wave_tot[wave] = incl;
+  __syncthreads();
+  uint64_t base = 0ull, all = 0ull;
+#pragma unroll
+  for (uint32_t w = 0; w < kThreads / 64u; ++w) {
+    const uint64_t t = wave_tot[w];
+    if (w < wave) base = seg_max_op(base, t);
+    all = seg_max_op(all, t);
+  }
+  __syncthreads();
+  *total = all;
+  return seg_max_op(base, prev);
+}
+
+template <bool PAIRS>
+__global__ void __launch_bounds__(kThreads) seg_max_sums_kernel(const uint32_t* __restrict__ in, const uint8_t* __restrict__ head,
+                                                                const uint64_t* __restrict__ pairs, uint64_t n,
+                                                                uint64_t* __restrict__ sums) {
+  __shared__ uint64_t wave_tot[kThreads / 64u];
+  const uint64_t base = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
+  uint64_t s = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < kPer; ++k)
+    if (base + k < n) s = seg_max_op(s, seg_load<PAIRS>(in, head, pairs, base + k));
+  uint64_t total;
+  (void)seg_block_excl_scan(s, wave_tot, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// PAIRS: pairs_out[i] = the EXCLUSIVE prefix of the pairs (in place is fine: a thread reads its elements before it
+// writes them); else out[i] = the inclusive maximum.  offsets == null: a single tile
+template <bool PAIRS>
+__global__ void __launch_bounds__(kThreads) seg_max_apply_kernel(const uint32_t* __restrict__ in, const uint8_t* __restrict__ head,
+                                                                 const uint64_t* pairs, uint32_t* __restrict__ out, uint64_t* pairs_out,
+                                                                 uint64_t n, const uint64_t* __restrict__ offsets) {
+  __shared__ uint64_t wave_tot[kThreads / 64u];
+  const uint64_t base = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
+  uint64_t v[kPer];
+  uint64_t s = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < kPer; ++k) {
+    v[k] = base + k < n ? seg_load<PAIRS>(in, head, pairs, base + k) : 0ull;
+    s = seg_max_op(s, v[k]);
+  }
+  uint64_t total;
+  const uint64_t excl = seg_block_excl_scan(s, wave_tot, &total);
+  uint64_t run = seg_max_op(offsets ? offsets[blockIdx.x] : 0ull, excl);
+#pragma unroll
+  for (uint32_t k = 0; k < kPer; ++k) {
+    if (PAIRS) {
+      if (base + k < n) pairs_out[base + k] = run;
+      run = seg_max_op(run, v[k]);
+    } else {
+      run = seg_max_op(run, v[k]);
+      if (base + k < n) out[base + k] = (uint32_t)run;
+    }
+  }
+}
+
+template <bool PAIRS>
+hipError_t seg_max_impl(const uint32_t* in, const uint8_t* head, uint64_t* pairs, uint32_t* out, uint64_t n, uint64_t* tmp,
+                        hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint64_t tiles = (n + kTile - 1) / kTile;
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  uint64_t* sums = nullptr;
+  if (tiles > 1) {
+    sums = tmp;
+    hipLaunchKernelGGL((seg_max_sums_kernel<PAIRS>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, in, head, (const uint64_t*)pairs, n,
+                       sums);
+    PCK(hipGetLastError());
+    PCK((seg_max_impl<true>(nullptr, nullptr, sums, nullptr, tiles, tmp + ((tiles + 63) & ~63ull), stream)));
+  }
+  hipLaunchKernelGGL((seg_max_apply_kernel<PAIRS>), dim3((uint32_t)tiles), dim3(kThreads), 0, stream, in, head, (const uint64_t*)pairs, out,
+                     pairs, n, (const uint64_t*)sums);
   return hipGetLastError();
 }
 
@@ -247,6 +357,10 @@ hipError_t inclusive_sum_u32(const uint32_t* in, uint32_t* out, uint64_t n, void
 }
 hipError_t exclusive_sum_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, void* tmp, hipStream_t stream) {
   return scan_impl<uint32_t, uint64_t, false>(in, out, n, (uint64_t*)tmp, stream);
+}
+
+hipError_t segmented_inclusive_max_u32(const uint32_t* in, const uint8_t* head, uint32_t* out, uint64_t n, void* tmp, hipStream_t stream) {
+  return seg_max_impl<false>(in, head, nullptr, out, n, (uint64_t*)tmp, stream);
 }
 
 size_t radix_temp_bytes(uint64_t n) {

@@ -15,6 +15,10 @@ hipError_t exclusive_sum_u32(const uint32_t* in, uint32_t* out, uint64_t n, void
 hipError_t inclusive_sum_u32(const uint32_t* in, uint32_t* out, uint64_t n, void* tmp, hipStream_t stream);
 hipError_t exclusive_sum_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, void* tmp, hipStream_t stream);
 
+// Segmented inclusive max-scan: out[i] = max of in[h .. i], h = the last index <= i with head[h] != 0 (or 0 when no
+// head precedes i).  in == out is allowed.  tmp: scan_temp_bytes(n) bytes.
+hipError_t segmented_inclusive_max_u32(const uint32_t* in, const uint8_t* head, uint32_t* out, uint64_t n, void* tmp, hipStream_t stream);
+
 // Stable least-significant-digit radix sort of (key, value) pairs over key bits [0, bits), eight bits per pass:
 // a pass = per-tile digit histogram, one prefix sum over (digit, tile), stable scatter (ranks inside a tile by
 // wave ballots).  Ping-pongs between the two buffer pairs; *result_in_second says where the sorted pairs are.

@@ -26,5 +26,16 @@ void write_bowtie(const char* path, bool sam, const char* cmdline, const std::ve
                   const char* names, const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, const uint64_t* offsets,
                   const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
                   int32_t m, uint64_t* summary);
+// Predict mode (mrg_write_sorted_sam, mrg_write_clusters, mrg_read_counts_from_names); bowtie_out.cpp.  The writers throw
+// std::runtime_error; read_counts_from_names returns the first read whose name has no `_<count>` field, or -1.
+void write_sorted_sam(const char* path, const std::vector<const FmIndex*>& parts, uint64_t n_reads, const char* names,
+                      const uint64_t* names_off, const char* seqs, const uint64_t* seqs_off, uint64_t n_rows, const uint32_t* row_read,
+                      const int32_t* entry, const int32_t* offset, const uint8_t* strand, const uint8_t* mm, const uint8_t* suppressed,
+                      int32_t m, uint64_t* summary);
+void write_clusters(const char* path, const char* sample, const std::vector<const FmIndex*>& parts, uint64_t n_clusters,
+                    const uint32_t* entry, const uint8_t* strand, const uint32_t* start, const uint32_t* end, const uint64_t* seq_off,
+                    const char* seq, const uint64_t* count_sum, const uint32_t* member_off, const uint32_t* members, uint64_t n_reads,
+                    const char* names, const uint64_t* names_off, uint64_t* rows);
+int64_t read_counts_from_names(uint64_t n_reads, const char* names, const uint64_t* names_off, uint32_t* counts);
 
 }  // namespace mrg

@@ -599,6 +599,176 @@ class Engine:
         return (offsets, entry[order].astype(np.int32), pos[order].astype(np.int32), strand[order], mm[order],
                 suppressed)
 
+    def cluster_valid(self, reads, libs, counts, entry_keep=None, threshold=14, strands=2, stratum_mode=STRATUM_ALL, m=0,
+                      seed_len=28, max_mm_seed=0, max_mm_total=2, sorted_rows=False, timings=None):
+        """Predict mode's location clusters of the listing of list_valid (same reads, libraries, entry numbering and
+        policy; `-m` and the best stratum are decided over all parts from the per-read counts, as there), without the
+        alignment rows leaving the device: mrg_list_valid_fill per part, then mrg_cluster_keys / _sort / _scan /
+        _bounds / _assemble (the rule is documented there).  counts: uint32 [n], the copies each read stands for;
+        entry_keep: bool per entry over all parts (None = all), False drops the entry's alignments from the clusters
+        (the reference keeps names containing "chr").
+        Returns a dict of host arrays: entry, strand, start, end (1-based inclusive), seq_off [C + 1], seq (bytes),
+        count_sum (uint64), member_off [C + 1], members (read numbers, cluster after cluster in list order), suppressed
+        [n] bool, n_rows, n_valid (rows on kept entries); clusters are ordered by (entry, strand, start).
+        sorted_rows=True adds "rows" = (read, entry, offset, strand, mm) of every alignment ordered by (entry, offset,
+        strand, read) -- a coordinate-sorted SAM file's order.  timings: a dict, or None; gets count_s / fill_s as
+        list_valid does and the device milliseconds sort_ms / scan_ms / assemble_ms."""
+        import time
+        torch = _torch()
+        n = reads.n
+        dev = self.device
+        st = self._stream_ptr()
+        if int(threshold) < 1:
+            raise ValueError("the overlap threshold must be at least 1 (got %d)" % int(threshold))
+        lids = [self.libs[k] if isinstance(k, str) else int(k) for k in libs]
+        keys = {v: k for k, v in self.libs.items()}
+        bases = np.cumsum([0] + [self.indexes[keys[l]].n_ref for l in lids])
+        n_entries = int(bases[-1])
+        nm = reads.nmask.data_ptr() if reads.nmask is not None else None
+        args = (reads.W, reads.lens.data_ptr(), nm, n)
+        per_lib = []
+        t0 = time.perf_counter()
+        for lid in lids:
+            cnt = torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev)
+            check(self._lib.mrg_list_valid_count(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(seed_len),
+                                                 int(max_mm_seed), int(max_mm_total), cnt.data_ptr(), st))
+            per_lib.append(cnt.cpu().numpy()[:, :n].view(np.uint32).astype(np.int64))
+        if timings is not None:
+            timings["count_s"] = time.perf_counter() - t0
+        tot = np.sum(per_lib, axis=0) if per_lib else np.zeros((4, n), dtype=np.int64)
+        aligned = tot.any(axis=0)
+        best = np.where(aligned, np.argmax(tot > 0, axis=0), 255)
+        cols = np.arange(n)
+        if stratum_mode == STRATUM_BEST:
+            reportable = np.where(aligned, tot[np.minimum(best, 3), cols], 0)
+        else:
+            reportable = tot.sum(axis=0)
+        suppressed = (reportable > m) if m > 0 else np.zeros(n, dtype=bool)
+        write = aligned & ~suppressed
+        part_off = []
+        for c in per_lib:
+            k = c[np.minimum(best, 3), cols] if stratum_mode == STRATUM_BEST else c.sum(axis=0)
+            off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(np.where(write, k, 0), out=off[1:])
+            part_off.append(off)
+        T = int(sum(int(o[-1]) for o in part_off))
+        if T >= 2 ** 32 - 1:
+            raise ValueError("%d alignment rows; the limit is 2^32 - 2" % T)
+        out = dict(suppressed=suppressed, n_rows=T, n_valid=0, entry=np.zeros(0, np.uint32), strand=np.zeros(0, np.uint8),
+                   start=np.zeros(0, np.uint32), end=np.zeros(0, np.uint32), seq_off=np.zeros(1, np.uint64), seq=b"",
+                   count_sum=np.zeros(0, np.uint64), member_off=np.zeros(1, np.uint32), members=np.zeros(0, np.uint32))
+        if sorted_rows:
+            out["rows"] = (np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
+                           np.zeros(0, np.uint8))
+        if T == 0:
+            return out
+
+        def dev_empty(count, dtype):
+            return torch.empty(max(int(count), 1), dtype=dtype, device=dev)
+        best_d = torch.from_numpy(np.where(write, best, 255).astype(np.uint8)).to(dev)
+        ref, pos = dev_empty(T, torch.int32), dev_empty(T, torch.int32)
+        strand, mm = dev_empty(T, torch.uint8), dev_empty(T, torch.uint8)
+        t_fill, row_base, offs_d = 0.0, 0, []
+        for lid, off in zip(lids, part_off):
+            t = int(off[-1])
+            offs_d.append((torch.from_numpy(off).to(dev), row_base, t))
+            if t:
+                sl = slice(row_base, row_base + t)
+                t0 = time.perf_counter()
+                check(self._lib.mrg_list_valid_fill(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(stratum_mode),
+                                                    int(seed_len), int(max_mm_seed), int(max_mm_total), best_d.data_ptr(),
+                                                    offs_d[-1][0].data_ptr(), t, ref[sl].data_ptr(), pos[sl].data_ptr(),
+                                                    strand[sl].data_ptr(), mm[sl].data_ptr(), st))
+                torch.cuda.current_stream(dev).synchronize()
+                t_fill += time.perf_counter() - t0
+            row_base += t
+        if timings is not None:
+            timings["fill_s"] = t_fill
+        max_pos = int(pos[:T].max())
+        if max_pos < 0 or max_pos >= 2 ** 31:
+            raise ValueError("an alignment at offset %d; positions must be below 2^31" % max_pos)
+        pos_bits = max(1, max_pos.bit_length())
+        bits = pos_bits + 1 + max(1, n_entries.bit_length())   # (entry numbers run to n_entries: the masked rows)
+        if bits > 64:
+            raise ValueError("%d entries do not fit the key's %d entry bits" % (n_entries, 63 - pos_bits))
+        counts_d = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32).view(np.int32)).to(dev)
+        keep_d = None
+        if entry_keep is not None:
+            keep = np.ascontiguousarray(entry_keep, dtype=np.uint8)
+            if keep.shape != (n_entries,):
+                raise ValueError("entry_keep must have one flag per entry (%d)" % n_entries)
+            keep_d = torch.from_numpy(keep).to(dev)
+        tmp_b, work_b = C.c_uint64(), C.c_uint64()
+        check(self._lib.mrg_cluster_workspace_bytes(T, C.byref(tmp_b), C.byref(work_b)))
+        tmp = dev_empty(tmp_b.value, torch.uint8)
+        work = dev_empty(work_b.value, torch.uint8)
+        owner = dev_empty(T, torch.int32)
+
+        def sorted_pairs(order, keep_ptr):
+            k0, k1 = dev_empty(T, torch.int64), dev_empty(T, torch.int64)
+            v0, v1 = dev_empty(T, torch.int32), dev_empty(T, torch.int32)
+            for (off_d, base_row, t), ebase in zip(offs_d, bases):
+                if t:
+                    sl = slice(base_row, base_row + t)
+                    check(self._lib.mrg_cluster_keys(self._h, off_d.data_ptr(), n, ref[sl].data_ptr(), pos[sl].data_ptr(),
+                                                     strand[sl].data_ptr(), t, base_row, T, int(ebase), n_entries, pos_bits, order,
+                                                     keep_ptr, k0.data_ptr(), v0.data_ptr(), owner.data_ptr(), st))
+            second = C.c_int32(0)
+            check(self._lib.mrg_cluster_sort(self._h, k0.data_ptr(), k1.data_ptr(), v0.data_ptr(), v1.data_ptr(), T, bits,
+                                             tmp.data_ptr(), tmp_b.value, C.byref(second), st))
+            return (k1, v1) if second.value else (k0, v0)
+
+        def event():
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(torch.cuda.current_stream(dev))
+            return e
+        ev = [event()]
+        skeys, svals = sorted_pairs(0, keep_d.data_ptr() if keep_d is not None else None)
+        ev.append(event())
+        member = dev_empty(T, torch.int32)
+        n_valid, n_clusters = C.c_uint64(), C.c_uint64()
+        check(self._lib.mrg_cluster_scan(self._h, skeys.data_ptr(), svals.data_ptr(), T, owner.data_ptr(), reads.lens.data_ptr(),
+                                         n_entries, pos_bits, int(threshold), work.data_ptr(), work_b.value, tmp.data_ptr(),
+                                         tmp_b.value, member.data_ptr(), C.byref(n_valid), C.byref(n_clusters), st))
+        V, K = int(n_valid.value), int(n_clusters.value)
+        c_entry, c_start, c_end = dev_empty(K, torch.int32), dev_empty(K, torch.int32), dev_empty(K, torch.int32)
+        c_strand = dev_empty(K, torch.uint8)
+        c_moff, c_len, c_soff = dev_empty(K + 1, torch.int32), dev_empty(K + 1, torch.int32), dev_empty(K + 1, torch.int64)
+        total = C.c_uint64()
+        check(self._lib.mrg_cluster_bounds(self._h, skeys.data_ptr(), T, V, K, pos_bits, work.data_ptr(), work_b.value,
+                                           tmp.data_ptr(), tmp_b.value, c_entry.data_ptr(), c_strand.data_ptr(), c_start.data_ptr(),
+                                           c_end.data_ptr(), c_moff.data_ptr(), c_len.data_ptr(), c_soff.data_ptr(),
+                                           C.byref(total), st))
+        ev.append(event())
+        seq = dev_empty(total.value, torch.uint8)
+        c_sum = dev_empty(K, torch.int64)
+        check(self._lib.mrg_cluster_assemble(self._h, skeys.data_ptr(), T, V, K, pos_bits, work.data_ptr(), work_b.value,
+                                             member.data_ptr(), reads.words.data_ptr(), reads.W, reads.lens.data_ptr(), nm, n,
+                                             counts_d.data_ptr(), c_start.data_ptr(), c_soff.data_ptr(), seq.data_ptr(),
+                                             c_sum.data_ptr(), st))
+        ev.append(event())
+        out.update(n_valid=V,
+                   entry=c_entry.cpu().numpy()[:K].view(np.uint32), strand=c_strand.cpu().numpy()[:K],
+                   start=c_start.cpu().numpy()[:K].view(np.uint32), end=c_end.cpu().numpy()[:K].view(np.uint32),
+                   seq_off=c_soff.cpu().numpy()[:K + 1].view(np.uint64), seq=seq.cpu().numpy()[:int(total.value)].tobytes(),
+                   count_sum=c_sum.cpu().numpy()[:K].view(np.uint64), member_off=c_moff.cpu().numpy()[:K + 1].view(np.uint32),
+                   members=member.cpu().numpy()[:V].view(np.uint32))
+        if timings is not None:
+            ev[-1].synchronize()
+            for name, a, b in (("sort_ms", 0, 1), ("scan_ms", 1, 2), ("assemble_ms", 2, 3)):
+                timings[name] = ev[a].elapsed_time(ev[b])
+        if sorted_rows:
+            del skeys, svals
+            skeys, svals = sorted_pairs(1, None)
+            r_read, r_entry, r_pos = dev_empty(T, torch.int32), dev_empty(T, torch.int32), dev_empty(T, torch.int32)
+            r_strand, r_mm = dev_empty(T, torch.uint8), dev_empty(T, torch.uint8)
+            check(self._lib.mrg_cluster_sorted_rows(self._h, skeys.data_ptr(), svals.data_ptr(), T, pos_bits, 1, owner.data_ptr(),
+                                                    mm.data_ptr(), r_read.data_ptr(), r_entry.data_ptr(), r_pos.data_ptr(),
+                                                    r_strand.data_ptr(), r_mm.data_ptr(), st))
+            out["rows"] = (r_read.cpu().numpy()[:T].view(np.uint32), r_entry.cpu().numpy()[:T], r_pos.cpu().numpy()[:T],
+                           r_strand.cpu().numpy()[:T], r_mm.cpu().numpy()[:T])
+        return out
+
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
         mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask
