@@ -70,6 +70,19 @@ int mrg_index_build(const char *const *names, const char *const *seqs,
 /* Build from a FASTA file (multi-line records allowed; name = header up to
  * first whitespace, as bowtie-build records it). */
 int mrg_index_build_fasta(const char *fasta_path, mrg_index **out);
+/* The same two, with the suffix array, the BWT blocks and the suffix-array rows computed on GPU `device` (prefix
+ * doubling over the library's radix sort; csrc/sa_build.hip).  The result is an ordinary host index, every array
+ * identical to the host builder's.  MRG_ERR_NO_DEVICE without a usable gfx950 device (checked before anything is
+ * read); MRG_ERR_NOMEM, with the bytes needed in the message, when the working set (about 33 bytes per base) does
+ * not fit the free device memory.  There is no fallback to the host builder.  The calling thread's current HIP
+ * device is the same after the call as before it. */
+int mrg_index_build_device(int device, const char *const *names, const char *const *seqs,
+                           uint32_t n_ref, mrg_index **out);
+int mrg_index_build_fasta_device(int device, const char *fasta_path, mrg_index **out);
+/* Sort rounds (the first-round sort of 30 bases included) of the device build this THREAD called last: never more
+ * than ceil(log2((n_bases + 1) / 30)) + 1, and 0 when that call failed or the text was empty.  Every device build
+ * resets it on entry, so a value is never left over from an earlier call. */
+uint32_t mrg_index_build_device_rounds(void);
 /* Build from the reference's own library file: `<prefix>.1.ebwt` (bowtie 1), the only form in which
  * miRge.Libs ships its libraries (MAIN:262-281).  Entry names and sequences are recovered from
  * the BWT as `bowtie-inspect` does (SUM:6, RAP:610-611,630, W2C:649) and indexed like a FASTA

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmirge_amd.so")
 
 MRG_MAX_PASSES = 16
 MRG_MAX_WORDS = 8
+MRG_ERR_ARG = -1
 MRG_ERR_NO_DEVICE = -3
 
 
@@ -73,6 +74,10 @@ SIGNATURES = {
     "mrg_index_build": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32,
                                   C.POINTER(C.c_void_p)]),
     "mrg_index_build_fasta": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "mrg_index_build_device": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32,
+                                         C.POINTER(C.c_void_p)]),
+    "mrg_index_build_fasta_device": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "mrg_index_build_device_rounds": (C.c_uint32, []),
     "mrg_index_build_ebwt": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "mrg_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "mrg_index_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),

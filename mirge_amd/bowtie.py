@@ -249,8 +249,11 @@ def build_main(argv):
         return 1
     from .index import FmIndex
     try:
-        FmIndex.from_fasta(args[0]).save(args[1] + ".mrgfm")
-    except (OSError, MirgeAmdError) as e:
+        # MIRGE_AMD_BUILD_GPU=<id>: sort the suffixes on that GPU (a failure there is an error, not a reason to
+        # fall back to the host builder)
+        gpu = os.environ.get("MIRGE_AMD_BUILD_GPU")
+        FmIndex.from_fasta(args[0], device=int(gpu) if gpu else None).save(args[1] + ".mrgfm")
+    except (OSError, ValueError, MirgeAmdError) as e:
         sys.stderr.write("bowtie-build: %s\n" % e)
         return 1
     return 0

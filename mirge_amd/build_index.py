@@ -1,7 +1,8 @@
 """`python -m mirge_amd.build_index lib.fa [more.fa ...] [-o prefix]`
 
 The offline counterpart of `bowtie-build` for this engine: FASTA -> `<prefix>.mrgfm`
-(FM index in the layout of mirge_amd/csrc/fm_index.hpp).  Host-only, no GPU needed.
+(FM index in the layout of mirge_amd/csrc/fm_index.hpp).  Host-only, no GPU needed;
+`--device N` sorts the suffixes on GPU N instead (same files, byte for byte; no fallback).
 `--max-bases N` splits a FASTA at entry boundaries into `<prefix>.partNNN.mrgfm` of at most
 N bases each (the genome for -ai: one index addresses < 2^31 bases and mrg_count_best
 wants <= 600 M per library so its rank table stays in LDS).
@@ -13,6 +14,7 @@ import os
 import sys
 import time
 
+from ._native import MirgeAmdError
 from .index import FmIndex
 
 
@@ -62,7 +64,19 @@ def main(argv=None):
     ap.add_argument("-o", "--output", help="index prefix (only with a single FASTA)")
     ap.add_argument("--max-bases", type=int, default=0,
                     help="split at entry boundaries into <prefix>.partNNN.mrgfm of at most this many bases")
+    ap.add_argument("--device", type=int, default=None,
+                    help="build the suffix array, BWT and rows on this GPU (default: the host builder)")
     args = ap.parse_args(argv)
+    try:
+        return _run(ap, args)
+    except MirgeAmdError as e:
+        if args.device is None:
+            raise
+        sys.stderr.write("build_index: %s\n" % e)
+        return 1
+
+
+def _run(ap, args):
     if args.output and len(args.fasta) != 1:
         ap.error("-o needs exactly one FASTA")
     for fa in args.fasta:
@@ -70,13 +84,13 @@ def main(argv=None):
         t0 = time.time()
         if args.max_bases:
             for k, (names, seqs) in enumerate(split_fasta(fa, args.max_bases)):
-                ix = FmIndex.build(names, seqs)
+                ix = FmIndex.build(names, seqs, device=args.device)
                 out = "%s.part%03d.mrgfm" % (prefix, k)
                 ix.save(out)
                 print("%s: part %d, %d entries, %d bp -> %s (%.1f s)" %
                       (fa, k, ix.info.n_ref, ix.info.n_bases, out, time.time() - t0))
             continue
-        ix = FmIndex.from_fasta(fa)
+        ix = FmIndex.from_fasta(fa, device=args.device)
         ix.save(prefix + ".mrgfm")
         inf = ix.info
         print("%s: %d entries, %d bp, %.1f MB index -> %s.mrgfm (%.1f s)" %

@@ -24,6 +24,7 @@
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
 #include "prims.hpp"
+#include "sa_build.hpp"
 #include "tables.hpp"
 #include "trf_peaks.hpp"
 
@@ -66,6 +67,7 @@ struct mrg_gz {
 namespace {
 
 thread_local std::string g_err;
+thread_local uint32_t g_device_build_rounds = 0;  // mrg_index_build_device_rounds
 
 int fail(int code, const char* fmt, ...) {
   char buf[1024];
@@ -317,6 +319,70 @@ int mrg_index_build_fasta(const char* fasta_path, mrg_index** out) {
     return fail(MRG_ERR_IO, "mrg_index_build_fasta: %s", e.what());
   }
 }
+
+// the device route: same host code, the suffix array and what is made from it by sa_build.hip on `device`
+static int build_on_device(const char* who, int device, bool from_fasta, const char* fasta_path, const char* const* names,
+                           const char* const* seqs, uint32_t n_ref, mrg_index** out) {
+  g_device_build_rounds = 0;
+  int count = 0;
+  hipError_t e = hipGetDeviceCount(&count);
+  if (e != hipSuccess || count <= 0)
+    return fail(MRG_ERR_NO_DEVICE, "%s: no HIP device visible (%s); the device route has no host fallback", who,
+                e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+  if (device < 0 || device >= count) return fail(MRG_ERR_NO_DEVICE, "%s: device %d not in [0,%d)", who, device, count);
+  // the calling thread's current device is the caller's: put it back on every way out
+  struct DeviceScope {
+    int prev = -1;
+    ~DeviceScope() {
+      if (prev >= 0) (void)hipSetDevice(prev);
+    }
+  } scope;
+  HIP_TRY(hipGetDevice(&scope.prev));
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+    return fail(MRG_ERR_NO_DEVICE, "%s: device %d is %s; kernels are built for gfx950 only", who, device, prop.gcnArchName);
+  try {
+    std::vector<std::string> nv, sv;
+    if (from_fasta) {
+      mrg::read_fasta(fasta_path, nv, sv);
+    } else {
+      nv.resize(n_ref);
+      sv.resize(n_ref);
+      for (uint32_t i = 0; i < n_ref; ++i) {
+        if (!names[i] || !seqs[i]) return fail(MRG_ERR_ARG, "%s: entry %u is null", who, i);
+        nv[i] = names[i];
+        sv[i] = seqs[i];
+      }
+    }
+    auto h = std::make_unique<mrg_index>();
+    uint32_t rounds = 0;
+    const mrg::RowBuilder rows = [&rounds](mrg::FmIndex& ix) { mrg::build_rows_device(ix, &rounds); };
+    mrg::build_index(nv, sv, h->ix, &rows);
+    g_device_build_rounds = rounds;
+    *out = h.release();
+    return MRG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(MRG_ERR_NOMEM, "%s: out of memory", who);
+  } catch (const mrg::SaBuildError& e) {
+    return fail(e.no_memory ? MRG_ERR_NOMEM : MRG_ERR_HIP, "%s: %s", who, e.what());
+  } catch (const std::exception& e) {
+    return fail(from_fasta ? MRG_ERR_IO : MRG_ERR_FORMAT, "%s: %s", who, e.what());
+  }
+}
+
+int mrg_index_build_device(int device, const char* const* names, const char* const* seqs, uint32_t n_ref, mrg_index** out) {
+  if (!out || (n_ref && (!names || !seqs))) return fail(MRG_ERR_ARG, "mrg_index_build_device: null argument");
+  return build_on_device("mrg_index_build_device", device, false, nullptr, names, seqs, n_ref, out);
+}
+
+int mrg_index_build_fasta_device(int device, const char* fasta_path, mrg_index** out) {
+  if (!fasta_path || !out) return fail(MRG_ERR_ARG, "mrg_index_build_fasta_device: null argument");
+  return build_on_device("mrg_index_build_fasta_device", device, true, fasta_path, nullptr, nullptr, 0, out);
+}
+
+uint32_t mrg_index_build_device_rounds(void) { return g_device_build_rounds; }
 
 int mrg_index_build_ebwt(const char* prefix, mrg_index** out) {
   if (!prefix || !out) return fail(MRG_ERR_ARG, "mrg_index_build_ebwt: null argument");

@@ -193,13 +193,13 @@ static inline int base_code(char ch) {
 }
 
 static void finish_from_codes(const std::vector<uint8_t>& codes, FmIndex& ix,
-                              std::vector<uint32_t>& sa32) {
+                              std::vector<uint32_t>& sa32, bool rows_elsewhere) {
   // codes: text bases 0..3, length n.
   const uint32_t n = (uint32_t)codes.size();
   ix.n = n;
 
   // suffix array of codes+1 followed by sentinel 0
-  {
+  if (!rows_elsewhere) {
     std::vector<uint8_t> t(n + 1);
     for (uint32_t i = 0; i < n; ++i) t[i] = codes[i] + 1;
     t[n] = 0;
@@ -227,6 +227,13 @@ static void finish_from_codes(const std::vector<uint8_t>& codes, FmIndex& ix,
   ix.super.assign((size_t)nsup * 4, 0);
   uint32_t run[4] = {0, 0, 0, 0}, sup_base[4] = {0, 0, 0, 0};
   ix.primary = 0;
+  // packed text, padded so a 64-bit window can be read at any base
+  const uint32_t words = (n + 15) / 16 + 4;
+  ix.text.assign(words, 0);
+  for (uint32_t p = 0; p < n; ++p)
+    ix.text[p >> 4] |= (uint32_t)codes[p] << ((p & 15) * 2);
+  if (rows_elsewhere) return;  // blocks, super and primary come from the RowBuilder
+
   for (uint32_t i = 0; i <= m; ++i) {
     if ((i & ((1u << kSuperShift) - 1)) == 0 && (i >> kSuperShift) < nsup) {
       for (int c = 0; c < 4; ++c) {
@@ -250,12 +257,6 @@ static void finish_from_codes(const std::vector<uint8_t>& codes, FmIndex& ix,
     b.hi |= (uint32_t)((c >> 1) & 1) << (i & 31);
     ++run[c];
   }
-
-  // packed text, padded so a 64-bit window can be read at any base
-  const uint32_t words = (n + 15) / 16 + 4;
-  ix.text.assign(words, 0);
-  for (uint32_t p = 0; p < n; ++p)
-    ix.text[p >> 4] |= (uint32_t)codes[p] << ((p & 15) * 2);
 }
 
 // k-mer jump tables.  Rows are sorted by suffix, so with the k-mers numbered in the same
@@ -533,7 +534,7 @@ void build_pair_tables(const FmIndex& ix, uint32_t anchor, PairTables& out) {
 }
 
 void build_index(const std::vector<std::string>& names,
-                 const std::vector<std::string>& seqs, FmIndex& ix) {
+                 const std::vector<std::string>& seqs, FmIndex& ix, const RowBuilder* rows) {
   if (names.size() != seqs.size()) throw std::runtime_error("names/seqs size mismatch");
   ix = FmIndex();
   ix.names = names;
@@ -575,7 +576,7 @@ void build_index(const std::vector<std::string>& names,
   ix.seg_start.push_back((uint32_t)codes.size());
 
   std::vector<uint32_t> sa32;
-  finish_from_codes(codes, ix, sa32);
+  finish_from_codes(codes, ix, sa32, rows != nullptr);
 
   // chunk -> segment map for O(1) locate
   const uint32_t nchunk = (ix.n >> 5) + 2;
@@ -589,23 +590,31 @@ void build_index(const std::vector<std::string>& names,
   }
 
   // 8-byte suffix-array rows: position + distance to both ends of its segment
-  std::vector<uint32_t> seg_of(ix.n);
-  for (uint32_t sg = 0; sg < nseg; ++sg)
-    for (uint32_t p = ix.seg_start[sg]; p < ix.seg_start[sg + 1]; ++p) seg_of[p] = sg;
-  ix.sa.resize(sa32.size());
-  for (size_t i = 0; i < sa32.size(); ++i) {
-    const uint32_t p = sa32[i];
-    uint64_t row = p;
-    if (p < ix.n) {
-      const uint32_t sg = seg_of[p];
-      const uint32_t before = std::min<uint32_t>(255u, p - ix.seg_start[sg]);
-      const uint32_t after = std::min<uint32_t>(255u, ix.seg_start[sg + 1] - p);
-      const uint32_t sid = nseg <= 0xFFFFu ? sg : 0xFFFFu;
-      row |= (uint64_t)before << 32 | (uint64_t)after << 40 | (uint64_t)sid << 48;
-    } else {
-      row |= (uint64_t)0xFFFFu << 48;
+  if (rows) {
+    codes = std::vector<uint8_t>();
+    (*rows)(ix);
+    if (ix.sa.size() != (size_t)ix.n + 1 || ix.blocks.size() != (size_t)((ix.n + 1) >> 5) + 1 ||
+        ix.super.size() != ((size_t)((ix.n + 1) >> kSuperShift) + 1) * 4 || ix.primary > ix.n)
+      throw std::runtime_error("row builder left an inconsistent index");
+  } else {
+    std::vector<uint32_t> seg_of(ix.n);
+    for (uint32_t sg = 0; sg < nseg; ++sg)
+      for (uint32_t p = ix.seg_start[sg]; p < ix.seg_start[sg + 1]; ++p) seg_of[p] = sg;
+    ix.sa.resize(sa32.size());
+    for (size_t i = 0; i < sa32.size(); ++i) {
+      const uint32_t p = sa32[i];
+      uint64_t row = p;
+      if (p < ix.n) {
+        const uint32_t sg = seg_of[p];
+        const uint32_t before = std::min<uint32_t>(255u, p - ix.seg_start[sg]);
+        const uint32_t after = std::min<uint32_t>(255u, ix.seg_start[sg + 1] - p);
+        const uint32_t sid = nseg <= 0xFFFFu ? sg : 0xFFFFu;
+        row |= (uint64_t)before << 32 | (uint64_t)after << 40 | (uint64_t)sid << 48;
+      } else {
+        row |= (uint64_t)0xFFFFu << 48;
+      }
+      ix.sa[i] = row;
     }
-    ix.sa[i] = row;
   }
   build_kmer_bits(ix);
   if (ix.n >= kLazyDeriveBases) {

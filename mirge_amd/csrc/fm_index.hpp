@@ -29,6 +29,7 @@
 //   chunk_seg[p>>5] = segment holding text position (p & ~31)
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -83,9 +84,12 @@ struct FmIndex {
   std::vector<uint32_t> seg_start, seg_ref, seg_off, chunk_seg;
 };
 
-// Throws std::runtime_error on malformed input.
+// Fills `blocks`, `super`, `primary` and `sa` of an index whose n, C, text, seg_* and chunk_seg are final (sa_build.hpp).
+using RowBuilder = std::function<void(FmIndex&)>;
+// Throws std::runtime_error on malformed input.  rows: null = the host builder (induced sorting); else the suffix
+// array and everything made from it come from *rows, the rest of the index from the same host code.
 void build_index(const std::vector<std::string>& names,
-                 const std::vector<std::string>& seqs, FmIndex& out);
+                 const std::vector<std::string>& seqs, FmIndex& out, const RowBuilder* rows = nullptr);
 void read_fasta(const std::string& path, std::vector<std::string>& names,
                 std::vector<std::string>& seqs);
 void plan_jump_tables(FmIndex& ix);   // ftab_ks only

@@ -25,7 +25,9 @@ class FmIndex:
 
     # ---- construction --------------------------------------------------
     @classmethod
-    def build(cls, names, seqs):
+    def build(cls, names, seqs, device=None):
+        """device: None = the host builder; an integer = suffix array, BWT and rows on that GPU (every array
+        identical; no fallback: a machine without that GPU raises MirgeAmdError)."""
         lib = _native.load()
         n = len(names)
         if n != len(seqs):
@@ -33,15 +35,26 @@ class FmIndex:
         arr_n = (C.c_char_p * n)(*[s.encode("ascii") for s in names])
         arr_s = (C.c_char_p * n)(*[s.encode("ascii") for s in seqs])
         h = C.c_void_p()
-        check(lib.mrg_index_build(arr_n, arr_s, n, C.byref(h)))
+        if device is None:
+            check(lib.mrg_index_build(arr_n, arr_s, n, C.byref(h)))
+        else:
+            check(lib.mrg_index_build_device(int(device), arr_n, arr_s, n, C.byref(h)))
         return cls(h.value)
 
     @classmethod
-    def from_fasta(cls, path):
+    def from_fasta(cls, path, device=None):
         lib = _native.load()
         h = C.c_void_p()
-        check(lib.mrg_index_build_fasta(os.fsencode(path), C.byref(h)))
+        if device is None:
+            check(lib.mrg_index_build_fasta(os.fsencode(path), C.byref(h)))
+        else:
+            check(lib.mrg_index_build_fasta_device(int(device), os.fsencode(path), C.byref(h)))
         return cls(h.value)
+
+    @staticmethod
+    def last_device_rounds():
+        """Sort rounds of the device build this thread called last, 0 if it failed (mrg_index_build_device_rounds)."""
+        return int(_native.load().mrg_index_build_device_rounds())
 
     @classmethod
     def from_ebwt(cls, prefix):
@@ -61,12 +74,13 @@ class FmIndex:
         return cls(h.value)
 
     @classmethod
-    def open_prefix(cls, prefix, cache=False):
+    def open_prefix(cls, prefix, cache=False, device=None):
         """Resolve a bowtie-style index prefix as the reference passes it around (MAIN:269-281):
         `<prefix>.mrgfm` if built (and not older than its source), else build from `<prefix>.fa`
         (what `bowtie-inspect <prefix>` would print) or from the reference's own `<prefix>.1.ebwt`
         (mirge_amd.ebwt reads names and sequences back out of it).  cache: save what had to be
-        built as `<prefix>.mrgfm` (best effort: a read-only library directory is not an error)."""
+        built as `<prefix>.mrgfm` (best effort: a read-only library directory is not an error).
+        device: build a FASTA's index on that GPU (see `build`); a `.1.ebwt` is always indexed on the host."""
         src = next((prefix + e for e in (".fa", ".fasta", ".1.ebwt") if os.path.isfile(prefix + e)), None)
         built = prefix + ".mrgfm"
         if os.path.isfile(built) and (src is None or os.path.getmtime(built) >= os.path.getmtime(src)):
@@ -78,7 +92,7 @@ class FmIndex:
         if src.endswith(".1.ebwt"):
             ix = cls.from_ebwt(prefix)
         else:
-            ix = cls.from_fasta(src)
+            ix = cls.from_fasta(src, device=device)
         # (an index read back from a `.1.ebwt` is not cached: that reader is validated by round trip
         # only, and a wrong guess must not outlive the run next to the library)
         if cache and not src.endswith(".1.ebwt"):
