@@ -824,6 +824,38 @@ int mrg_cluster_sorted_rows(mrg_ctx *ctx, const uint64_t *d_keys, const uint32_t
                             uint8_t *d_strand, uint8_t *d_mm_out, void *stream);
 
 /*
+ * Direct access to the library's own device primitives (csrc/prims.hip), for tests and diagnostics: the prefix sums,
+ * the segmented max-scan and the radix sort that the collapse, the pair and dictionary builders, the ingest, the
+ * library tables, the suffix-array builder and the clustering above are made of.  Device pointers, asynchronous on
+ * `stream`; n == 0 succeeds and touches nothing.  d_tmp: at least the bytes mrg_prims_temp_bytes reports for n.
+ *   mrg_prims_temp_bytes     scratch of a scan or a segmented max-scan (MRG_PRIMS_SCAN) or of a sort (MRG_PRIMS_SORT)
+ *                            of n elements;
+ *   mrg_prims_scan           d_out[i] = d_in[0] + .. + d_in[i - 1] (MRG_SCAN_EXCLUSIVE_U32, modulo 2^32; _U64: d_out
+ *                            is uint64 and exact) or .. + d_in[i] (MRG_SCAN_INCLUSIVE_U32).  d_in == d_out is allowed
+ *                            for the 32-bit kinds;
+ *   mrg_prims_segmented_max  d_out[i] = max of d_in[h .. i], h = the last index <= i with d_head[h] != 0 (0 when
+ *                            there is none).  d_in == d_out is allowed;
+ *   mrg_prims_radix_sort     stable sort of n < 2^32 - 1 keys of key_bytes (4 or 8) by their bits [0, bits), bits <=
+ *                            8 * key_bytes; key bits at and above `bits` travel with the key and order nothing.  The
+ *                            32-bit values follow their keys; d_vals0 == d_vals1 == NULL sorts keys alone.  The
+ *                            passes ping-pong between the two buffer sets: *in_second = the result is in d_keys1 /
+ *                            d_vals1 (n == 0 or bits == 0: nothing moves, *in_second = 0).
+ */
+#define MRG_PRIMS_SCAN 0
+#define MRG_PRIMS_SORT 1
+#define MRG_SCAN_EXCLUSIVE_U32 0
+#define MRG_SCAN_INCLUSIVE_U32 1
+#define MRG_SCAN_EXCLUSIVE_U64 2
+int mrg_prims_temp_bytes(int32_t kind, uint64_t n, uint64_t *bytes);
+int mrg_prims_scan(mrg_ctx *ctx, int32_t kind, const uint32_t *d_in, void *d_out, uint64_t n, void *d_tmp,
+                   uint64_t tmp_bytes, void *stream);
+int mrg_prims_segmented_max(mrg_ctx *ctx, const uint32_t *d_in, const uint8_t *d_head, uint32_t *d_out,
+                            uint64_t n, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_prims_radix_sort(mrg_ctx *ctx, uint32_t key_bytes, void *d_keys0, void *d_keys1, uint32_t *d_vals0,
+                         uint32_t *d_vals1, uint64_t n, uint32_t bits, void *d_tmp, uint64_t tmp_bytes,
+                         int32_t *in_second, void *stream);
+
+/*
  * Predict mode's two files from HOST arrays (reads and index parts as for mrg_write_bowtie), formatted by worker
  * threads in blocks and written in order:
  *   mrg_write_sorted_sam  `@HD VN:1.0 SO:coordinate`, the @SQ lines of mrg_write_bowtie, then the n_rows aligned lines

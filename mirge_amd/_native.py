@@ -165,6 +165,12 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mrg_cluster_sorted_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mrg_prims_temp_bytes": (C.c_int, [C.c_int32, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mrg_prims_scan": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_prims_segmented_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                          C.c_void_p]),
+    "mrg_prims_radix_sort": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.c_void_p]),
     "mrg_write_sorted_sam": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, C.c_char_p, C.c_void_p, C.c_char_p,
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p]),

@@ -2869,6 +2869,65 @@ int mrg_cluster_sorted_rows(mrg_ctx* ctx, const uint64_t* d_keys, const uint32_t
   return MRG_OK;
 }
 
+// ------------------------------------------------- the primitives, directly (tests and diagnostics)
+int mrg_prims_temp_bytes(int32_t kind, uint64_t n, uint64_t* bytes) {
+  if (!bytes) return fail(MRG_ERR_ARG, "mrg_prims_temp_bytes: null argument");
+  if (kind != MRG_PRIMS_SCAN && kind != MRG_PRIMS_SORT) return fail(MRG_ERR_ARG, "mrg_prims_temp_bytes: unknown kind %d", kind);
+  *bytes = kind == MRG_PRIMS_SCAN ? mrg::prims::scan_temp_bytes(n) : mrg::prims::radix_temp_bytes(n);
+  return MRG_OK;
+}
+
+int mrg_prims_scan(mrg_ctx* ctx, int32_t kind, const uint32_t* d_in, void* d_out, uint64_t n, void* d_tmp, uint64_t tmp_bytes,
+                   void* stream) {
+  if (kind != MRG_SCAN_EXCLUSIVE_U32 && kind != MRG_SCAN_INCLUSIVE_U32 && kind != MRG_SCAN_EXCLUSIVE_U64)
+    return fail(MRG_ERR_ARG, "mrg_prims_scan: unknown kind %d", kind);
+  if (!ctx) return fail(MRG_ERR_ARG, "mrg_prims_scan: null argument");
+  if (n && (!d_in || !d_out || !d_tmp)) return fail(MRG_ERR_ARG, "mrg_prims_scan: null buffers");
+  if (tmp_bytes < mrg::prims::scan_temp_bytes(n)) return fail(MRG_ERR_ARG, "mrg_prims_scan: scratch smaller than mrg_prims_temp_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == MRG_SCAN_EXCLUSIVE_U32)
+    HIP_TRY(mrg::prims::exclusive_sum_u32(d_in, (uint32_t*)d_out, n, d_tmp, st));
+  else if (kind == MRG_SCAN_INCLUSIVE_U32)
+    HIP_TRY(mrg::prims::inclusive_sum_u32(d_in, (uint32_t*)d_out, n, d_tmp, st));
+  else
+    HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(d_in, (uint64_t*)d_out, n, d_tmp, st));
+  return MRG_OK;
+}
+
+int mrg_prims_segmented_max(mrg_ctx* ctx, const uint32_t* d_in, const uint8_t* d_head, uint32_t* d_out, uint64_t n, void* d_tmp,
+                            uint64_t tmp_bytes, void* stream) {
+  if (!ctx) return fail(MRG_ERR_ARG, "mrg_prims_segmented_max: null argument");
+  if (n && (!d_in || !d_head || !d_out || !d_tmp)) return fail(MRG_ERR_ARG, "mrg_prims_segmented_max: null buffers");
+  if (tmp_bytes < mrg::prims::scan_temp_bytes(n))
+    return fail(MRG_ERR_ARG, "mrg_prims_segmented_max: scratch smaller than mrg_prims_temp_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(mrg::prims::segmented_inclusive_max_u32(d_in, d_head, d_out, n, d_tmp, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_prims_radix_sort(mrg_ctx* ctx, uint32_t key_bytes, void* d_keys0, void* d_keys1, uint32_t* d_vals0, uint32_t* d_vals1,
+                         uint64_t n, uint32_t bits, void* d_tmp, uint64_t tmp_bytes, int32_t* in_second, void* stream) {
+  if (key_bytes != 4 && key_bytes != 8) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: keys of %u bytes (4 or 8)", key_bytes);
+  if (bits > 8 * key_bytes) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: %u key bits of %u", bits, 8 * key_bytes);
+  if (!ctx || !in_second) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: null argument");
+  if (n >= 0xffffffffull) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: %llu keys; the limit is 2^32 - 2", (unsigned long long)n);
+  if ((d_vals0 == nullptr) != (d_vals1 == nullptr)) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: one value buffer without the other");
+  if (n && (!d_keys0 || !d_keys1 || !d_tmp)) return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: null buffers");
+  if (tmp_bytes < mrg::prims::radix_temp_bytes(n))
+    return fail(MRG_ERR_ARG, "mrg_prims_radix_sort: scratch smaller than mrg_prims_temp_bytes");
+  HIP_TRY(hipSetDevice(ctx->device));
+  bool second = false;
+  if (key_bytes == 8)
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64((uint64_t*)d_keys0, (uint64_t*)d_keys1, d_vals0, d_vals1, (uint32_t)n, bits, d_tmp,
+                                             (hipStream_t)stream, &second));
+  else
+    HIP_TRY(mrg::prims::radix_sort_pairs_u32((uint32_t*)d_keys0, (uint32_t*)d_keys1, d_vals0, d_vals1, (uint32_t)n, bits, d_tmp,
+                                             (hipStream_t)stream, &second));
+  *in_second = second ? 1 : 0;
+  return MRG_OK;
+}
+
 namespace {
 int index_list(const char* who, const mrg_index* const* parts, uint32_t n_parts, std::vector<const mrg::FmIndex*>* ix) {
   if (n_parts && !parts) return fail(MRG_ERR_ARG, "%s: null argument", who);

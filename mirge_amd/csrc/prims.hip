@@ -1,5 +1,6 @@
 // Device-wide prefix sums, a segmented max-scan and a stable LSD radix sort, written for gfx950 (wave64) -- what
-// collapse.hip, pairs.hip and ingest.hip used to call a library for.
+// collapse.hip, pairs.hip and ingest.hip used to call a library for.  tests/test_gpu_prims.py calls every entry point
+// directly (mrg_prims_* in capi.hip) and compares with tests/prims_model.py.
 //
 // Prefix sum: tiles of 4096 elements (256 threads x 16 consecutive elements).  Level by level: tile sums -> the
 // same scan over the sums -> tile-local scan + the tile's offset.  Three levels cover 2^36 elements.
@@ -235,8 +236,8 @@ hipError_t seg_max_impl(const uint32_t* in, const uint8_t* head, uint64_t* pairs
 
 // ---------------------------------------------------------------- radix sort
 template <class K>
-__global__ void __launch_bounds__(kThreads) radix_hist_kernel(const K* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t n_tiles,
-                                                              uint32_t* __restrict__ counts_t) {
+__global__ void __launch_bounds__(kThreads) radix_hist_kernel(const K* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t mask,
+                                                              uint32_t n_tiles, uint32_t* __restrict__ counts_t) {
   __shared__ uint32_t hist[256];
   hist[threadIdx.x] = 0u;
   __syncthreads();
@@ -245,7 +246,7 @@ __global__ void __launch_bounds__(kThreads) radix_hist_kernel(const K* __restric
 #pragma unroll
   for (uint32_t k = 0; k < kPer; ++k) {
     const uint64_t i = base + (uint64_t)k * 64u;
-    if (i < n) atomicAdd(&hist[(uint32_t)(keys[i] >> shift) & 255u], 1u);
+    if (i < n) atomicAdd(&hist[(uint32_t)(keys[i] >> shift) & mask], 1u);
   }
   __syncthreads();
   counts_t[(size_t)threadIdx.x * n_tiles + blockIdx.x] = hist[threadIdx.x];
@@ -254,7 +255,8 @@ __global__ void __launch_bounds__(kThreads) radix_hist_kernel(const K* __restric
 template <class K, bool VALS>
 __global__ void __launch_bounds__(kThreads) radix_scatter_kernel(const K* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                                  K* __restrict__ keys_out, uint32_t* __restrict__ vals_out, uint32_t n,
-                                                                 uint32_t shift, uint32_t n_tiles, const uint32_t* __restrict__ off_t) {
+                                                                 uint32_t shift, uint32_t mask, uint32_t n_tiles,
+                                                                 const uint32_t* __restrict__ off_t) {
   __shared__ uint32_t wcnt[kThreads / 64u][256];  // d-keys of a wave so far, then: d-keys of the waves in front
   volatile uint32_t* vw = &wcnt[0][0];
   for (uint32_t i = threadIdx.x; i < (kThreads / 64u) * 256u; i += kThreads) wcnt[0][i] = 0u;
@@ -271,7 +273,7 @@ __global__ void __launch_bounds__(kThreads) radix_scatter_kernel(const K* __rest
     const bool live = i < n;
     key[k] = live ? keys_in[i] : (K)0;
     val[k] = (VALS && live) ? vals_in[i] : 0u;
-    const uint32_t d = (uint32_t)(key[k] >> shift) & 255u;
+    const uint32_t d = (uint32_t)(key[k] >> shift) & mask;
     uint64_t peers = __ballot(live);
 #pragma unroll
     for (uint32_t b = 0; b < 8u; ++b) {
@@ -327,15 +329,18 @@ hipError_t radix_impl(K* keys0, K* keys1, uint32_t* vals0, uint32_t* vals1, uint
   uint32_t* vout = vals1;
   bool second = false;
   for (uint32_t shift = 0; shift < bits; shift += 8u) {
-    hipLaunchKernelGGL((radix_hist_kernel<K>), dim3(n_tiles), dim3(kThreads), 0, stream, kin, n, shift, n_tiles, counts);
+    // the last pass of a width that is no multiple of 8 sees only the bits below `bits`: whatever the caller keeps
+    // above them must not order anything.  Both kernels take the same mask, so the scatter stays a permutation.
+    const uint32_t mask = bits - shift < 8u ? (1u << (bits - shift)) - 1u : 255u;
+    hipLaunchKernelGGL((radix_hist_kernel<K>), dim3(n_tiles), dim3(kThreads), 0, stream, kin, n, shift, mask, n_tiles, counts);
     PCK(hipGetLastError());
     PCK((scan_impl<uint32_t, uint32_t, false>(counts, counts, n_counts, scan_tmp, stream)));
     if (vals0)
-      hipLaunchKernelGGL((radix_scatter_kernel<K, true>), dim3(n_tiles), dim3(kThreads), 0, stream, kin, vin, kout, vout, n, shift, n_tiles,
-                         counts);
+      hipLaunchKernelGGL((radix_scatter_kernel<K, true>), dim3(n_tiles), dim3(kThreads), 0, stream, kin, vin, kout, vout, n, shift, mask,
+                         n_tiles, counts);
     else
       hipLaunchKernelGGL((radix_scatter_kernel<K, false>), dim3(n_tiles), dim3(kThreads), 0, stream, kin, (const uint32_t*)nullptr, kout,
-                         (uint32_t*)nullptr, n, shift, n_tiles, counts);
+                         (uint32_t*)nullptr, n, shift, mask, n_tiles, counts);
     PCK(hipGetLastError());
     std::swap(kin, kout);
     std::swap(vin, vout);

@@ -1,5 +1,7 @@
-// Device-wide primitives of this library's own (gfx950, wave64): prefix sums and a stable LSD radix sort.
-// Internal header (collapse.hip, pairs.hip, ingest.hip); everything is asynchronous on `stream`.
+// Device-wide primitives of this library's own (gfx950, wave64): prefix sums, a segmented max-scan and a stable LSD
+// radix sort.  Internal header (collapse.hip, pairs.hip, ingest.hip, libtables.hip, dictbuild.hip, sa_build.hip and the
+// predict-mode clustering in capi.hip); everything is asynchronous on `stream`.  capi.hip also exports every function
+// here as mrg_prims_* for tests/test_gpu_prims.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,7 +21,8 @@ hipError_t exclusive_sum_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t 
 // head precedes i).  in == out is allowed.  tmp: scan_temp_bytes(n) bytes.
 hipError_t segmented_inclusive_max_u32(const uint32_t* in, const uint8_t* head, uint32_t* out, uint64_t n, void* tmp, hipStream_t stream);
 
-// Stable least-significant-digit radix sort of (key, value) pairs over key bits [0, bits), eight bits per pass:
+// Stable least-significant-digit radix sort of (key, value) pairs over key bits [0, bits), eight bits per pass (the
+// last pass takes the bits that remain: key bits at and above `bits` travel with the key and order nothing):
 // a pass = per-tile digit histogram, one prefix sum over (digit, tile), stable scatter (ranks inside a tile by
 // wave ballots).  Ping-pongs between the two buffer pairs; *result_in_second says where the sorted pairs are.
 // vals may be null (keys only).  tmp: radix_temp_bytes(n) bytes.

@@ -55,6 +55,24 @@ def test_null_and_invalid_arguments_are_errors_not_crashes(native_lib):
     bytes_ = C.c_uint64()
     assert L.mrg_cascade_workspace_bytes(1000, C.byref(bytes_)) == 0 and bytes_.value > 4000
     assert L.mrg_cascade_workspace_bytes(1000, None) < 0
+    # the primitives' direct entry points: null pointers, unknown kinds, more key bits than the key has
+    assert L.mrg_prims_temp_bytes(0, 1000, None) < 0
+    assert L.mrg_prims_temp_bytes(2, 1000, C.byref(bytes_)) < 0
+    assert L.mrg_prims_temp_bytes(0, 4096, C.byref(bytes_)) == 0 and bytes_.value >= 512
+    assert L.mrg_prims_temp_bytes(0, 4096 * 4096 + 1, C.byref(bytes_)) == 0 and bytes_.value >= 8 * (4097 + 2)
+    assert L.mrg_prims_temp_bytes(1, 65_537, C.byref(bytes_)) == 0 and bytes_.value >= 4 * 256 * 17
+    assert L.mrg_prims_scan(None, 1, None, None, 10, None, 0, None) < 0
+    assert b"null" in L.mrg_last_error()
+    assert L.mrg_prims_scan(None, 3, None, None, 10, None, 0, None) < 0
+    assert b"kind" in L.mrg_last_error()
+    assert L.mrg_prims_segmented_max(None, None, None, None, 10, None, 0, None) < 0
+    assert b"null" in L.mrg_last_error()
+    second = C.c_int32()
+    assert L.mrg_prims_radix_sort(None, 8, None, None, None, None, 10, 64, None, 0, C.byref(second), None) < 0
+    assert b"null" in L.mrg_last_error()
+    for key_bytes, bits in ((4, 33), (8, 65), (2, 8)):
+        assert L.mrg_prims_radix_sort(None, key_bytes, None, None, None, None, 10, bits, None, 0, C.byref(second), None) < 0
+        assert b"key" in L.mrg_last_error() and b"null" not in L.mrg_last_error()
 
 
 def test_index_file_round_trip_and_rejects_garbage(native_lib, tmp_path):
