@@ -242,6 +242,10 @@ int mrg_ctx_add_library(mrg_ctx *ctx, const mrg_index *ix, int32_t *lib_id);
  * test_gpu_random_worlds.py); measured slower -- 1.10 against 0.67 ms for the 6.4 M reads of 33..40 nt of
  * `bench.py --workload varlen`: a long read's candidate costs two or three dependent text trips where a short one is
  * judged from its 16-byte row -- hence off;
+ * "count_variants" = 1 (default) / 0 / 2: mrg_count_best with one seed mismatch on one-word reads without N answers the
+ * reads that fit it (8 <= largest jump table k <= length <= min(seed_len, 32)) with count_variants_kernel and the rest
+ * with count_kernel / everything with count_kernel / (tests) runs count_variants_kernel ALONE, so that the reads it left
+ * come back with d_best_mm = 254 and an unwritten d_count: which kernel answered a read is then visible;
  * "wide_rows_16", "round_large": see DESIGN.md. */
 int mrg_ctx_set_option(mrg_ctx *ctx, const char *key, int64_t value);
 int mrg_ctx_device_info(const mrg_ctx *ctx, int32_t *n_cu, uint64_t *hbm_bytes,
@@ -489,7 +493,11 @@ int mrg_edit_tally_run(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per
  * Best stratum of every read against ONE library, forward strand only: d_best_mm[r] = fewest
  * mismatches of a valid alignment (255 = the read does not align), d_count[r] = number of
  * alignments reaching it (saturates at 255; also 255 when a seed is too repetitive to be
- * walked).  Replaces the genome bowtie runs of the -ai path (utils/writeDataToCSV.py:1263
+ * walked: more than 4096 suffix-array rows, of which only the first 4096 are looked at).  Such a
+ * read's d_best_mm is what the walked rows gave and may be too high; (255, 255) -- none of them
+ * aligned -- means UNDECIDED, too repetitive, and not "does not align" (255, 0): a caller that
+ * combines libraries must not let another library's answer make such a read unique.
+ * Replaces the genome bowtie runs of the -ai path (utils/writeDataToCSV.py:1263
  * `-n 1 -f -a -3 2` and :1488 `-n 0 -f -a -3 2`), which only ask "is the best hit unique"
  * (:1277-1287) and "does it align" (:1491-1496); the host trims the 3' 2 nt, submits each
  * read and its reverse complement, and sums over the chromosome libraries.

@@ -416,6 +416,9 @@ class EngineGenome:
         self.keys = list(library_keys)
 
     def _best(self, reads, max_mm_seed):
+        """-> (best_mm, count, undecided) over all parts and both strands.  undecided: some part answered
+        (255, 255) for a strand -- a seed too repetitive to be walked and no alignment among the rows that were
+        (include/mirge_amd.h: mrg_count_best); what that part holds for the read is not known."""
         import numpy as np
         from . import pack
         from .engine import ReadSet
@@ -424,26 +427,31 @@ class EngineGenome:
         n = len(reads)
         best_mm = np.full(n, 255, dtype=np.int32)
         count = np.zeros(n, dtype=np.int64)
+        undecided = np.zeros(n, dtype=bool)
         if n == 0:
-            return best_mm, count
+            return best_mm, count, undecided
         words, lens, nmask = pack.pack_reads(both)
         rs = ReadSet(words, lens, nmask, None, device=self.engine.device)
         for key in self.keys:
             mm, cnt = self.engine.count_best(rs, key, seed_len=28, max_mm_seed=max_mm_seed, max_mm_total=2)
             for half in (slice(0, n), slice(n, 2 * n)):
                 m, c = mm[half].astype(np.int32), cnt[half].astype(np.int64)
+                undecided |= (m == 255) & (c == 255)
                 better = m < best_mm
                 same = (m == best_mm) & (m < 255)
                 count = np.where(better, c, np.where(same, count + c, count))
                 best_mm = np.where(better, m, best_mm)
-        return best_mm, count
+        return best_mm, count, undecided
 
     def unique_best(self, reads):
+        """An undecided part makes the read non-unique: a sequence that repetitive there has no unique best hit."""
         reads = list(dict.fromkeys(reads))
-        mm, cnt = self._best(reads, 1)
-        return {r for r, m, c in zip(reads, mm, cnt) if m < 255 and c == 1}
+        mm, cnt, und = self._best(reads, 1)
+        return {r for r, m, c, u in zip(reads, mm, cnt, und) if m < 255 and c == 1 and not u}
 
     def exact_hit(self, reads):
+        """An undecided part counts as a hit: the edited sequence is then taken to occur in the genome and its
+        site leaves the report (W2C:1488-1496), the reading that never reports a site the genome explains."""
         reads = list(dict.fromkeys(reads))
-        mm, _ = self._best(reads, 0)
-        return {r for r, m in zip(reads, mm) if m < 255}
+        mm, _, und = self._best(reads, 0)
+        return {r for r, m, u in zip(reads, mm, und) if m < 255 or u}

@@ -237,7 +237,7 @@ struct mrg_ctx {
   int64_t split_min_len = 16;  // ... and so do not reads shorter than this (the reference's own minimum length, trim_file.py:33; shorter seed regions than 15 bases have no pair tables)
   int64_t stratum0_unit = 0;  // (measured slower, default off) the exact stratum of a 2-mismatch pass behind a seed launch rides in that launch
   int64_t walk_diag = 0;
-  int64_t count_variants = 1;  // mrg_count_best, one seed mismatch: the jump-table variants kernel in front of the pigeonhole kernel
+  int64_t count_variants = 1;  // mrg_count_best, one seed mismatch: the jump-table variants kernel in front of the pigeonhole kernel (2: and no pigeonhole kernel behind it)
   int64_t long_lane = 0;   // round 6: 1 = the reads of 33..63 nt of a split batch ride the dictionary kernels too (their LONG instantiations; measured no faster than the FM kernels: off)
   int64_t walk_cap = 256;  // records a wave may leave behind its stream (<= 256; tests shrink it: beyond it a seed is verified row by row)
   int64_t pos_scan = 1;   // 0 at run time: the seed launches verify a wide interval row by row as before round 6
@@ -832,7 +832,8 @@ int mrg_ctx_set_option(mrg_ctx* ctx, const char* key, int64_t value) {
   } else if (k == "pos_scan") {
     ctx->pos_scan = value != 0;
   } else if (k == "count_variants") {
-    ctx->count_variants = value != 0;
+    if (value < 0 || value > 2) return fail(MRG_ERR_ARG, "count_variants must be 0, 1 or 2");
+    ctx->count_variants = value;
   } else if (k == "walk_cap") {
     if (value < 0 || value > (int64_t)kWalkCap) return fail(MRG_ERR_ARG, "walk_cap must be in [0,256]");
     ctx->walk_cap = value;
@@ -2582,6 +2583,7 @@ int mrg_count_best(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_rea
     const uint32_t vgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->n_cu * 32u));
     HIP_TRY(mrg::launch_count_variants(p, vgrid, (hipStream_t)stream));
     p.only_todo = 1u;
+    if (ctx->count_variants == 2) return MRG_OK;  // (tests: the reads it left keep best_mm 254, their count is not written)
   }
   HIP_TRY(mrg::launch_count(p, words_per_read, grid, lds, (hipStream_t)stream));
   return MRG_OK;

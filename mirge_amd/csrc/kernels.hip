@@ -1814,8 +1814,9 @@ __global__ void __launch_bounds__(kCountThreads) count_kernel(const CountParams 
     }
     if (!LIST) {
       p.best_mm[r] = (uint8_t)best_mm;
+      // (best_mm 255 with count 255: a seed was cut short at max_rows and none of the walked rows aligned -- undecided)
       if (p.count32) p.count32[r] = best_mm == 255u ? 0u : count;
-      else p.count[r] = (uint8_t)(best_mm == 255u ? 0u : count);
+      else p.count[r] = (uint8_t)((best_mm == 255u && count != 255u) ? 0u : count);
     }
   }
 }
@@ -2098,7 +2099,8 @@ __global__ void __launch_bounds__(kCountThreads) count_variants_kernel(const Cou
     }
     if (lane32 == 0u) {
       p.best_mm[r] = (uint8_t)best;
-      const uint32_t c = best == 255u ? 0u : ((sat && !p.count32) ? 255u : cnt);
+      // (a lookup cut short at max_rows: 255 whatever the walked rows gave, (255, 255) = undecided, as count_kernel)
+      const uint32_t c = (sat && !p.count32) ? 255u : (best == 255u ? 0u : cnt);
       if (p.count32) p.count32[r] = best == 255u ? 0u : cnt;
       else p.count[r] = (uint8_t)min(c, 255u);
     }

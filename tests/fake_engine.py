@@ -96,3 +96,22 @@ class OracleEngine:
                 for k, v in a.items():
                     b[k] += v
         return pass_id, ref_id, pos, mm, own
+
+
+class CannedCountEngine:
+    """Engine.count_best answered from a table (TEST INFRASTRUCTURE): `answers[library key][read] = (best_mm, count)`,
+    (255, 0) for a read the table does not hold.  What mirge_amd.a2i.EngineGenome does with the answers of several
+    parts and both strands can then be checked on the CPU; `calls` lists (library key, policy) of every call."""
+
+    def __init__(self, answers):
+        self.device = "cpu"
+        self.answers = answers
+        self.calls = []
+
+    def count_best(self, reads, lib, seed_len=28, max_mm_seed=1, max_mm_total=2):
+        from mirge_amd import pack
+        self.calls.append((lib, seed_len, max_mm_seed, max_mm_total))
+        nm = None if reads.nmask is None else reads.nmask.numpy().view(np.uint64)
+        seqs = pack.unpack_reads(reads.words.numpy().view(np.uint64), reads.lens.numpy(), nm)
+        got = [self.answers[lib].get(s, (255, 0)) for s in seqs]
+        return np.array([g[0] for g in got], dtype=np.uint8), np.array([g[1] for g in got], dtype=np.uint8)

@@ -228,3 +228,29 @@ def test_columnar_path_gives_the_same_a2i_report(golden, native_lib, tmp_path):
     a2i.a_to_i_report(str(tmp_path), golden["sample_list"], log_dic, sub, mir_dic, name_seq,
                       golden["mirMergedNameDic"], golden["removedMiRNAList"], a2i.EngineGenome(eng, keys))
     check_files(golden, tmp_path)
+
+
+def test_an_undecided_genome_part_makes_a_read_non_unique():
+    """mrg_count_best answers (255, 255) when a seed was too repetitive to be walked and none of the rows it did
+    walk aligned (include/mirge_amd.h): that part may hold any number of alignments.  EngineGenome must not let
+    another part's (0, 1) make the read unique, whichever part comes first, on either strand; for the `-n 0`
+    filter the undecided read counts as present in the genome (its site leaves the report)."""
+    from tests.fake_engine import CannedCountEngine
+    read, other, absent = "ACGTTGCAAGGCTTACCGATGG", "TTGACCGTAGGCATCAAGTCAG", "GGGGCATCATACGATCGGACTA"
+    t, t_other = read[:-2], other[:-2]                       # (-3 2: the engine sees the reads without their last 2 nt)
+    for hit in (t, a2i.revcomp(t)):                          # the alignment on the forward / the reverse strand
+        for undecided_first in (True, False):
+            und = {hit: (255, 255), t_other: (0, 1)}
+            dec = {hit: (0, 1)}
+            eng = CannedCountEngine({"u": und, "d": dec})
+            g = a2i.EngineGenome(eng, ["u", "d"] if undecided_first else ["d", "u"])
+            assert g.unique_best([read, other, absent]) == {other}
+            assert g.exact_hit([read, other, absent]) == {read, other}
+            assert [c[1:] for c in eng.calls] == [(28, 1, 2)] * 2 + [(28, 0, 2)] * 2
+    # the same answers with (255, 0) = "does not align" in place of (255, 255): unique, as before
+    g = a2i.EngineGenome(CannedCountEngine({"u": {t: (255, 0), t_other: (0, 1)}, "d": {t: (0, 1)}}), ["u", "d"])
+    assert g.unique_best([read, other, absent]) == {read, other}
+    assert g.exact_hit([read, other, absent]) == {read, other}
+    # a saturated count beside a best_mm is no news: (0, 255) was never unique, (1, 255) loses against (0, 1)
+    g = a2i.EngineGenome(CannedCountEngine({"u": {t: (0, 255), t_other: (1, 255)}, "d": {t_other: (0, 1)}}), ["u", "d"])
+    assert g.unique_best([read, other]) == {other}

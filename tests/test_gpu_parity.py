@@ -423,7 +423,9 @@ def test_list_best_matches_exhaustive_scan(native_lib, oracle_lib):
 def test_count_best_matches_exhaustive_scan(native_lib, oracle_lib):
     """mrg_count_best (the -ai genome filters, W2C:1263/:1488): best mismatch count and its
     multiplicity equal the exhaustive scan, on a library with planted repeats so that one
-    alignment is reachable from several pigeonhole pieces and one read has several best hits."""
+    alignment is reachable from several pigeonhole pieces and one read has several best hits.
+    Its read set (an N, reads of up to 40 nt: two words and an N mask) goes through count_kernel only;
+    count_variants_kernel, which takes one-word reads without N, is covered by test_gpu_count_variants.py."""
     eng, olib, reads, rs = _repeat_world()
     for seed_len, n_seed, n_total in ((28, 1, 2), (28, 0, 2), (28, 2, 2), (20, 1, 1), (64, 0, 0)):
         for opts in ({}, {"wstop": 0, "ftab": 0}):
