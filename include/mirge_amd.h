@@ -488,6 +488,24 @@ int mrg_edit_tally_run(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per
                        uint32_t n_bins, int32_t lib, int32_t canon_pass, int32_t isomir_pass,
                        int32_t isomir_trim5, uint32_t flank5, uint32_t flank3, uint32_t from_base,
                        uint32_t to_base, uint64_t *d_counts, void *stream);
+/*
+ * What the context's last tally launch was (tests and diagnostics; read-only, no device work): both tallies
+ * choose among instantiations of their kernel from the "lds_budget" option, the bin count and the pointers'
+ * alignment, and all of them must count alike.  which = MRG_TALLY_LAUNCH_COUNTS (mrg_tally_run*) or
+ * MRG_TALLY_LAUNCH_EDIT (mrg_edit_tally_run*); a call with n = 0 launches nothing and leaves the record alone, and
+ * so does a call whose launch fails.
+ *   out4[0]  flags: MRG_TALLY_LDS_HIST  the per-entry bins are privatised in LDS (else: global atomics)
+ *                   MRG_TALLY_LDS_LIB   edit tally only: the library's text and entry starts are staged in LDS
+ *                   MRG_TALLY_VEC4      one sample (edit tally: and one-word reads), every array aligned for
+ *                                       16-byte loads: four reads per lane and trip, the rest one by one
+ *   out4[1]  workgroups launched      out4[2]  dynamic LDS bytes      out4[3]  0 (reserved)
+ */
+#define MRG_TALLY_LAUNCH_COUNTS 0
+#define MRG_TALLY_LAUNCH_EDIT 1
+#define MRG_TALLY_LDS_HIST 1u
+#define MRG_TALLY_LDS_LIB 2u
+#define MRG_TALLY_VEC4 4u
+int mrg_ctx_last_tally_launch(const mrg_ctx *ctx, int32_t which, uint32_t *out4);
 
 /*
  * Best stratum of every read against ONE library, forward strand only: d_best_mm[r] = fewest

@@ -15,6 +15,8 @@ MRG_MAX_PASSES = 16
 MRG_MAX_WORDS = 8
 MRG_ERR_ARG = -1
 MRG_ERR_NO_DEVICE = -3
+MRG_TALLY_LAUNCH_COUNTS, MRG_TALLY_LAUNCH_EDIT = 0, 1             # mrg_ctx_last_tally_launch: which
+MRG_TALLY_LDS_HIST, MRG_TALLY_LDS_LIB, MRG_TALLY_VEC4 = 1, 2, 4    # ... and the flags of out4[0]
 
 
 class MirgeAmdError(RuntimeError):
@@ -131,6 +133,7 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mrg_ctx_last_tally_launch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
     "mrg_count_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),

@@ -252,6 +252,7 @@ struct mrg_ctx {
   int64_t fused_step = 0;
   uint64_t* pending_export_out = nullptr;
   hipStream_t pending_export_stream = nullptr;
+  uint32_t last_tally_launch[2][4] = {{0}};  // mrg_ctx_last_tally_launch: [tally, edit tally] x (flags, grid, LDS bytes, 0)
   int64_t device_tables = 1;  // mrg_ctx_add_library: a large library's derived tables (dictionary, wide rows, seed buckets) are filled on the device
   int64_t collapse_fast = 1;  // mrg_collapse_run: batches that fit it take the duplication-aware path (0: always the general sort)
   int64_t seed_impl = -1;  // -1 = per launch (run_seed), 0 = seed_kernel (tiles), 1 = wave_seed_kernel, 2 = the same with more registers
@@ -2321,6 +2322,10 @@ int tally_run_impl(mrg_ctx* ctx, const int8_t* d_pass_id, const int32_t* d_ref_i
   uint32_t per_cu = lds_hist ? (lds * 2 <= 160 * 1024 ? 2u : 1u) : 2u;
   uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)ctx->n_cu * per_cu);
   HIP_TRY(mrg::launch_tally(p, lds_hist, grid, lds_hist ? (uint32_t)lds : 0u, (hipStream_t)stream_));
+  uint32_t* last = ctx->last_tally_launch[MRG_TALLY_LAUNCH_COUNTS];  // (a launch that failed leaves the record alone)
+  last[0] = (lds_hist ? MRG_TALLY_LDS_HIST : 0u) | (p.vec4 ? MRG_TALLY_VEC4 : 0u);
+  last[1] = grid;
+  last[2] = lds_hist ? (uint32_t)lds : 0u;
   return MRG_OK;
 }
 }  // namespace
@@ -2479,6 +2484,10 @@ int edit_tally_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_re
   const uint32_t per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)ctx->n_cu * per_cu);
   HIP_TRY(mrg::launch_edit_tally(p, lds_hist, lds_lib, grid, (uint32_t)lds, (hipStream_t)stream));
+  uint32_t* last = ctx->last_tally_launch[MRG_TALLY_LAUNCH_EDIT];
+  last[0] = (lds_hist ? MRG_TALLY_LDS_HIST : 0u) | (lds_lib ? MRG_TALLY_LDS_LIB : 0u) | (p.vec4 ? MRG_TALLY_VEC4 : 0u);
+  last[1] = grid;
+  last[2] = (uint32_t)lds;
   return MRG_OK;
 }
 }  // namespace
@@ -2508,6 +2517,14 @@ int mrg_edit_tally_run_packed(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t wo
   return edit_tally_impl(ctx, d_reads, words_per_read, d_lens, d_nmask, nullptr, nullptr, nullptr, d_packed, d_quant, d_keep, d_remap, n,
                          n_samples, n_bins, lib, canon_pass, isomir_pass, isomir_trim5, flank5, flank3, from_base, to_base, d_counts,
                          stream);
+}
+
+int mrg_ctx_last_tally_launch(const mrg_ctx* ctx, int32_t which, uint32_t* out4) {
+  if (!ctx || !out4) return fail(MRG_ERR_ARG, "mrg_ctx_last_tally_launch: null argument");
+  if (which != MRG_TALLY_LAUNCH_COUNTS && which != MRG_TALLY_LAUNCH_EDIT)
+    return fail(MRG_ERR_ARG, "mrg_ctx_last_tally_launch: which must be 0 (tally) or 1 (edit tally)");
+  for (int i = 0; i < 4; ++i) out4[i] = ctx->last_tally_launch[which][i];
+  return MRG_OK;
 }
 
 // ------------------------------------------------------------ count best

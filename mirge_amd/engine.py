@@ -419,6 +419,15 @@ class Engine:
             counts.data_ptr(), self._stream_ptr()))
         return counts
 
+    def last_tally_launch(self, edit=False):
+        """Which instantiation the last tally (edit=True: edit tally) launch of this engine ran
+        (mrg_ctx_last_tally_launch): dict(lds_hist, lds_lib, vec4, grid, lds_bytes)."""
+        out = (C.c_uint32 * 4)()
+        which = _native.MRG_TALLY_LAUNCH_EDIT if edit else _native.MRG_TALLY_LAUNCH_COUNTS
+        check(self._lib.mrg_ctx_last_tally_launch(self._h, which, out))
+        return dict(lds_hist=bool(out[0] & _native.MRG_TALLY_LDS_HIST), lds_lib=bool(out[0] & _native.MRG_TALLY_LDS_LIB),
+                    vec4=bool(out[0] & _native.MRG_TALLY_VEC4), grid=int(out[1]), lds_bytes=int(out[2]))
+
     def collapse(self, words, lens, nmask=None, sample=None, n_samples=1, max_len=0, out=None):
         """quantReads (QNT:3-24) on device tensors: raw reads (words int64 [W, n], lens uint8 [n],
         nmask or None, sample int16 [n] or None) -> (ReadSet of the unique reads with their

@@ -52,6 +52,9 @@ def test_null_and_invalid_arguments_are_errors_not_crashes(native_lib):
     assert L.mrg_list_best_fill(None, None, 1, None, None, 0, 0, 28, 1, 2, None, None, 0, None, None, None) < 0
     assert L.mrg_cascade_run(None, None, 1, None, None, 0, None, 0, None, None, None, None, None, None, 0, None) < 0
     assert L.mrg_tally_run(None, None, None, None, 0, 1, 1, 9, 0, 8, None, None) < 0
+    out4 = (C.c_uint32 * 4)()
+    assert L.mrg_ctx_last_tally_launch(None, 0, out4) < 0
+    assert b"mrg_ctx_last_tally_launch: null" in L.mrg_last_error()
     bytes_ = C.c_uint64()
     assert L.mrg_cascade_workspace_bytes(1000, C.byref(bytes_)) == 0 and bytes_.value > 4000
     assert L.mrg_cascade_workspace_bytes(1000, None) < 0
