@@ -747,6 +747,24 @@ int mrg_collapse_run(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_r
                      uint64_t n, uint32_t n_samples, uint32_t max_len, uint64_t cap,
                      uint64_t *d_u_reads, uint8_t *d_u_lens, uint64_t *d_u_nmask, uint32_t *d_quant,
                      uint64_t *d_len_hist, uint64_t *n_unique, void *stream);
+/*
+ * What the context's last mrg_collapse_run did (tests and diagnostics; read-only, no device work): the fast path hands
+ * a batch it does not take to the general path silently, and both give the same arrays.  The record is of the last
+ * call that succeeded (all 0 before the first, and after a call with n = 0); a call that failed leaves it alone.
+ *   out8[0]  path      0 = general path, the fast path was not tried; 1 = the fast path answered; 2 = the fast path
+ *                      declined the batch's shape after its prepass, the general path answered; 3 = a reduce table of
+ *                      the fast path overflowed, the general path answered
+ *   out8[1]  reason    paths 0 and 2: 1 = option "collapse_fast" is 0, 2 = more than one word per read, 3 = an N mask,
+ *                      4 = more than 16 samples, 5 = a pointer not aligned for the wide loads (d_reads 16, d_lens 4,
+ *                      d_sample 8 bytes), 6 = a read beyond 29 nt, 7 = more than 16 distinct lengths,
+ *                      8 = 2 max_len + sample bits > 58; else 0
+ *   out8[2]  n_chunks  workgroups of the prepass and the split      out8[3]  chunk  reads per workgroup
+ *                      (both 0 when the prepass did not run)
+ *   out8[4]  n_hot     keys in the split's LDS hot table            out8[5]  n_pairs  (rest of key, count) pairs the split left
+ *   out8[6]  n_buckets non-empty final buckets the reduce walked    (4 to 6: 0 unless the fast path reached its reduce)
+ *   out8[7]  n_unique  unique reads returned
+ */
+int mrg_ctx_last_collapse(const mrg_ctx *ctx, uint32_t *out8);
 
 /*
  * mapped.csv / unmapped.csv (utils/writeDataToCSV.py:582-619, :1172-1188) streamed from the

@@ -254,6 +254,7 @@ struct mrg_ctx {
   hipStream_t pending_export_stream = nullptr;
   uint32_t last_tally_launch[2][4] = {{0}};  // mrg_ctx_last_tally_launch: [tally, edit tally] x (flags, grid, LDS bytes, 0)
   int64_t device_tables = 1;  // mrg_ctx_add_library: a large library's derived tables (dictionary, wide rows, seed buckets) are filled on the device
+  mrg::CollapseInfo last_collapse;  // mrg_ctx_last_collapse: what the last mrg_collapse_run that succeeded did
   int64_t collapse_fast = 1;  // mrg_collapse_run: batches that fit it take the duplication-aware path (0: always the general sort)
   int64_t seed_impl = -1;  // -1 = per launch (run_seed), 0 = seed_kernel (tiles), 1 = wave_seed_kernel, 2 = the same with more registers
   std::vector<DevLib> libs;
@@ -3378,6 +3379,7 @@ int mrg_collapse_run(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
   if (d_nmask && !d_u_nmask) return fail(MRG_ERR_ARG, "mrg_collapse_run: d_u_nmask required with d_nmask");
   HIP_TRY(hipSetDevice(ctx->device));
   uint32_t nu = 0;
+  mrg::CollapseInfo info;
   // temporaries of the keys-only path (3 x 8 B per read + the sort's own) out of the context's
   // scratch, grown on demand and kept: per-call hipMalloc / hipFree of gigabytes costs milliseconds
   const uint64_t want = n * 40ull + (64ull << 20);
@@ -3391,7 +3393,7 @@ int mrg_collapse_run(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
   }
   hipError_t e = mrg::collapse_reads(d_reads, words_per_read, d_lens, d_nmask, d_sample, (uint32_t)n, n_samples,
                                      max_len, cap, d_u_reads, d_u_lens, d_u_nmask, d_quant, d_len_hist, &nu,
-                                     (hipStream_t)stream, ctx->scratch, ctx->scratch_bytes, ctx->n_cu, ctx->collapse_fast != 0);
+                                     (hipStream_t)stream, ctx->scratch, ctx->scratch_bytes, ctx->n_cu, ctx->collapse_fast != 0, &info);
   if (e == hipErrorInvalidValue)
     return fail(MRG_ERR_ARG, "mrg_collapse_run: cap %llu is smaller than the number of unique reads",
                 (unsigned long long)cap);
@@ -3399,6 +3401,15 @@ int mrg_collapse_run(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
     return fail(MRG_ERR_ARG, "mrg_collapse_run: a sample id is not below n_samples (%u)", n_samples);
   if (e != hipSuccess) return fail(MRG_ERR_HIP, "mrg_collapse_run: %s", hipGetErrorString(e));
   *n_unique = nu;
+  ctx->last_collapse = info;  // (a call that failed leaves the record alone)
+  return MRG_OK;
+}
+
+int mrg_ctx_last_collapse(const mrg_ctx* ctx, uint32_t* out8) {
+  if (!ctx || !out8) return fail(MRG_ERR_ARG, "mrg_ctx_last_collapse: null argument");
+  const mrg::CollapseInfo& c = ctx->last_collapse;
+  const uint32_t v[8] = {c.path, c.reason, c.n_chunks, c.chunk, c.n_hot, c.n_pairs, c.n_buckets, c.n_unique};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
   return MRG_OK;
 }
 

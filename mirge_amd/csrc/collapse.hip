@@ -586,7 +586,9 @@ __global__ void __launch_bounds__(kFastThreads) subdivide_kernel(FastShape f, co
   if (tid == 0) n_tiles_s = 0u;
   const uint32_t L = f.len_of_slot[b >> 8];
   const uint32_t r1 = l1_shift(L) + f.sb;
-  const uint32_t b2 = sub_bits_of(P, r1);
+  // (b2 bits of BASES: a final bucket boundary between two samples of one read -- thousands of pairs of a read of at most
+  // 7 nt that the hot table did not absorb -- would count and emit the read once per bucket)
+  const uint32_t b2 = sub_bits_of(P, r1 - f.sb);
   const uint32_t sh = r1 - b2;
   if (!SCATTER && g == 0 && tid == 0) l1_b2[b] = (uint8_t)b2;
   const size_t at = ((size_t)L * 256u + (b & 255u)) * f.n_chunks;
@@ -925,8 +927,9 @@ hipError_t fast_prepass(const uint64_t* d_reads, const uint8_t* d_lens, const ui
 // written that the general path does not overwrite.  h_len_hist: the length histogram of the batch ([256][S], on the host).
 hipError_t collapse_fast(const uint64_t* d_reads, const uint8_t* d_lens, const uint16_t* smp, uint32_t n, uint32_t n_samples,
                          const std::vector<uint64_t>& h_len_hist, FastPlan& plan, uint64_t cap, uint64_t* d_u_words, uint8_t* d_u_lens,
-                         uint32_t* d_quant, uint32_t* h_n_unique, int n_cu, hipStream_t stream, bool* took) {
+                         uint32_t* d_quant, uint32_t* h_n_unique, int n_cu, hipStream_t stream, bool* took, CollapseInfo& info) {
   *took = false;
+  info.path = 2;  // (until the shape is taken)
   FastShape f;
   std::fill(f.slot_of_len, f.slot_of_len + 64, (uint8_t)0xFF);
   f.n = n;
@@ -938,12 +941,18 @@ hipError_t collapse_fast(const uint64_t* d_reads, const uint8_t* d_lens, const u
     uint64_t c = 0;
     for (uint32_t s = 0; s < n_samples; ++s) c += h_len_hist[(size_t)L * n_samples + s];
     if (!c) continue;
-    if (L > kFastMaxLen || f.n_slots == kMaxLenSlots) return hipSuccess;
+    if (L > kFastMaxLen || f.n_slots == kMaxLenSlots) {
+      info.reason = L > kFastMaxLen ? 6u : 7u;
+      return hipSuccess;
+    }
     f.slot_of_len[L] = (uint8_t)f.n_slots;
     f.len_of_slot[f.n_slots++] = (uint8_t)L;
     max_len = L;
   }
-  if (2u * max_len + f.sb > 58u || f.n_slots == 0) return hipSuccess;
+  if (2u * max_len + f.sb > 58u || f.n_slots == 0) {
+    info.reason = 8;
+    return hipSuccess;
+  }
   f.n_bins = f.n_slots * 256u;
   f.n_chunks = plan.n_chunks;
   f.chunk = plan.chunk;
@@ -1020,7 +1029,12 @@ hipError_t collapse_fast(const uint64_t* d_reads, const uint8_t* d_lens, const u
   uint32_t h_over = 0, h_unique = 0;
   CK(hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, stream));
   CK(hipMemcpyAsync(&h_unique, read_base + n_fb, 4, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(&info.n_hot, n_hot, 4, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(&info.n_pairs, offs + n_ht, 4, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(&info.n_buckets, n_work, 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
+  info.n_hot = std::min(info.n_hot, kHotKeys);
+  info.path = h_over ? 3u : 1u;
   if (h_over) return hipSuccess;  // (general path)
   const uint64_t n_unique = h_unique;
   if (n_unique > cap) return hipErrorInvalidValue;
@@ -1041,7 +1055,10 @@ hipError_t collapse_reads(const uint64_t* d_reads, uint32_t W, const uint8_t* d_
                           uint32_t n_samples, uint32_t max_len, uint64_t cap, uint64_t* d_u_words,
                           uint8_t* d_u_lens, uint64_t* d_u_nmask, uint32_t* d_quant,
                           uint64_t* d_len_hist, uint32_t* h_n_unique, hipStream_t stream, void* arena_base,
-                          uint64_t arena_bytes, int n_cu, bool allow_fast) {
+                          uint64_t arena_bytes, int n_cu, bool allow_fast, CollapseInfo* info_out) {
+  CollapseInfo local_info;
+  CollapseInfo& info = info_out ? *info_out : local_info;
+  info = CollapseInfo();
   Arena arena;
   arena.base = (char*)arena_base;
   arena.size = arena_base ? (size_t)arena_bytes : 0;
@@ -1063,19 +1080,23 @@ hipError_t collapse_reads(const uint64_t* d_reads, uint32_t W, const uint8_t* d_
   // take the general path: advisor, round 5)
   const bool aligned = ((uintptr_t)d_reads % 16u == 0u) && ((uintptr_t)d_lens % 4u == 0u) && (!smp || (uintptr_t)smp % 8u == 0u);
   const bool try_fast = W == 1 && !d_nmask && allow_fast && n_samples <= 16u && aligned;
+  info.reason = !allow_fast ? 1u : W != 1 ? 2u : d_nmask ? 3u : n_samples > 16u ? 4u : !aligned ? 5u : 0u;
   if (try_fast) {
     // one pass for the histogram, the sample bound and the raw counts the fast path partitions by (K0)
     const size_t mark = arena.used;
     FastPlan plan;
     DevBuf stmp;
     CK(fast_prepass(d_reads, d_lens, smp, n, n_samples, d_len_hist, stream, &plan, &stmp));
+    info.n_chunks = plan.n_chunks;
+    info.chunk = plan.chunk;
     uint32_t h_ms = 0;
     CK(hipMemcpyAsync(&h_ms, plan.max_sample.p, 4, hipMemcpyDeviceToHost, stream));
     CK(hipMemcpyAsync(h_hist.data(), d_len_hist, h_hist.size() * 8, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
     if (smp && h_ms >= n_samples) return hipErrorInvalidDevicePointer;  // (mapped to MRG_ERR_ARG by the C-ABI)
     bool took = false;
-    CK(collapse_fast(d_reads, d_lens, smp, n, n_samples, h_hist, plan, cap, d_u_words, d_u_lens, d_quant, h_n_unique, n_cu, stream, &took));
+    CK(collapse_fast(d_reads, d_lens, smp, n, n_samples, h_hist, plan, cap, d_u_words, d_u_lens, d_quant, h_n_unique, n_cu, stream, &took, info));
+    info.n_unique = *h_n_unique;
     if (took) return hipSuccess;
     arena.used = mark;
   } else {
@@ -1158,6 +1179,7 @@ hipError_t collapse_reads(const uint64_t* d_reads, uint32_t W, const uint8_t* d_
   CK(hipGetLastError());
   CK(hipStreamSynchronize(stream));
   *h_n_unique = n_unique;
+  info.n_unique = n_unique;
   return hipSuccess;
 }
 

@@ -553,12 +553,20 @@ hipError_t launch_pair_wave(const MatchParams& p, uint32_t grid, hipStream_t str
 hipError_t launch_tally(const TallyParams& p, bool lds_hist, uint32_t grid,
                         uint32_t lds_bytes, hipStream_t stream);
 // collapse.hip: raw reads -> unique reads + per-sample counts + length histogram
+// What a call did (mrg_ctx_last_collapse documents the values): filled from what the call brings back to the host anyway.
+struct CollapseInfo {
+  uint32_t path = 0, reason = 0;      // which path answered, and why the fast path did not
+  uint32_t n_chunks = 0, chunk = 0;   // the prepass's plan (0: it did not run)
+  uint32_t n_hot = 0, n_pairs = 0, n_buckets = 0;  // the fast path up to its reduce (0: it did not get there)
+  uint32_t n_unique = 0;
+};
 hipError_t collapse_reads(const uint64_t* d_reads, uint32_t W, const uint8_t* d_lens,
                           const uint64_t* d_nmask, const uint16_t* d_sample, uint32_t n,
                           uint32_t n_samples, uint32_t max_len, uint64_t cap, uint64_t* d_u_words,
                           uint8_t* d_u_lens, uint64_t* d_u_nmask, uint32_t* d_quant,
                           uint64_t* d_len_hist, uint32_t* h_n_unique, hipStream_t stream, void* arena_base = nullptr,
-                          uint64_t arena_bytes = 0, int n_cu = 0, bool allow_fast = true);  // arena: device scratch the temporaries are carved from
+                          uint64_t arena_bytes = 0, int n_cu = 0, bool allow_fast = true,  // arena: device scratch the temporaries are carved from
+                          CollapseInfo* info = nullptr);
 hipError_t launch_count_variants(const CountParams& p, uint32_t grid, hipStream_t stream);
 hipError_t launch_count(const CountParams& p, uint32_t words_per_read, uint32_t grid, uint32_t lds_bytes,
                         hipStream_t stream);

@@ -464,6 +464,15 @@ class Engine:
                                  quant[:U], 0, int(max_len) if max_len else 255)
         return rs, hist
 
+    def last_collapse(self):
+        """What the last collapse of this engine that succeeded did (mrg_ctx_last_collapse): dict(path, reason, n_chunks,
+        chunk, n_hot, n_pairs, n_buckets, n_unique).  path 0 = general path, fast path not tried; 1 = the fast path
+        answered; 2 = it declined the batch's shape after its prepass; 3 = one of its reduce tables overflowed (2 and 3:
+        the general path answered).  reason says why for paths 0 and 2 (include/mirge_amd.h lists the values)."""
+        out = (C.c_uint32 * 8)()
+        check(self._lib.mrg_ctx_last_collapse(self._h, out))
+        return dict(zip(("path", "reason", "n_chunks", "chunk", "n_hot", "n_pairs", "n_buckets", "n_unique"), (int(x) for x in out)))
+
     def expand_compact(self, bits, runs, quant8=None, esc=None, n_samples=1, out=None):
         """mrg_expand_compact: the compact wire form of a host-resident collapsed read set
         (pack.compact_read_set; bits int64 [n_words] and quant8 uint8 [n, S] / esc int32 [k, 2] already on

@@ -55,6 +55,9 @@ def test_null_and_invalid_arguments_are_errors_not_crashes(native_lib):
     out4 = (C.c_uint32 * 4)()
     assert L.mrg_ctx_last_tally_launch(None, 0, out4) < 0
     assert b"mrg_ctx_last_tally_launch: null" in L.mrg_last_error()
+    out8 = (C.c_uint32 * 8)()
+    assert L.mrg_ctx_last_collapse(None, out8) < 0
+    assert b"mrg_ctx_last_collapse: null" in L.mrg_last_error()
     bytes_ = C.c_uint64()
     assert L.mrg_cascade_workspace_bytes(1000, C.byref(bytes_)) == 0 and bytes_.value > 4000
     assert L.mrg_cascade_workspace_bytes(1000, None) < 0
