@@ -942,6 +942,56 @@ int mrg_write_isomir_tables(const char *isomirs_path, const char *samples_path, 
                             uint32_t n_groups, const double *filtered, uint64_t *rows);
 
 /*
+ * `annotate -gff`: the per-sample <sample>_isomiRs.gff files from the arrays, without one Python record per read.  The two
+ * calls replace updateIsomiRDic / updateIsomiRDic2 with fillTerminal, analyzeAlignment, make_cigar and make_id
+ * (runAnnotationPipeline.py, RAP:86-446) and the writer loop of writeDataToCSV.py (W2C:621-646); mirge_amd/isomir.py holds
+ * the Python model (classify_alignment, write_isomir_gff) whose results they reproduce exactly.
+ *
+ * mrg_isomir_classify   DEVICE arrays of a cascade (reads [W][stride], W in {1, 2, 4, 8}; d_nmask or NULL; pass_id, ref_id,
+ *                       pos) and the HOST tables of mirge_amd.isomir.entry_table, which the call uploads:
+ *                         desc    int32 [n_entries][5] per miRNA library entry: first word of its precursor in text /
+ *                                 nplane, bases of the precursor, m0 = first occurrence of the mature sequence in it, bases
+ *                                 of the mature sequence, status (0 = ok, 1 = mature not in the precursor: the read is
+ *                                 dropped, 2 = unresolvable: the Python route raises for a read on this entry);
+ *                         text    the precursors, 2 bits per base as the reads, each from a word boundary;
+ *                         nplane  same shape, bit 2i set = base i is no ACGT: code 0 = N (equals a read's N), code 1 = any
+ *                                 other character (equals nothing).
+ *                       Rows: the reads with pass_id == canon_pass in array order, then those with pass_id == isomir_pass
+ *                       in array order (flags, an exclusive prefix sum and a scatter on the device).  counts[0..1] (HOST)
+ *                       = the two numbers of rows.  Capacity as for mrg_list_best_fill: rows >= cap are not written, so a
+ *                       call with cap = 0 (output pointers may be NULL) only counts, and counts[0] + counts[1] > cap says
+ *                       that the output is truncated.  Row k: d_idx[k] = the read, d_rec[k][8] =
+ *                         [0] pre_start = r0 + 1, [1] pre_end = r1 (the read at [r0, r1) on the precursor's axis: r0 =
+ *                             m0 - 2 + pos, one less for the isomiR pass; either may lie outside the precursor),
+ *                         [2] iso_5p value m0 - r0 (0: none), [3] iso_3p or iso_add value r1 - m1 (0: none),
+ *                         [4] kind | snp << 8 | add << 16: kind 0 = dropped, 1 = ref_miRNA, 2 = isomiR, 3 = the entry is
+ *                             unresolvable, 4 = ref_id / pos / length out of range; snp 0 = none, 1 = iso_snp, 2 = _seed,
+ *                             3 = _central_offset, 4 = _central, 5 = central_supp; add = [3] is an iso_add,
+ *                         [5] leading | trailing << 16 read bases outside the precursor (the CIGAR's I columns),
+ *                         [6] the entry, [7] 0,
+ *                       d_mask[k][ceil(32 W / 64)]: bit i = read base i differs from the PRECURSOR at r0 + i (character
+ *                       equality: N equals N, a position outside the precursor equals nothing).  kernel_ms (HOST, or NULL):
+ *                       the time of the classification kernel alone, between two events.  Synchronises `stream`.
+ * mrg_write_isomir_gff  HOST arrays: the reads and quant [n][n_samples], idx / rec / mask [k] as above, the entries' names
+ *                       and precursor names.  Writes paths[s] for every sample: the four header lines (source; coldata[s]),
+ *                       then one line per row with quant[idx][s] >= 1 and kind 1 or 2, in row order (kind 0 is skipped, any
+ *                       other is MRG_ERR_ARG).  rows[s] (or NULL) = lines of sample s.  Blocks are formatted by worker
+ *                       threads (MIRGE_AMD_TABLE_THREADS, as for the other writers; MIRGE_AMD_GFF_BLOCK_ROWS = rows per block,
+ *                       default 32768, lowered by tests so that small inputs span several blocks); the bytes depend on neither.
+ */
+int mrg_isomir_classify(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride,
+                        const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n, const int8_t *d_pass_id,
+                        const int32_t *d_ref_id, const int32_t *d_pos, int32_t canon_pass, int32_t isomir_pass,
+                        const int32_t *desc, uint64_t n_entries, const uint64_t *text, const uint64_t *nplane,
+                        uint64_t text_words, uint64_t cap, uint32_t *d_idx, int32_t *d_rec, uint64_t *d_mask,
+                        uint64_t *counts, float *kernel_ms, void *stream);
+int mrg_write_isomir_gff(const char *const *paths, const char *const *coldata, uint32_t n_samples, const char *source,
+                         const uint64_t *reads, uint32_t words_per_read, uint64_t stride, const uint8_t *lens,
+                         const uint64_t *nmask, uint64_t n, const uint32_t *quant, const uint32_t *idx, const int32_t *rec,
+                         const uint64_t *mask, uint64_t k, const char *const *entry_names, const char *const *pre_names,
+                         uint64_t n_entries, uint64_t *rows);
+
+/*
  * -trf: density-peak clustering (Rodriguez-Laio) of the per-sample tRF reports, the O(n^2) parts of
  * utils/writeDataToCSV.py (W2C) :802-1088 for every (sample, tRNA) group of one run at once.
  * Group g owns rows [off[g], off[g+1]) (off: HOST array of n_groups + 1, off[0] = 0), in the order of its

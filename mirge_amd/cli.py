@@ -48,6 +48,8 @@ def build_parser():
     p.add_argument("-cpu", dest="cpu", metavar="<int>", default="1")
     p.add_argument("-ai", dest="a_to_i", action="store_true")
     p.add_argument("-gff", dest="gff_output", action="store_true")
+    p.add_argument("--gff-host", dest="gff_host", action="store_true",
+                   help="extension: -gff through the per-read Python records instead of the GPU classification (same files)")
     p.add_argument("-trf", dest="trf_output", action="store_true")
     p.add_argument("--gpu", type=int, default=0, help="device index (default 0)")
     p.add_argument("--device-ingest", action="store_true",
@@ -455,13 +457,27 @@ def annotate_main(args, engine_factory=None, materialize=False):
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())
     long_mirna = long_res is not None and bool(np.isin(np.asarray(long_res[2]), (CANON_PASS, ISOMIR_PASS)).any())
-    need_records = args.gff_output or args.trf_output or args.a_to_i or (args.diff_isomirs and long_mirna)
+    # -gff: classified on the GPU and written from the arrays (Engine.isomir_classify, columnar.write_isomir_gff) unless
+    # a read beyond 255 nt, which the packed arrays do not hold, was claimed by a miRNA pass, or --gff-host asks for the records
+    gff_records = args.gff_output and (long_mirna or args.gff_host)
+    need_records = gff_records or args.trf_output or args.a_to_i or (args.diff_isomirs and long_mirna)
     sub, align = {}, {}
     if need_records:
         sub, align = columnar.read_subset(h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, h_pos, h_mm, npp, want, spike)
         if long_res is not None:
             columnar.add_long_records(sub, align, long_res, npp, want, spike)
-    if args.gff_output:   # RAP:609-619, :653-656
+    if args.gff_output and not gff_records:   # RAP:609-619, :653-656 and W2C:621-646 from the arrays
+        from . import isomir
+        mirna_ix = engine.indexes["mirna"]
+        table = isomir.entry_table(npp[CANON_PASS], [mirna_ix.sequence(i) for i in range(mirna_ix.n_ref)],
+                                   engine.indexes["hairpin"].name_seq_dict(), pre_name, db)
+        if world > 1:   # (the gathered host arrays)
+            rows = engine.isomir_classify(table, h_words, h_lens, h_nmask, h_pass, h_ref, h_pos)
+        else:
+            rows = engine.isomir_classify(table, shard.words, shard.lens, shard.nmask, res.pass_id, res.ref_id, res.pos)
+        columnar.write_isomir_gff(outdir, sample_list, h_words, h_lens, h_nmask, h_quant, rows[0], rows[1], rows[2], table,
+                                  npp[CANON_PASS], db)
+    elif args.gff_output:
         from . import isomir
         hairpin_seqs = engine.indexes["hairpin"].name_seq_dict()
         mirna_seqs = engine.indexes["mirna"].name_seq_dict()

@@ -15,6 +15,8 @@ downstream consumers actually look at are turned into the reference's shapes:
                        passes 0 / 8 feed the isomiR tables, the GFF and the -ai report, passes 2 / 3
                        the tRF tables -- none of them ever looks at another read
   isomir_dic           the grouping write_mapped_csv builds on the way (W2C:588-606)
+  write_isomir_gff     the per-sample GFF files from the rows of Engine.isomir_classify (W2C:621-646;
+                       mrg_write_isomir_gff)
   mirna_read_subset    the miRNA-claimed subset, optionally only what the -ai grouping keeps
   full_seq_dic         everything as the reference's seqDic (small inputs, tests)
 """
@@ -195,6 +197,37 @@ def write_isomir_tables(isomir_path, sample_path, sample_list, words, lens, nmas
         None if nm is None else nm.ctypes.data, n, pass_id.ctypes.data, ref_id.ctypes.data, quant.ctypes.data, S,
         CANON_PASS, ISOMIR_PASS, group_of.ctypes.data, len(mirna_names), arr, len(gnames), filtered.ctypes.data, C.byref(k)))
     return int(k.value)
+
+
+def write_isomir_gff(outdir, sample_list, words, lens, nmask, quant, idx, rec, mask, table, mirna_names, database):
+    """<sample>_isomiRs.gff of every sample (W2C:621-646) from the arrays and the rows of Engine.isomir_classify, by the
+    native writer (mrg_write_isomir_gff): the files isomir.write_isomir_gff writes for the content build_isomir_content
+    builds, byte for byte.  A row on an entry the Python route cannot resolve raises that route's exception.  Returns the
+    lines written per sample."""
+    from . import isomir
+    lib = _native.load()
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, 8)
+    isomir.raise_unresolved(table, rec)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    quant = np.ascontiguousarray(quant, dtype=np.uint32)
+    S = quant.shape[1] if quant.ndim == 2 else 1
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    mask = np.ascontiguousarray(mask, dtype=np.uint64)
+    source = "miRBase22" if database == "miRBase" else database + "2.0"
+    stems = [os.path.splitext(s)[0] for s in sample_list]
+    paths = (C.c_char_p * S)(*[os.fsencode(os.path.join(outdir, st + "_isomiRs.gff")) for st in stems])
+    coldata = (C.c_char_p * S)(*[st.encode() for st in stems])
+    M = len(mirna_names)
+    names = (C.c_char_p * max(M, 1))(*[x.encode() for x in mirna_names])
+    pres = (C.c_char_p * max(M, 1))(*[x.encode() for x in table.pre_names])
+    rows = (C.c_uint64 * S)()
+    check(lib.mrg_write_isomir_gff(
+        paths, coldata, S, source.encode(), words.ctypes.data, W, n, lens.ctypes.data, None if nm is None else nm.ctypes.data,
+        n, quant.ctypes.data, idx.ctypes.data, rec.ctypes.data, mask.ctypes.data, idx.shape[0], names, pres, M, rows))
+    return [int(x) for x in rows]
 
 
 def mirna_read_subset(engine, cols, words, lens, nmask, quant, log_dic=None, spike_in=False, for_a2i=False):

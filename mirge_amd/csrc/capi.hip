@@ -13,6 +13,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -21,6 +22,7 @@
 #include "pgzip.hpp"
 #include "fastq.hpp"
 #include "fm_index.hpp"
+#include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
 #include "prims.hpp"
@@ -3453,6 +3455,132 @@ int mrg_write_isomir_tables(const char* isomirs_path, const char* samples_path, 
     return MRG_OK;
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "mrg_write_isomir_tables: %s", e.what());
+  }
+}
+
+// ------------------------------------------------------------- -gff
+int mrg_isomir_classify(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                        const uint64_t* d_nmask, uint64_t n, const int8_t* d_pass_id, const int32_t* d_ref_id, const int32_t* d_pos,
+                        int32_t canon_pass, int32_t isomir_pass, const int32_t* desc, uint64_t n_entries, const uint64_t* text,
+                        const uint64_t* nplane, uint64_t text_words, uint64_t cap, uint32_t* d_idx, int32_t* d_rec, uint64_t* d_mask,
+                        uint64_t* counts, float* kernel_ms, void* stream) {
+  if (!ctx || !counts) return fail(MRG_ERR_ARG, "mrg_isomir_classify: null argument");
+  if (kernel_ms) *kernel_ms = 0.0f;
+  if (n && (!d_reads || !d_lens || !d_pass_id || !d_ref_id || !d_pos)) return fail(MRG_ERR_ARG, "mrg_isomir_classify: null buffers");
+  if ((n_entries && !desc) || (text_words && (!text || !nplane))) return fail(MRG_ERR_ARG, "mrg_isomir_classify: null tables");
+  if (cap && (!d_idx || !d_rec || !d_mask)) return fail(MRG_ERR_ARG, "mrg_isomir_classify: null output buffers");
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "mrg_isomir_classify: words_per_read must be 1, 2, 4 or 8");
+  if (stride < n || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_isomir_classify: bad stride / n");
+  if (canon_pass == isomir_pass || canon_pass < 0 || isomir_pass < 0 || canon_pass > 127 || isomir_pass > 127)
+    return fail(MRG_ERR_ARG, "mrg_isomir_classify: the two passes must differ and lie in 0..127");
+  if (n_entries >= (1ull << 31) || text_words >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_isomir_classify: tables too large");
+  // the kernel trusts the table: every resolvable entry's precursor lies inside the text, its mature inside the precursor
+  for (uint64_t e = 0; e < n_entries; ++e) {
+    const int32_t* d = desc + e * mrg::kIsoDescInts;
+    if (d[mrg::kIsoDescStatus] < 0 || d[mrg::kIsoDescStatus] > 2)
+      return fail(MRG_ERR_ARG, "mrg_isomir_classify: entry %llu has status %d", (unsigned long long)e, d[mrg::kIsoDescStatus]);
+    if (d[mrg::kIsoDescStatus] != 0) continue;
+    const int64_t off = d[mrg::kIsoDescOff], len = d[mrg::kIsoDescLen], m0 = d[mrg::kIsoDescM0], mat = d[mrg::kIsoDescMat];
+    if (off < 0 || len < 0 || len > (1 << 24) || m0 < 0 || mat < 0 || m0 + mat > len || off + (len + 31) / 32 > (int64_t)text_words)
+      return fail(MRG_ERR_ARG, "mrg_isomir_classify: entry %llu lies outside the precursor table", (unsigned long long)e);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  counts[0] = counts[1] = 0;
+  if (n == 0) return MRG_OK;
+  // context scratch: [entry table | text | N plane | flags -> offsets (2n + 1) | scan scratch], 256-byte aligned pieces
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  const uint64_t n_flags = 2 * n + 1;
+  const uint64_t o_desc = 0, o_text = o_desc + up(n_entries * mrg::kIsoDescInts * sizeof(int32_t)),
+                 o_npl = o_text + up(text_words * sizeof(uint64_t)), o_flags = o_npl + up(text_words * sizeof(uint64_t)),
+                 o_tmp = o_flags + up(n_flags * sizeof(uint32_t)), need_bytes = o_tmp + up(mrg::prims::scan_temp_bytes(n_flags));
+  if (ctx->scratch_bytes < need_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(ctx->scratch);
+    ctx->scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->scratch, need_bytes));
+    ctx->scratch_bytes = need_bytes;
+  }
+  char* base = (char*)ctx->scratch;
+  uint32_t* flags = (uint32_t*)(base + o_flags);
+  // select and order: the exclusive sums of [canon flags | isomiR flags | 0] are the rows.  (A caller that counts first and
+  // fills then, as Engine.isomir_classify does, runs this stage twice: two launches and a scan over 2n + 1 flags, small next
+  // to the download of the rows; the offsets are not kept between calls because another call may use the scratch.)
+  HIP_TRY(mrg::iso_flags_launch(d_pass_id, n, canon_pass, isomir_pass, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n_flags, base + o_tmp, st));
+  uint32_t ends[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&ends[0], flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&ends[1], flags + 2 * n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  counts[0] = ends[0];
+  counts[1] = ends[1] - ends[0];
+  const uint64_t rows = std::min<uint64_t>(ends[1], cap);
+  if (rows == 0) return MRG_OK;
+  HIP_TRY(mrg::iso_scatter_launch(d_pass_id, n, canon_pass, isomir_pass, flags, cap, d_idx, st));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(base + o_desc, desc, n_entries * mrg::kIsoDescInts * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (text_words) {
+    HIP_TRY(hipMemcpyAsync(base + o_text, text, text_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(base + o_npl, nplane, text_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  }
+  mrg::IsoClassifyParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.ref_id = d_ref_id;
+  p.pos = d_pos;
+  p.stride = stride;
+  p.W = words_per_read;
+  p.idx = d_idx;
+  p.rows = (uint32_t)rows;
+  p.n_canon = ends[0];
+  p.desc = (const int32_t*)(base + o_desc);
+  p.n_entries = (uint32_t)n_entries;
+  p.text = (const uint64_t*)(base + o_text);
+  p.nplane = (const uint64_t*)(base + o_npl);
+  p.text_words = (uint32_t)text_words;
+  p.rec = d_rec;
+  p.mask = (uint32_t*)d_mask;
+  p.mask_words = (words_per_read + 1) / 2;
+  // kernel_ms: classify_kernel alone, between two events on the stream
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipError_t e = hipSuccess;
+  if (kernel_ms) {
+    e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, st);
+  }
+  if (e == hipSuccess) e = mrg::iso_classify_launch(p, st);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev1, st);
+  // (the tables were copied from pageable host memory, which the caller may free on return)
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, ev0, ev1);
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  HIP_TRY(e);
+  return MRG_OK;
+}
+
+int mrg_write_isomir_gff(const char* const* paths, const char* const* coldata, uint32_t n_samples, const char* source,
+                         const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens, const uint64_t* nmask,
+                         uint64_t n, const uint32_t* quant, const uint32_t* idx, const int32_t* rec, const uint64_t* mask, uint64_t k,
+                         const char* const* entry_names, const char* const* pre_names, uint64_t n_entries, uint64_t* rows) {
+  if (!paths || !coldata || !source || !n_samples) return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: null argument");
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (!paths[s] || !coldata[s]) return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: null argument");
+  if (k && (!reads || !lens || !quant || !idx || !rec || !mask || !entry_names || !pre_names))
+    return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: null buffers");
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: bad words_per_read / stride");
+  try {
+    mrg::write_isomir_gff(paths, coldata, n_samples, source, reads, words_per_read, stride, lens, nmask, n, quant, idx, rec, mask, k,
+                          entry_names, pre_names, n_entries, rows);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: %s", e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_isomir_gff: %s", e.what());
   }
 }
 

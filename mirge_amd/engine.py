@@ -539,6 +539,63 @@ class Engine:
         order = np.lexsort((pos_h, ref_h, owner))
         return mm.cpu().numpy(), off_h, ref_h[order], pos_h[order]
 
+    def isomir_classify(self, table, words, lens, nmask, pass_id, ref_id, pos, canon_pass=CANON_PASS,
+                        isomir_pass=ISOMIR_PASS, timings=None):
+        """The rows of the `-gff` files (mrg_isomir_classify): the reads claimed by canon_pass in array order, then those
+        claimed by isomir_pass, each classified against its entry of `table` (isomir.entry_table).  words [W, n] / lens /
+        nmask (or None) / pass_id / ref_id / pos: the device tensors of a ReadSet and a CascadeResult, or host arrays
+        (uploaded).  Returns host arrays (idx uint32 [k], rec int32 [k, 8], mask uint64 [k, ceil(W / 2)], rows of the
+        canon pass, rows of the isomiR pass).  timings: a dict that receives `kernel_ms`, the time of classify_kernel alone (device events
+        inside the call), and `classify_call_ms`, the whole filling call (selection, table uploads, kernel; events around it).
+        The rows are counted by a first call and filled by a second: the selection (two launches and a scan) runs twice."""
+        torch = _torch()
+
+        def dev(x, np_dtype, view=None):
+            if x is None or torch.is_tensor(x):
+                return x
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+        words = dev(words, np.uint64, np.int64).contiguous()
+        nmask = dev(nmask, np.uint64, np.int64)
+        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
+        ref_id, pos = dev(ref_id, np.int32).contiguous(), dev(pos, np.int32).contiguous()
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        W, n = int(words.shape[0]), int(words.shape[1])
+        desc = np.ascontiguousarray(table.desc, dtype=np.int32)
+        text = np.ascontiguousarray(table.words, dtype=np.uint64)
+        npl = np.ascontiguousarray(table.nplane, dtype=np.uint64)
+        counts = (C.c_uint64 * 2)()
+
+        kernel_ms = C.c_float(0.0)
+
+        def call(cap, idx, rec, mask):
+            check(self._lib.mrg_isomir_classify(
+                self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(), n,
+                pass_id.data_ptr(), ref_id.data_ptr(), pos.data_ptr(), int(canon_pass), int(isomir_pass), desc.ctypes.data,
+                desc.shape[0], text.ctypes.data, npl.ctypes.data, text.shape[0], cap,
+                None if idx is None else idx.data_ptr(), None if rec is None else rec.data_ptr(),
+                None if mask is None else mask.data_ptr(), counts, None if timings is None else C.byref(kernel_ms),
+                self._stream_ptr()))
+        call(0, None, None, None)
+        k = int(counts[0]) + int(counts[1])
+        mw = (W + 1) // 2
+        idx = torch.empty(max(k, 1), dtype=torch.int32, device=self.device)
+        rec = torch.empty((max(k, 1), 8), dtype=torch.int32, device=self.device)
+        mask = torch.empty((max(k, 1), mw), dtype=torch.int64, device=self.device)
+        if k:
+            if timings is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            call(k, idx, rec, mask)
+            if timings is not None:
+                e1.record()
+                e1.synchronize()
+                timings["classify_call_ms"] = e0.elapsed_time(e1)
+                timings["kernel_ms"] = float(kernel_ms.value)
+        return (idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k], mask.cpu().numpy().view(np.uint64)[:k],
+                int(counts[0]), int(counts[1]))
+
     def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
                    max_mm_total=2, timings=None):
         """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a

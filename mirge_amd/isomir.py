@@ -8,6 +8,8 @@ Host-side restatement, in coordinates rather than dash-padded strings, of
   updateIsomiRDic / updateIsomiRDic2  runAnnotationPipeline.py:382-446
   extractPreMiRName          extractPreMiRName.py:19-63
   the per-sample GFF writer  writeDataToCSV.py:621-646
+The command line runs the array route (entry_table below + mrg_isomir_classify + mrg_write_isomir_gff); the functions here
+are its model and serve reads beyond 255 nt and `--gff-host`.
 
 Inputs are what the GPU cascade returns for reads claimed by pass 0 (exact
 miRNA) or pass 8 (isomiR): library entry and 0-based offset (SAM POS - 1).
@@ -226,6 +228,128 @@ def write_isomir_gff(outputdir, sampleList, content, seqDic, database):
                                         " Cigar " + rec["cigar"], " Expression " + rec["expression"],
                                         " Filter " + rec["filter"]]))
                     out.write("\n")
+
+
+# ---------------------------------------------------------------------------------------------
+# The array route of `-gff` (mrg_isomir_classify + mrg_write_isomir_gff, include/mirge_amd.h): what depends on the
+# library entry alone is resolved once per entry here, with build_isomir_content's own expressions; the per-read part runs
+# on the GPU (csrc/isomir_gff.hip) and the files are written by csrc/isomir_gff_write.cpp.
+ENTRY_OK, ENTRY_DROP, ENTRY_UNRESOLVABLE = 0, 1, 2
+KIND_DROPPED, KIND_REF, KIND_ISOMIR, KIND_UNRESOLVABLE, KIND_BAD = 0, 1, 2, 3, 4
+SNP_CLASSES = ("", "", "_seed", "_central_offset", "_central", "central_supp")   # record code -> suffix (0 = no iso_snp)
+
+
+class EntryTable:
+    """entry_table's result.  desc int32 [M, 5] = (first word of the precursor in words / nplane, its bases, m0, bases of
+    mature, status); words / nplane uint64: the distinct precursors, 2 bits per base, each from a word boundary (nplane bit
+    2i = base i is no ACGT; code 0 under it = N, code 1 = a character no read holds); pre_names[e] = preMiRName of entry e;
+    pre_seqs[e] = the (patched) precursor text or None; errors[e] = the exception the Python route raises for a read on
+    entry e."""
+
+    def __init__(self, desc, words, nplane, pre_names, pre_seqs, errors):
+        self.desc, self.words, self.nplane = desc, words, nplane
+        self.pre_names, self.pre_seqs, self.errors = pre_names, pre_seqs, errors
+
+
+def _pack_texts(texts):
+    """Distinct precursor texts -> (words, nplane, first word of each)."""
+    import numpy as np
+    lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+    first = np.zeros(len(texts) + 1, dtype=np.int64)
+    np.cumsum((lens + 31) // 32, out=first[1:])
+    total = int(first[-1])
+    words = np.zeros(max(total, 1), dtype=np.uint64)
+    nplane = np.zeros(max(total, 1), dtype=np.uint64)
+    if total:
+        code = np.full(256, 5, dtype=np.uint8)
+        for ch, v in (("A", 0), ("C", 1), ("G", 2), ("T", 3), ("N", 4)):
+            code[ord(ch)] = v
+        c = code[np.frombuffer("".join(texts).encode("latin-1", "replace"), dtype=np.uint8)]
+        base_off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum(lens, out=base_off[1:])
+        owner = np.repeat(np.arange(len(texts)), lens)
+        i = np.arange(c.size) - base_off[owner]
+        slot = first[owner] + (i >> 5)
+        sh = ((i & 31) * 2).astype(np.uint64)
+        other = c > 3
+        np.bitwise_or.at(words, slot, np.where(other, c == 5, c).astype(np.uint64) << sh)
+        np.bitwise_or.at(nplane, slot[other], np.uint64(1) << sh[other])
+    return words, nplane, first[:-1]
+
+
+def entry_table(mirna_names, mirna_seqs, hairpin_seqs, mirna_to_pre, database):
+    """Per miRNA library entry, what build_isomir_content works out per read: the precursor's name (infer_premir_name of
+    the name before the first '.'), its text (a `.SNP` entry that is no `.SNPC`: the canonical precursor carrying the
+    entry's own mature sequence, RAP:417-432), mature = lib_seq[2:-6] and m0 = pre_seq.find(mature).  A KeyError or the
+    ValueError of the SNP branch is kept per entry (status unresolvable) and raised only when a read refers to it."""
+    import numpy as np
+    lib = dict(zip(mirna_names, mirna_seqs))   # (name -> sequence, as name_seq_dict: the route's mirna_lib_seqs)
+    M = len(mirna_names)
+    desc = np.zeros((M, 5), dtype=np.int32)
+    pre_names, pre_seqs, errors = [], [None] * M, {}
+    slot_of, texts = {}, []
+    for e, name in enumerate(mirna_names):
+        canonical = name.split(".")[0] if "." in name else name
+        pre_names.append(infer_premir_name(canonical, mirna_to_pre, database))
+        try:
+            lib_seq = lib[name]
+            mature = lib_seq[2:-6]
+            pre_seq = hairpin_seqs[pre_names[e]]
+            if ".SNP" in name and ".SNPC" not in name:
+                base = name.split(".")[0]
+                canon_mature = lib[base + ".SNPC"][2:-6]
+                canon_pre = hairpin_seqs[infer_premir_name(base, mirna_to_pre, database)]
+                at = canon_pre.find(canon_mature)
+                if at < 0:
+                    raise ValueError("canonical mature of %s not found in its precursor" % name)
+                pre_seq = canon_pre[:at] + mature + canon_pre[at + len(mature):]
+        except (KeyError, ValueError) as err:
+            errors[e] = err
+            desc[e, 4] = ENTRY_UNRESOLVABLE
+            continue
+        pre_seqs[e] = pre_seq
+        m0 = pre_seq.find(mature)
+        if m0 < 0:
+            desc[e, 4] = ENTRY_DROP
+            continue
+        if pre_seq not in slot_of:
+            slot_of[pre_seq] = len(texts)
+            texts.append(pre_seq)
+        desc[e] = (slot_of[pre_seq], len(pre_seq), m0, len(mature), ENTRY_OK)
+    words, nplane, first = _pack_texts(texts)
+    ok = desc[:, 4] == ENTRY_OK
+    if ok.any():
+        desc[ok, 0] = first[desc[ok, 0]]
+    return EntryTable(desc, words, nplane, pre_names, pre_seqs, errors)
+
+
+def variant_text(rec):
+    """The Variant field of one record of mrg_isomir_classify (int32 [8])."""
+    flags = int(rec[4])
+    if flags & 255 == KIND_REF:
+        return "NA"
+    snp, add, out = (flags >> 8) & 255, (flags >> 16) & 1, []
+    if snp:
+        out.append("iso_snp" + SNP_CLASSES[snp])
+    if add and rec[3]:
+        out.append("iso_add:%+d" % rec[3])
+    if rec[2]:
+        out.append("iso_5p:%+d" % rec[2])
+    if not add and rec[3]:
+        out.append("iso_3p:%+d" % rec[3])
+    return ",".join(out)
+
+
+def raise_unresolved(table, rec):
+    """What the Python route does when a read refers to an entry it cannot resolve: the first such row's exception."""
+    import numpy as np
+    kind = rec[:, 4] & 255
+    bad = np.nonzero(kind >= KIND_UNRESOLVABLE)[0]
+    if bad.size:
+        row = int(bad[0])
+        if kind[row] == KIND_UNRESOLVABLE:
+            raise table.errors[int(rec[row, 6])]
+        raise IndexError("row %d: entry %d, offset or read length out of range" % (row, int(rec[row, 6])))
 
 
 def _pick_optimal(names):
