@@ -992,6 +992,73 @@ int mrg_write_isomir_gff(const char *const *paths, const char *const *coldata, u
                          uint64_t n_entries, uint64_t *rows);
 
 /*
+ * `annotate -trf`: tRFs.potential.report.tsv, discarded.reads.summary.assigningtRFs.csv, tRF.Counts.csv and tRF.RP100K.csv
+ * from the arrays, without one Python record per read.  The two calls replace updatetrfContentDic2/3 with trfTypes
+ * (runAnnotationPipeline.py, RAP:448-541) over the `-a --best --strata` listings and the first part of writeDataToCSV's
+ * `if trf_output:` block with assign_cluster / getDistance2 (W2C:353-392, :546-564, :648-800); mirge_amd/trf.py holds the
+ * Python model (collect_trf_content, write_trf_tables with choose = min) whose results they reproduce exactly.
+ *
+ * mrg_trf_classify      DEVICE arrays of a cascade (reads [W][stride], W in {1, 2, 4, 8}; d_nmask or NULL; pass_id), the two
+ *                       tRNA libraries of the context and the HOST tables of mirge_amd.trf.entry_tables, which the call
+ *                       uploads:
+ *                         desc      int32 [n_entries][8] per entry of mature_lib, then of pre_lib: template length (-1: the
+ *                                   Python lookup raises), len(trnaStruDic[name]["seq"]), anticodonStart - 1, flags (bit 0:
+ *                                   "pre_" in name, bit 1: trfTypes raises), rank of the de-duplicated name in Python string
+ *                                   order, the entry of the same library with that name (or -1), first and number of its
+ *                                   predefined tRFs;
+ *                         clusters  int32 [n_clusters][6] per predefined tRF: coordinate() of its dashed string (1-based
+ *                                   first and last non-dash position), the string's length, its first word in text / plane,
+ *                                   rank of the cluster name, index into trfMergedList (-1: none);
+ *                         text      the dashed strings, 2 bits per character as the reads, each from a word boundary;
+ *                         plane     same shape, bit 2i set = character i is no ACGT (code 0 = N, which equals a read's N,
+ *                                   code 1 = any other character, which equals nothing), bit 2i + 1 set = it is a dash.
+ *                       Rows: the reads with pass_id == mature_pass in array order, then those with pass_id ==
+ *                       trailer_pass in array order (flags, an exclusive prefix sum and a scatter on the device), gathered
+ *                       into two read sets on the device -- a trailer read without its trailing T's, or empty when fewer
+ *                       than 3 T's would be cut or fewer than 11 nt left -- and listed with mrg_list_best_count / _fill: -v 1
+ *                       against mature_lib, -v 0 against pre_lib.  The alignments are sorted by (row, entry, offset); the
+ *                       lowest offset of each (row, entry) is kept.  counts[0..1] (HOST) = the two numbers of rows,
+ *                       counts[2] = kept alignments of the rows processed.  Capacity as for mrg_list_best_fill: rows >=
+ *                       cap_rows are neither listed nor written, kept alignments >= cap_hits are not written (the rows'
+ *                       records are complete all the same), so a call with cap_rows = 0 (output pointers may be NULL) only
+ *                       counts the rows.  Kept alignment j: d_hits[j][4] = entry (pre_lib's entries behind mature_lib's),
+ *                       start (0-based), end = start + length - 1 - T tail, type (0 tRF-1, 1 tRF-whole, 2 5'-half, 3 5'-tRF,
+ *                       4 3'-half, 5 3'-tRF, 6 i-tRF, 7 = trfTypes raises for the entry, 8 = entry / offset out of range).
+ *                       Row r: d_rec[r][12] =
+ *                         [0] the read, [1] the selected tRNA's entry (the smallest de-duplicated name among the read's
+ *                             alignments; -1: none), [2] [3] [4] start, end and type of its alignment,
+ *                         [5] the nearest predefined tRF by (get_distance2, name) or -1, [6] that distance (100: none),
+ *                         [7] kind: 0 = assigned (distance <= 8), 1 = "Undef", 2 = "Dele" (the tRNA has no predefined
+ *                             tRFs), 3 = unresolvable (the Python route raises: the de-duplicated name is no alignment of
+ *                             the read, or a table lacks it), 4 = out of range (also a trailer read strip_poly_t rejects),
+ *                             5 = no alignment,
+ *                         [8] [9] first and number of the read's kept alignments (ascending entry), [10] its T tail, [11] 0.
+ *                       kernel_ms (HOST float[2], or NULL): the times of trf_type_kernel and trf_assign_kernel alone, between
+ *                       events.  Synchronises `stream`.
+ * mrg_write_trf_tables  HOST arrays: the reads and quant [n][n_samples], rec [k] IN THE ORDER OF THE TSV (mature rows, then
+ *                       the trailer rows grouped by stripped sequence: mirge_amd.trf.row_order), hits [h], desc and clusters
+ *                       as above, per entry its name, aaType and anticodon (NULL where trnaAAanticodonDic lacks the name),
+ *                       trfMergedList, denom[s] = maturetrnaReads + pretrnaReads of sample s.  paths[0..3] = the tsv, the
+ *                       discarded-reads summary, tRF.Counts.csv, tRF.RP100K.csv.  A row of kind 5 is skipped, one of kind
+ *                       3 or 4 (or one whose tables lack a name it needs) is MRG_ERR_ARG.  *rows (or NULL) = lines of the
+ *                       tsv.  Blocks are formatted by worker threads (MIRGE_AMD_TABLE_THREADS; MIRGE_AMD_TRF_BLOCK_ROWS = rows
+ *                       per block, default 16384, lowered by tests); the per-entity sums are added sequentially in row order
+ *                       from the RP100K values re-read from their 3-decimal text; the bytes depend on neither setting.
+ */
+int mrg_trf_classify(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                     const uint64_t *d_nmask, uint64_t n, const int8_t *d_pass_id, int32_t mature_pass, int32_t trailer_pass,
+                     int32_t mature_lib, int32_t pre_lib, const int32_t *desc, uint64_t n_entries, const int32_t *clusters,
+                     uint64_t n_clusters, const uint64_t *text, const uint64_t *plane, uint64_t text_words, uint64_t cap_rows,
+                     uint64_t cap_hits, int32_t *d_rec, int32_t *d_hits, uint64_t *counts, float *kernel_ms, void *stream);
+int mrg_write_trf_tables(const char *const *paths, const char *const *samples, uint32_t n_samples, const uint64_t *denom,
+                         const uint64_t *reads, uint32_t words_per_read, uint64_t stride, const uint8_t *lens,
+                         const uint64_t *nmask, uint64_t n, const uint32_t *quant, const int32_t *rec, uint64_t k,
+                         const int32_t *hits, uint64_t h, const int32_t *desc, const char *const *entry_names,
+                         const char *const *aa_types, const char *const *anticodons, uint64_t n_entries,
+                         const int32_t *clusters, uint64_t n_clusters, const char *const *merged_names, uint64_t n_merged,
+                         uint64_t *rows);
+
+/*
  * -trf: density-peak clustering (Rodriguez-Laio) of the per-sample tRF reports, the O(n^2) parts of
  * utils/writeDataToCSV.py (W2C) :802-1088 for every (sample, tRNA) group of one run at once.
  * Group g owns rows [off[g], off[g+1]) (off: HOST array of n_groups + 1, off[0] = 0), in the order of its

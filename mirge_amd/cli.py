@@ -51,6 +51,9 @@ def build_parser():
     p.add_argument("--gff-host", dest="gff_host", action="store_true",
                    help="extension: -gff through the per-read Python records instead of the GPU classification (same files)")
     p.add_argument("-trf", dest="trf_output", action="store_true")
+    p.add_argument("--trf-host", dest="trf_host", action="store_true",
+                   help="extension: the -trf tables through the per-read Python records instead of the GPU typing and "
+                        "assignment (same files)")
     p.add_argument("--gpu", type=int, default=0, help="device index (default 0)")
     p.add_argument("--device-ingest", action="store_true",
                    help="split, trim and pack the FASTQ records on the GPU (raw text blocks are uploaded; `-ad none` / `-ad +N` "
@@ -460,7 +463,13 @@ def annotate_main(args, engine_factory=None, materialize=False):
     # -gff: classified on the GPU and written from the arrays (Engine.isomir_classify, columnar.write_isomir_gff) unless
     # a read beyond 255 nt, which the packed arrays do not hold, was claimed by a miRNA pass, or --gff-host asks for the records
     gff_records = args.gff_output and (long_mirna or args.gff_host)
-    need_records = gff_records or args.trf_output or args.a_to_i or (args.diff_isomirs and long_mirna)
+    # -trf: typed, selected and assigned on the GPU and written from the arrays (Engine.trf_classify,
+    # columnar.write_trf_tables) unless a read beyond 255 nt was claimed by a tRNA pass, or --trf-host asks for the records
+    long_trna = long_res is not None and bool(np.isin(np.asarray(long_res[2]), (2, 3)).any())
+    trf_records = args.trf_output and (long_trna or args.trf_host)
+    if not trf_records:
+        want -= {2, 3}
+    need_records = gff_records or trf_records or args.a_to_i or (args.diff_isomirs and long_mirna)
     sub, align = {}, {}
     if need_records:
         sub, align = columnar.read_subset(h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, h_pos, h_mm, npp, want, spike)
@@ -490,9 +499,24 @@ def annotate_main(args, engine_factory=None, materialize=False):
     if args.trf_output:   # RAP:629-634, :657-660, :698-701; W2C:648
         from . import trf
         pre_seqs = engine.indexes["pre_trna"].name_seq_dict()
-        trf.collect_trf_content(trf_content, sub, sample_list, trf_tables["trnaStruDic"], pre_seqs,
-                                trf.engine_lister(engine))
-        trf.write_trf_tables(outdir, sample_list, log_dic, trf_content, trf_tables, pre_seqs)
+        if trf_records:
+            trf.collect_trf_content(trf_content, sub, sample_list, trf_tables["trnaStruDic"], pre_seqs,
+                                    trf.engine_lister(engine))
+            trf.write_trf_tables(outdir, sample_list, log_dic, trf_content, trf_tables, pre_seqs)
+        else:   # from the arrays
+            from . import pack
+            et = trf.entry_tables(npp[2], npp[3], trf_tables, pre_seqs)
+            if world > 1:   # (the gathered host arrays)
+                rows = engine.trf_classify(et, h_words, h_lens, h_nmask, h_pass)
+            else:
+                rows = engine.trf_classify(et, shard.words, shard.lens, shard.nmask, res.pass_id)
+            t_rec, _ = columnar.write_trf_tables(outdir, sample_list, log_dic, h_words, h_lens, h_nmask, h_quant, rows[0],
+                                                 rows[1], rows[2], et)
+            t_idx = t_rec[:, 0]
+            t_seqs = pack.unpack_reads(np.ascontiguousarray(h_words[:, t_idx]), h_lens[t_idx],
+                                       None if h_nmask is None else np.ascontiguousarray(h_nmask[:, t_idx]))
+            trf_content.update(trf.content_from_rows(
+                et, t_rec, t_seqs, h_quant[t_idx], [q["maturetrnaReads"] + q["pretrnaReads"] for q in log_dic["quantStats"]]))
         from . import trf_samples   # W2C:802-1088: tRFs.samples.tmp/, density peaks on the GPU
         trf_samples.write_trf_samples(outdir, sample_list, trf_content, trf_tables, pre_seqs,
                                       trf_samples.engine_peaks(engine))

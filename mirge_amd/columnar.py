@@ -17,6 +17,7 @@ downstream consumers actually look at are turned into the reference's shapes:
   isomir_dic           the grouping write_mapped_csv builds on the way (W2C:588-606)
   write_isomir_gff     the per-sample GFF files from the rows of Engine.isomir_classify (W2C:621-646;
                        mrg_write_isomir_gff)
+  write_trf_tables     the four tRF tables from the rows of Engine.trf_classify (W2C:648-800; mrg_write_trf_tables)
   mirna_read_subset    the miRNA-claimed subset, optionally only what the -ai grouping keeps
   full_seq_dic         everything as the reference's seqDic (small inputs, tests)
 """
@@ -228,6 +229,41 @@ def write_isomir_gff(outdir, sample_list, words, lens, nmask, quant, idx, rec, m
         paths, coldata, S, source.encode(), words.ctypes.data, W, n, lens.ctypes.data, None if nm is None else nm.ctypes.data,
         n, quant.ctypes.data, idx.ctypes.data, rec.ctypes.data, mask.ctypes.data, idx.shape[0], names, pres, M, rows))
     return [int(x) for x in rows]
+
+
+def write_trf_tables(outdir, sample_list, log_dic, words, lens, nmask, quant, rec, hits, n_mature, et):
+    """tRFs.potential.report.tsv, discarded.reads.summary.assigningtRFs.csv, tRF.Counts.csv and tRF.RP100K.csv (W2C:648-800)
+    from the arrays and the rows of Engine.trf_classify, by the native writer (mrg_write_trf_tables): the files
+    trf.write_trf_tables writes for the content collect_trf_content builds, byte for byte.  A row that reaches a name the
+    Python route cannot resolve raises that route's exception.  Returns (rec in the order of the tsv, lines written)."""
+    from . import trf
+    lib = _native.load()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, trf.REC_INTS)
+    rec = np.ascontiguousarray(rec[trf.row_order(rec, n_mature, words, lens, nm)])
+    hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, trf.HIT_INTS)
+    trf.raise_unresolved(et, rec, hits)
+    quant = np.ascontiguousarray(quant, dtype=np.uint32)
+    S = quant.shape[1] if quant.ndim == 2 else 1
+    denom = np.array([q["maturetrnaReads"] + q["pretrnaReads"] for q in log_dic["quantStats"]][:S], dtype=np.uint64)
+    paths = (C.c_char_p * 4)(*[os.fsencode(os.path.join(outdir, fn)) for fn in (
+        "tRFs.potential.report.tsv", "discarded.reads.summary.assigningtRFs.csv", "tRF.Counts.csv", "tRF.RP100K.csv")])
+    samples = (C.c_char_p * S)(*[s.encode() for s in sample_list])
+
+    def strings(items):
+        return (C.c_char_p * max(len(items), 1))(*[None if x is None else x.encode() for x in items])
+    desc = np.ascontiguousarray(et.desc, dtype=np.int32)
+    clusters = np.ascontiguousarray(et.clusters, dtype=np.int32)
+    rows = C.c_uint64(0)
+    check(lib.mrg_write_trf_tables(
+        paths, samples, S, denom.ctypes.data, words.ctypes.data, W, n, lens.ctypes.data, None if nm is None else nm.ctypes.data,
+        n, quant.ctypes.data, rec.ctypes.data, rec.shape[0], hits.ctypes.data, hits.shape[0], desc.ctypes.data,
+        strings(et.names), strings(et.aa_types), strings(et.anticodons), desc.shape[0], clusters.ctypes.data, clusters.shape[0],
+        strings(et.merged_list), len(et.merged_list), C.byref(rows)))
+    return rec, int(rows.value)
 
 
 def mirna_read_subset(engine, cols, words, lens, nmask, quant, log_dic=None, spike_in=False, for_a2i=False):

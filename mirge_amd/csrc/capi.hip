@@ -29,6 +29,7 @@
 #include "sa_build.hpp"
 #include "tables.hpp"
 #include "trf_peaks.hpp"
+#include "trf_tables.hpp"
 
 struct mrg_index {
   mutable mrg::FmIndex ix;
@@ -3581,6 +3582,276 @@ int mrg_write_isomir_gff(const char* const* paths, const char* const* coldata, u
     return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: %s", e.what());
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "mrg_write_isomir_gff: %s", e.what());
+  }
+}
+
+// ------------------------------------------------------------- -trf
+extern "C++" {
+namespace {
+
+struct TrfBuf {  // one device allocation, carved into 256-byte aligned pieces
+  char* p = nullptr;
+  uint64_t used = 0;
+  ~TrfBuf() {
+    if (p) (void)hipFree(p);
+  }
+  static uint64_t up(uint64_t b) { return (b + 255) & ~255ull; }
+  uint64_t reserve(uint64_t bytes) {
+    const uint64_t at = used;
+    used += up(std::max<uint64_t>(bytes, 1));
+    return at;
+  }
+  hipError_t alloc() { return hipMalloc((void**)&p, std::max<uint64_t>(used, 256)); }
+  template <class T>
+  T* at(uint64_t off) const { return (T*)(p + off); }
+};
+
+uint32_t bits_for(uint64_t v) {  // the smallest b with v < 2^b
+  uint32_t b = 0;
+  while (b < 64 && (v >> b)) ++b;
+  return b;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mrg_trf_classify(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                     const uint64_t* d_nmask, uint64_t n, const int8_t* d_pass_id, int32_t mature_pass, int32_t trailer_pass,
+                     int32_t mature_lib, int32_t pre_lib, const int32_t* desc, uint64_t n_entries, const int32_t* clusters,
+                     uint64_t n_clusters, const uint64_t* text, const uint64_t* plane, uint64_t text_words, uint64_t cap_rows,
+                     uint64_t cap_hits, int32_t* d_rec, int32_t* d_hits, uint64_t* counts, float* kernel_ms, void* stream) {
+  if (!ctx || !counts) return fail(MRG_ERR_ARG, "mrg_trf_classify: null argument");
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0f;
+  if (n && (!d_reads || !d_lens || !d_pass_id)) return fail(MRG_ERR_ARG, "mrg_trf_classify: null buffers");
+  if ((n_entries && !desc) || (n_clusters && !clusters) || (text_words && (!text || !plane)))
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: null tables");
+  if ((cap_rows && !d_rec) || (cap_hits && !d_hits)) return fail(MRG_ERR_ARG, "mrg_trf_classify: null output buffers");
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: words_per_read must be 1, 2, 4 or 8");
+  if (stride < n || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_trf_classify: bad stride / n");
+  if (mature_pass == trailer_pass || mature_pass < 0 || trailer_pass < 0 || mature_pass > 127 || trailer_pass > 127)
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: the two passes must differ and lie in 0..127");
+  if (mature_lib < 0 || (size_t)mature_lib >= ctx->libs.size() || pre_lib < 0 || (size_t)pre_lib >= ctx->libs.size())
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: unknown library");
+  const uint64_t n_mature_entries = ctx->libs[mature_lib].n_ref;
+  if (n_entries != n_mature_entries + ctx->libs[pre_lib].n_ref || n_entries >= (1ull << 30) || n_clusters >= (1ull << 30) ||
+      text_words >= (1ull << 31))
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: the entry table must hold the entries of the two libraries, in that order");
+  // the kernels trust the tables: a representative is an entry, the predefined tRFs of an entry and their strings lie inside
+  // the tables
+  for (uint64_t e = 0; e < n_entries; ++e) {
+    const int32_t* d = desc + e * mrg::kTrfDescInts;
+    const int64_t rep = d[mrg::kTrfDescRep], first = d[mrg::kTrfDescFirst], cnt = d[mrg::kTrfDescCount];
+    const bool same_lib = rep < 0 || ((uint64_t)rep < n_mature_entries) == (e < n_mature_entries);
+    if (rep < -1 || rep >= (int64_t)n_entries || !same_lib || cnt < 0 || (cnt && (first < 0 || first + cnt > (int64_t)n_clusters)))
+      return fail(MRG_ERR_ARG, "mrg_trf_classify: entry %llu points outside the tables", (unsigned long long)e);
+  }
+  for (uint64_t t = 0; t < n_clusters; ++t) {
+    const int32_t* c = clusters + t * mrg::kTrfClusterInts;
+    const int64_t len = c[mrg::kTrfClusterLen], word = c[mrg::kTrfClusterWord];
+    if (len < 0 || len > (1 << 20) || word < 0 || word + (len + 31) / 32 > (int64_t)text_words)
+      return fail(MRG_ERR_ARG, "mrg_trf_classify: predefined tRF %llu lies outside the text table", (unsigned long long)t);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  counts[0] = counts[1] = counts[2] = 0;
+  if (n == 0) return MRG_OK;
+  const uint32_t W = words_per_read;
+
+  // ---- select and order: the exclusive sums of [mature flags | trailer flags | 0] are the rows (as mrg_isomir_classify)
+  const uint64_t n_flags = 2 * n + 1;
+  TrfBuf sel;
+  const uint64_t o_flags = sel.reserve(n_flags * sizeof(uint32_t)), o_scan = sel.reserve(mrg::prims::scan_temp_bytes(n_flags));
+  HIP_TRY(sel.alloc());
+  uint32_t* flags = sel.at<uint32_t>(o_flags);
+  HIP_TRY(mrg::iso_flags_launch(d_pass_id, n, mature_pass, trailer_pass, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n_flags, sel.p + o_scan, st));
+  uint32_t ends[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&ends[0], flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&ends[1], flags + 2 * n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  counts[0] = ends[0];
+  counts[1] = ends[1] - ends[0];
+  const uint32_t k = (uint32_t)std::min<uint64_t>(ends[1], cap_rows);
+  if (k == 0) return MRG_OK;
+  const uint32_t n_a = std::min(ends[0], k), n_b = k - n_a;
+
+  // ---- the selected reads as two contiguous read sets, the tables
+  TrfBuf rs;
+  const uint64_t set_a = (uint64_t)W * n_a * sizeof(uint64_t), set_b = (uint64_t)W * n_b * sizeof(uint64_t);
+  const uint64_t o_idx = rs.reserve(k * sizeof(uint32_t)), o_sub = rs.reserve(k), o_tail = rs.reserve(k), o_wa = rs.reserve(set_a),
+                 o_wb = rs.reserve(set_b), o_na = rs.reserve(d_nmask ? set_a : 0), o_nb = rs.reserve(d_nmask ? set_b : 0),
+                 o_mm = rs.reserve(k), o_offa = rs.reserve((n_a + 1ull) * sizeof(uint64_t)),
+                 o_offb = rs.reserve((n_b + 1ull) * sizeof(uint64_t)), o_h0 = rs.reserve(k * sizeof(uint32_t)),
+                 o_h1 = rs.reserve(k * sizeof(uint32_t)), o_desc = rs.reserve(n_entries * mrg::kTrfDescInts * sizeof(int32_t)),
+                 o_cl = rs.reserve(n_clusters * mrg::kTrfClusterInts * sizeof(int32_t)), o_text = rs.reserve(text_words * sizeof(uint64_t)),
+                 o_plane = rs.reserve(text_words * sizeof(uint64_t));
+  HIP_TRY(rs.alloc());
+  uint32_t* idx = rs.at<uint32_t>(o_idx);
+  HIP_TRY(mrg::iso_scatter_launch(d_pass_id, n, mature_pass, trailer_pass, flags, k, idx, st));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(rs.p + o_desc, desc, n_entries * mrg::kTrfDescInts * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (n_clusters)
+    HIP_TRY(hipMemcpyAsync(rs.p + o_cl, clusters, n_clusters * mrg::kTrfClusterInts * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (text_words) {
+    HIP_TRY(hipMemcpyAsync(rs.p + o_text, text, text_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(rs.p + o_plane, plane, text_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemsetAsync(rs.p + o_h0, 0, k * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(rs.p + o_h1, 0, k * sizeof(uint32_t), st));
+  mrg::TrfGatherParams g;
+  g.reads = d_reads;
+  g.nmask = d_nmask;
+  g.lens = d_lens;
+  g.stride = stride;
+  g.W = W;
+  g.idx = idx;
+  g.k = k;
+  g.n_mature = n_a;
+  g.words_a = rs.at<uint64_t>(o_wa);
+  g.words_b = rs.at<uint64_t>(o_wb);
+  g.nmask_a = d_nmask ? rs.at<uint64_t>(o_na) : nullptr;
+  g.nmask_b = d_nmask ? rs.at<uint64_t>(o_nb) : nullptr;
+  g.sub_len = rs.at<uint8_t>(o_sub);
+  g.tail = rs.at<uint8_t>(o_tail);
+  HIP_TRY(mrg::trf_gather_launch(g, st));
+
+  // ---- list: -v 1 against the mature tRNAs, -v 0 against the pre-tRNAs (`-a --best --strata`, the whole read is seed)
+  constexpr int32_t kVModeSeed = 1024;
+  uint64_t total_a = 0, total_b = 0;
+  int rc = MRG_OK;
+  if (n_a)
+    rc = mrg_list_best_count(ctx, g.words_a, W, g.sub_len, g.nmask_a, n_a, mature_lib, kVModeSeed, 1, 1, rs.at<uint8_t>(o_mm),
+                             rs.at<uint64_t>(o_offa), &total_a, stream);
+  if (rc != MRG_OK) return rc;
+  if (n_b)
+    rc = mrg_list_best_count(ctx, g.words_b, W, g.sub_len + n_a, g.nmask_b, n_b, pre_lib, kVModeSeed, 0, 0, rs.at<uint8_t>(o_mm) + n_a,
+                             rs.at<uint64_t>(o_offb), &total_b, stream);
+  if (rc != MRG_OK) return rc;
+  const uint64_t H = total_a + total_b;
+  const uint32_t owner_bits = bits_for(k), entry_bits = bits_for(n_entries),
+                 pos_bits = bits_for(std::max(ctx->libs[mature_lib].n, ctx->libs[pre_lib].n));
+  if (H >= (1ull << 32) - 1 || pos_bits > 30 || owner_bits + entry_bits + pos_bits > 64)
+    return fail(MRG_ERR_ARG, "mrg_trf_classify: too many alignments for one call (split the reads)");
+  TrfBuf al;
+  const uint64_t o_ref = al.reserve(H * sizeof(int32_t)), o_pos = al.reserve(H * sizeof(int32_t)), o_k0 = al.reserve(H * sizeof(uint64_t)),
+                 o_k1 = al.reserve(H * sizeof(uint64_t)), o_head = al.reserve((H + 1) * sizeof(uint32_t)),
+                 o_tmp = al.reserve(std::max<uint64_t>(mrg::prims::radix_temp_bytes(H + 1), mrg::prims::scan_temp_bytes(H + 1)));
+  HIP_TRY(al.alloc());
+  int32_t *ref = al.at<int32_t>(o_ref), *pos = al.at<int32_t>(o_pos);
+  uint64_t* keys[2] = {al.at<uint64_t>(o_k0), al.at<uint64_t>(o_k1)};
+  if (total_a) {
+    rc = mrg_list_best_fill(ctx, g.words_a, W, g.sub_len, g.nmask_a, n_a, mature_lib, kVModeSeed, 1, 1, rs.at<uint8_t>(o_mm),
+                            rs.at<uint64_t>(o_offa), total_a, ref, pos, stream);
+    if (rc != MRG_OK) return rc;
+    HIP_TRY(mrg::trf_keys_launch(rs.at<uint64_t>(o_offa), ref, pos, n_a, 0u, 0u, entry_bits, pos_bits, 0, keys[0], st));
+  }
+  if (total_b) {
+    rc = mrg_list_best_fill(ctx, g.words_b, W, g.sub_len + n_a, g.nmask_b, n_b, pre_lib, kVModeSeed, 0, 0, rs.at<uint8_t>(o_mm) + n_a,
+                            rs.at<uint64_t>(o_offb), total_b, ref + total_a, pos + total_a, stream);
+    if (rc != MRG_OK) return rc;
+    HIP_TRY(mrg::trf_keys_launch(rs.at<uint64_t>(o_offb), ref + total_a, pos + total_a, n_b, n_a, (uint32_t)n_mature_entries, entry_bits,
+                                 pos_bits, total_a, keys[0], st));
+  }
+  // ---- order by (owner, entry, offset); the first alignment of an (owner, entry) run is kept (the lowest offset)
+  bool second = false;
+  if (H) HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[0], keys[1], nullptr, nullptr, (uint32_t)H, owner_bits + entry_bits + pos_bits,
+                                                  al.p + o_tmp, st, &second));
+  const uint64_t* sorted = keys[second ? 1 : 0];
+  uint32_t* head = al.at<uint32_t>(o_head);
+  HIP_TRY(mrg::trf_heads_launch(sorted, (uint32_t)H, pos_bits, head, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(head, head, H + 1, al.p + o_tmp, st));
+  uint32_t kept = 0;
+  HIP_TRY(hipMemcpyAsync(&kept, head + H, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  counts[2] = kept;
+
+  TrfBuf hb;
+  const uint64_t o_hits = hb.reserve((uint64_t)kept * mrg::kTrfHitInts * sizeof(int32_t));
+  HIP_TRY(hb.alloc());
+  mrg::TrfTypeParams tp;
+  tp.keys = sorted;
+  tp.slot = head;
+  tp.n_keys = (uint32_t)H;
+  tp.entry_bits = entry_bits;
+  tp.pos_bits = pos_bits;
+  tp.lens = d_lens;
+  tp.idx = idx;
+  tp.tail = g.tail;
+  tp.k = k;
+  tp.desc = rs.at<int32_t>(o_desc);
+  tp.n_entries = (uint32_t)n_entries;
+  tp.hits = hb.at<int32_t>(o_hits);
+  tp.hit0 = rs.at<uint32_t>(o_h0);
+  tp.hit1 = rs.at<uint32_t>(o_h1);
+  mrg::TrfAssignParams ap;
+  ap.reads = d_reads;
+  ap.nmask = d_nmask;
+  ap.lens = d_lens;
+  ap.stride = stride;
+  ap.W = W;
+  ap.idx = idx;
+  ap.sub_len = g.sub_len;
+  ap.tail = g.tail;
+  ap.k = k;
+  ap.n_mature = n_a;
+  ap.hits = tp.hits;
+  ap.hit0 = tp.hit0;
+  ap.hit1 = tp.hit1;
+  ap.desc = tp.desc;
+  ap.n_entries = tp.n_entries;
+  ap.clusters = rs.at<int32_t>(o_cl);
+  ap.n_clusters = (uint32_t)n_clusters;
+  ap.text = rs.at<uint64_t>(o_text);
+  ap.plane = rs.at<uint64_t>(o_plane);
+  ap.rec = d_rec;
+  // kernel_ms: trf_type_kernel and trf_assign_kernel alone, between events on the stream
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  if (kernel_ms)
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) e = mrg::trf_type_launch(tp, st);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[1], st);
+  if (e == hipSuccess) e = mrg::trf_assign_launch(ap, st);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev[2], st);
+  const uint64_t out_hits = std::min<uint64_t>(kept, cap_hits);
+  if (e == hipSuccess && out_hits)
+    e = hipMemcpyAsync(d_hits, tp.hits, out_hits * mrg::kTrfHitInts * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+  // (the tables were copied from pageable host memory, and the buffers above are freed on return)
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(&kernel_ms[0], ev[0], ev[1]);
+  if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(&kernel_ms[1], ev[1], ev[2]);
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  HIP_TRY(e);
+  return MRG_OK;
+}
+
+int mrg_write_trf_tables(const char* const* paths, const char* const* samples, uint32_t n_samples, const uint64_t* denom,
+                         const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens, const uint64_t* nmask,
+                         uint64_t n, const uint32_t* quant, const int32_t* rec, uint64_t k, const int32_t* hits, uint64_t h,
+                         const int32_t* desc, const char* const* entry_names, const char* const* aa_types, const char* const* anticodons,
+                         uint64_t n_entries, const int32_t* clusters, uint64_t n_clusters, const char* const* merged_names,
+                         uint64_t n_merged, uint64_t* rows) {
+  if (!paths || !samples || !denom || !n_samples) return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null argument");
+  for (int i = 0; i < 4; ++i)
+    if (!paths[i]) return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null argument");
+  for (uint32_t s = 0; s < n_samples; ++s)
+    if (!samples[s]) return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null argument");
+  if (k && (!reads || !lens || !quant || !rec || !desc || !entry_names || !aa_types || !anticodons))
+    return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null buffers");
+  if ((h && !hits) || (n_clusters && !clusters) || (n_merged && !merged_names)) return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null buffers");
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "mrg_write_trf_tables: bad words_per_read / stride");
+  try {
+    const mrg::TrfWriteArgs a{paths, samples, n_samples, denom, reads, words_per_read, stride, lens, nmask, n, quant, rec, k, hits, h,
+                              desc, entry_names, aa_types, anticodons, n_entries, clusters, n_clusters, merged_names, n_merged};
+    mrg::write_trf_tables(a, rows);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "mrg_write_trf_tables: %s", e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_trf_tables: %s", e.what());
   }
 }
 

@@ -596,6 +596,69 @@ class Engine:
         return (idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k], mask.cpu().numpy().view(np.uint64)[:k],
                 int(counts[0]), int(counts[1]))
 
+    def trf_classify(self, et, words, lens, nmask, pass_id, mature_pass=2, trailer_pass=3, mature_lib="mature_trna",
+                     pre_lib="pre_trna", timings=None):
+        """The rows of the `-trf` tables (mrg_trf_classify): the reads claimed by mature_pass in array order, then those
+        claimed by trailer_pass, listed against their library on the device (`-v 1` / `-v 0`, a trailer read without its T
+        tail), every kept alignment typed, the read's tRNA selected and its predefined tRF assigned against `et`
+        (trf.entry_tables over the names of the two libraries).  words [W, n] / lens / nmask (or None) / pass_id: the device
+        tensors of a ReadSet and a CascadeResult, or host arrays (uploaded).  Returns host arrays (rec int32 [k, 12], hits
+        int32 [h, 4], rows of the mature pass, rows of the trailer pass).  timings: a dict that receives `type_kernel_ms` and
+        `assign_kernel_ms` (device events inside the call) and `classify_call_ms` (events around the filling call).  The
+        rows are counted by a first call; the filling call is repeated only if the read set has more than 4 kept
+        alignments per read."""
+        torch = _torch()
+
+        def dev(x, np_dtype, view=None):
+            if x is None or torch.is_tensor(x):
+                return x
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+        words = dev(words, np.uint64, np.int64).contiguous()
+        nmask = dev(nmask, np.uint64, np.int64)
+        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        W, n = int(words.shape[0]), int(words.shape[1])
+        desc = np.ascontiguousarray(et.desc, dtype=np.int32)
+        clusters = np.ascontiguousarray(et.clusters, dtype=np.int32)
+        text = np.ascontiguousarray(et.words, dtype=np.uint64)
+        plane = np.ascontiguousarray(et.plane, dtype=np.uint64)
+        counts = (C.c_uint64 * 3)()
+        kernel_ms = (C.c_float * 2)()
+        lids = [self.libs[x] if isinstance(x, str) else int(x) for x in (mature_lib, pre_lib)]
+
+        def call(cap_rows, cap_hits, rec, hits):
+            check(self._lib.mrg_trf_classify(
+                self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(), n,
+                pass_id.data_ptr(), int(mature_pass), int(trailer_pass), lids[0], lids[1], desc.ctypes.data, desc.shape[0],
+                clusters.ctypes.data, clusters.shape[0], text.ctypes.data, plane.ctypes.data, text.shape[0], cap_rows,
+                cap_hits, None if rec is None else rec.data_ptr(), None if hits is None else hits.data_ptr(), counts,
+                None if timings is None else kernel_ms, self._stream_ptr()))
+        call(0, 0, None, None)
+        n2, n3 = int(counts[0]), int(counts[1])
+        k, h = n2 + n3, 0
+        rec = torch.empty((max(k, 1), 12), dtype=torch.int32, device=self.device)
+        hits = torch.empty((1, 4), dtype=torch.int32, device=self.device)
+        if k:
+            cap = 4 * k + 64
+            while True:
+                hits = torch.empty((cap, 4), dtype=torch.int32, device=self.device)
+                if timings is not None:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                call(k, cap, rec, hits)
+                if timings is not None:
+                    e1.record()
+                    e1.synchronize()
+                    timings["classify_call_ms"] = e0.elapsed_time(e1)
+                    timings["type_kernel_ms"], timings["assign_kernel_ms"] = float(kernel_ms[0]), float(kernel_ms[1])
+                h = int(counts[2])
+                if h <= cap:
+                    break
+                cap = h
+        return rec.cpu().numpy()[:k], hits.cpu().numpy()[:h], n2, n3
+
     def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
                    max_mm_total=2, timings=None):
         """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a

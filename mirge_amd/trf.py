@@ -14,6 +14,10 @@ Restates, on small host data:
 The listings come from the GPU (`Engine.list_best` = mrg_list_best_count/fill); tests can pass
 any `lister(reads, library_key, max_mismatches) -> [[(entry name, 0-based offset), ...], ...]`.
 
+The command line runs the array route (entry_tables, row_order, raise_unresolved and content_from_rows below +
+mrg_trf_classify + mrg_write_trf_tables); the functions above them are its model and serve reads beyond 255 nt, a
+`choose` other than min and `--trf-host`.
+
 The per-sample `tRFs.samples.tmp/*` reports and their density-peak clustering (W2C:802-1088), which
 start from the trfContentDic that write_trf_tables leaves, are mirge_amd.trf_samples.
 
@@ -310,3 +314,225 @@ def write_trf_tables(outputdir, sampleList, logDic, trfContentDic, tables, pretr
             o1.write(m + "," + ",".join(str(entity[s][m][0]) for s in sampleList) + "\n")
             o2.write(m + "," + ",".join("%.2f" % round(entity[s][m][1], 2) for s in sampleList) + "\n")
     return rows
+
+
+# ---------------------------------------------------------------------------------------------
+# The array route of `-trf` (mrg_trf_classify + mrg_write_trf_tables, include/mirge_amd.h): what depends on the library
+# entry alone is resolved once per entry here, with the expressions of the functions above; the per-read part runs on the
+# GPU (csrc/trf_tables.hip) and the files are written by csrc/trf_tables_write.cpp.
+TRF_TYPES = ("tRF-1", "tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF")
+TYPE_UNRESOLVABLE, TYPE_RANGE = 7, 8
+KIND_ASSIGNED, KIND_UNDEF, KIND_DELE, KIND_UNRESOLVABLE, KIND_RANGE, KIND_NONE = 0, 1, 2, 3, 4, 5
+REC_INTS, HIT_INTS = 12, 4
+
+
+class EntryTables:
+    """entry_tables' result, over the entries of mature_trna followed by those of pre_trna (n_mature = the former).
+    desc int32 [E, 8] = (template length or -1, len(stru seq), anticodonStart - 1, flags: 1 = "pre_" in name, 2 = trfTypes
+    raises, rank of dup.get(name, name), entry of that name in the same library or -1, first and number of predefined tRFs);
+    clusters int32 [T, 6] = (coordinate first, last, len(dashed), first word, rank of the cluster name, merged index or
+    -1); words / plane uint64: the dashed strings, 2 bits per character (plane bit 2i = no ACGT: code 0 = N, 1 = another
+    character; bit 2i + 1 = dash); names, rep_names, aa_types, anticodons per entry (None where trnaAAanticodonDic lacks the
+    name); rep_aa_missing[e] = trnaAAanticodonDic lacks rep_names[e]; cluster_names, dashed per predefined tRF; merged_list;
+    errors[(e, stage)] = the exception the Python route raises: stage "type" (trfTypes), "aa" (a hit without amino acid),
+    "length" (the selected tRNA's template), and errors[("cluster", t)] (a predefined tRF without merged entity)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _pack_dashed(texts):
+    """Dashed strings -> (words, plane, first word of each)."""
+    import numpy as np
+    lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+    first = np.zeros(len(texts) + 1, dtype=np.int64)
+    np.cumsum((lens + 31) // 32, out=first[1:])
+    total = int(first[-1])
+    words = np.zeros(max(total, 1), dtype=np.uint64)
+    plane = np.zeros(max(total, 1), dtype=np.uint64)
+    if total:
+        code = np.full(256, 5, dtype=np.uint8)
+        for ch, v in (("A", 0), ("C", 1), ("G", 2), ("T", 3), ("N", 4), ("-", 6)):
+            code[ord(ch)] = v
+        c = code[np.frombuffer("".join(texts).encode("latin-1", "replace"), dtype=np.uint8)]
+        base_off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum(lens, out=base_off[1:])
+        owner = np.repeat(np.arange(len(texts)), lens)
+        i = np.arange(c.size) - base_off[owner]
+        slot = first[owner] + (i >> 5)
+        sh = ((i & 31) * 2).astype(np.uint64)
+        value = np.where(c <= 3, c, np.where(c == 5, 1, 0)).astype(np.uint64)
+        flag = np.where(c <= 3, 0, np.where(c == 6, 2, 1)).astype(np.uint64)
+        np.bitwise_or.at(words, slot, value << sh)
+        np.bitwise_or.at(plane, slot, flag << sh)
+    return words, plane, first[:-1]
+
+
+def entry_tables(mature_names, pre_names, tables, pre_seqs):
+    """Per entry of the two tRNA libraries, everything collect_trf_content and write_trf_tables ask of an entry.  A lookup
+    that raises there is kept per entry and raised only when a read reaches it (raise_unresolved)."""
+    import numpy as np
+    stru, aa_dic = tables["trnaStruDic"], tables["trnaAAanticodonDic"]
+    dup, clusters_dic = tables["duptRNA2UniqueDic"], tables["tRNAtrfDic"]
+    merged_name, merged_list = tables["trfMergedNameDic"], list(tables["trfMergedList"])
+    names = list(mature_names) + list(pre_names)
+    n_mature, E = len(mature_names), len(names)
+    rep_names = [dup.get(x, x) for x in names]
+    rank_of = {x: r for r, x in enumerate(sorted(set(rep_names)))}
+    entry_of = ({}, {})
+    for e in range(E - 1, -1, -1):
+        entry_of[e >= n_mature][names[e]] = e
+    merged_index = {}
+    for g, x in enumerate(merged_list):
+        merged_index.setdefault(x, g)
+    cluster_rank = {x: r for r, x in enumerate(sorted({c for d in clusters_dic.values() for c in d.values()}))}
+    desc = np.zeros((E, 8), dtype=np.int32)
+    errors, aa_types, anticodons, rep_aa_missing = {}, [], [], np.zeros(E, dtype=bool)
+    cluster_rows, cluster_names, dashed_all, slice_of = [], [], [], {}
+    for e, name in enumerate(names):
+        if "pre_" in name:
+            desc[e, 3] |= 1
+            if name not in pre_seqs:
+                desc[e, 3] |= 2
+                errors[(e, "type")] = KeyError(name)
+        elif name in stru:
+            desc[e, 1], desc[e, 2] = len(stru[name]["seq"]), stru[name]["anticodonStart"] - 1
+        else:
+            desc[e, 3] |= 2
+            errors[(e, "type")] = KeyError(name)
+        try:
+            desc[e, 0] = len(pre_seqs[name]) if "pre" in name else len(stru[name]["seq"])
+        except KeyError as err:
+            desc[e, 0] = -1
+            errors[(e, "length")] = err
+        if name in aa_dic:
+            aa_types.append(aa_dic[name]["aaType"])
+            anticodons.append(aa_dic[name]["anticodon"])
+        else:
+            aa_types.append(None)
+            anticodons.append(None)
+            errors[(e, "aa")] = KeyError(name)
+        desc[e, 4] = rank_of[rep_names[e]]
+        desc[e, 5] = entry_of[e >= n_mature].get(rep_names[e], -1)
+        rep_aa_missing[e] = rep_names[e] not in aa_dic
+        if name not in slice_of:
+            first = len(cluster_rows)
+            for dashed, cname in clusters_dic.get(name, {}).items():
+                c0, c1 = coordinate(dashed)
+                t = len(cluster_rows)
+                m = merged_index.get(merged_name[cname], -1) if cname in merged_name else -1
+                if m < 0:
+                    errors[("cluster", t)] = KeyError(cname)
+                cluster_rows.append((c0, c1, len(dashed), 0, cluster_rank[cname], m))
+                cluster_names.append(cname)
+                dashed_all.append(dashed)
+            slice_of[name] = (first, len(cluster_rows) - first)
+        desc[e, 6], desc[e, 7] = slice_of[name]
+    clusters = np.array(cluster_rows, dtype=np.int32).reshape(-1, 6)
+    words, plane, first_word = _pack_dashed(dashed_all)
+    if len(cluster_rows):
+        clusters[:, 3] = first_word
+    return EntryTables(desc=desc, clusters=clusters, words=words, plane=plane, names=names, rep_names=rep_names,
+                       aa_types=aa_types, anticodons=anticodons, rep_aa_missing=rep_aa_missing, cluster_names=cluster_names,
+                       dashed=dashed_all, merged_list=merged_list, errors=errors, n_mature=n_mature)
+
+
+def row_order(rec, n_mature, words, lens, nmask=None):
+    """The order of trfContentDic's keys, as a permutation of the rows of mrg_trf_classify: the rows of the mature pass as
+    they are, then those of the trailer pass grouped by their T-stripped sequence -- groups in order of first appearance,
+    rows inside a group in array order (update_trf_content_trailer walks subseqSeqDic).  No loop over reads."""
+    import numpy as np
+    rec = np.asarray(rec).reshape(-1, REC_INTS)
+    k = rec.shape[0]
+    order = np.arange(k, dtype=np.int64)
+    t = rec[n_mature:]
+    n3 = t.shape[0]
+    if n3 < 2:
+        return order
+    idx = t[:, 0].astype(np.int64)
+    sub = np.asarray(lens)[idx].astype(np.int64) - t[:, 10]
+    cols = [sub]
+    for w in range(np.asarray(words).shape[0]):
+        nb = np.clip(sub - 32 * w, 0, 32)
+        keep = np.where(nb >= 32, ~np.uint64(0), (np.uint64(1) << (2 * np.minimum(nb, 31)).astype(np.uint64)) - np.uint64(1))
+        cols.append(np.asarray(words)[w, idx] & keep)
+        if nmask is not None:
+            cols.append(np.asarray(nmask)[w, idx] & keep)
+    by_seq = np.lexsort(cols[::-1])
+    new = np.zeros(n3, dtype=bool)
+    for c in cols:
+        new[1:] |= c[by_seq][1:] != c[by_seq][:-1]
+    group = np.empty(n3, dtype=np.int64)
+    group[by_seq] = np.cumsum(new)
+    first = np.full(int(group.max()) + 1, n3, dtype=np.int64)
+    np.minimum.at(first, group, np.arange(n3))
+    order[n_mature:] = n_mature + np.lexsort((np.arange(n3), first[group]))
+    return order
+
+
+def raise_unresolved(et, rec, hits):
+    """What the Python route does when a read reaches a name it cannot resolve: collect_trf_content's first exception, else
+    the first of write_trf_tables' report loop, else the first of its counting loop.  rec in the order of the tsv."""
+    import numpy as np
+    rec = np.asarray(rec).reshape(-1, REC_INTS)
+    hits = np.asarray(hits).reshape(-1, HIT_INTS)
+    k = rec.shape[0]
+    counts = rec[:, 9].astype(np.int64)
+    row = np.repeat(np.arange(k), counts)                                   # the tsv row of every (row, hit) pair, and
+    at = np.repeat(rec[:, 8].astype(np.int64) - np.cumsum(counts) + counts, counts) + np.arange(int(counts.sum()))   # its hit
+    entry, typ = hits[at, 0], hits[at, 3]
+    # collect_trf_content: a hit is typed before anything else looks at it (hits of a read from the highest entry down)
+    bad_rows = np.union1d(row[typ >= TYPE_UNRESOLVABLE], np.nonzero(rec[:, 7] == KIND_RANGE)[0])
+    if bad_rows.size:
+        r = int(bad_rows[0])
+        mine = row == r
+        for e, ty in sorted(zip(entry[mine].tolist(), typ[mine].tolist()), reverse=True):
+            if ty == TYPE_UNRESOLVABLE:
+                raise et.errors[(e, "type")]
+        raise IndexError("row %d: read %d: entry, offset or poly-T tail out of range" % (r, int(rec[r, 0])))
+    # the report loop: a hit without amino acid, then a de-duplicated name that is no hit of the read or has no amino acid
+    E = et.desc.shape[0]
+    ok = entry < E
+    entry = np.where(ok, entry, 0)
+    no_aa = np.array([x is None for x in et.aa_types], dtype=bool)
+    rep = et.desc[entry, 5].astype(np.int64)
+    rep_is_hit = (rep >= 0) & np.isin(row * (E + 1) + rep, row * (E + 1) + entry)
+    bad = no_aa[entry] | ~rep_is_hit | et.rep_aa_missing[entry]
+    if bad.any():
+        r = int(row[bad].min())
+        mine = np.nonzero(row == r)[0]
+        es = sorted(entry[mine].tolist(), reverse=True)
+        for e in es:
+            if no_aa[e]:
+                raise et.errors[(e, "aa")]
+        by_rank = sorted(set((int(et.desc[e, 4]), et.rep_names[e], bool(et.rep_aa_missing[e])) for e in es))
+        for _, name, missing in by_rank:
+            if missing:
+                raise KeyError(name)
+        have = {et.names[e] for e in es}
+        for _, name, _ in by_rank:
+            if name not in have:
+                raise KeyError(name)
+    # the counting loop: the selected tRNA's template, the merged entity of the assigned predefined tRF
+    for r in np.nonzero((rec[:, 7] == KIND_UNRESOLVABLE) | (rec[:, 7] == KIND_ASSIGNED))[0].tolist():
+        if rec[r, 7] == KIND_UNRESOLVABLE:
+            raise et.errors.get((int(rec[r, 1]), "length"), KeyError("row %d" % r))
+        if ("cluster", int(rec[r, 5])) in et.errors:
+            raise et.errors[("cluster", int(rec[r, 5]))]
+
+
+def content_from_rows(et, rec, seqs, quant, denom):
+    """The trfContentDic write_trf_tables leaves (one tRNA per read, with uid, count and RPM), from the rows in the order of
+    the tsv: what trf_samples.write_trf_samples starts from.  seqs[r] = the read of row r, quant[r] its counts, denom[s] =
+    maturetrnaReads + pretrnaReads of sample s.  The per-read Python that remains on the array route."""
+    content = {}
+    S = len(denom)
+    for r, row in enumerate(rec.tolist()):
+        if row[7] > KIND_DELE:
+            continue
+        count = [int(x) for x in quant[r]]
+        content[seqs[r]] = {"count": count, "uid": make_id(seqs[r], NT2CODE),
+                            "RPM": [100000.0 * count[i] / denom[i] if denom[i] else 0.0 for i in range(S)],
+                            et.names[row[1]]: {"tRFType": TRF_TYPES[row[4]], "start": row[2], "end": row[3],
+                                               "cigar": "undifined"}}
+    return content
