@@ -1059,6 +1059,57 @@ int mrg_write_trf_tables(const char *const *paths, const char *const *samples, u
                          uint64_t *rows);
 
 /*
+ * `annotate -ai`: every read claimed by the exact-miRNA or the isomiR pass aligned to the canonical sequence of its (merged)
+ * miRNA, and a2IEditing.detail.txt, from the arrays.  mirge_amd/a2i.py holds the Python model (local_pair, judge_align,
+ * a2i_editing) whose results the two calls reproduce exactly; DESIGN.md 8.6 holds the argument.
+ *
+ * mrg_a2i_align         DEVICE arrays of a cascade (reads [W][stride], W in {1, 2, 4, 8}; d_nmask or NULL; pass_id, ref_id;
+ *                       d_keep: uint8 per read, 0 = leave the read out, or NULL) and the HOST tables of
+ *                       mirge_amd.a2i.target_table, which the call checks and uploads:
+ *                         canon_target / isomir_target  int32 per entry of the library the pass aligns to: its target id, -1
+ *                                                       = none;
+ *                         target_words / target_lens    per target its sequence, 2 bits per base as the reads, and its length:
+ *                                                       1..32, or 0 for a target that cannot be aligned here (no sequence,
+ *                                                       more than 32 bases, a character other than ACGT).
+ *                       Rows: the selected reads in array order (flags, an exclusive prefix sum and a scatter on the device).
+ *                       counts[0] (HOST) = their number.  Capacity as for mrg_isomir_classify: rows >= cap are not written, a
+ *                       call with cap = 0 (output pointers may be NULL) only counts.  d_idx[row] = the read; d_rec[row] =
+ *                       int32 [4] (16-byte aligned):
+ *                         [0] status | verdict << 8 | substring << 9 | m << 16
+ *                             status 0 = simple: `localms(target, read, 2, -1, -20, -20)` lists first the ungapped frame of
+ *                                        diagonal d (the best ungapped local score m > 0 ends in one cell only and every path
+ *                                        with a gap scores below m);
+ *                                    1 = the best ungapped score ends in several cells, 2 = a path with a gap reaches m,
+ *                                    3 = m == 0, 4 = unsupported (a read of 0 or more than 32 bases, no usable target);
+ *                             verdict   = judge_align on the frame; substring = the read occurs in the target
+ *                         [1] d = target position - read position
+ *                         [2] bit k set: k < target length - 5, target[k] == from_base and read[k - d] == to_base (codes 0..3)
+ *                         [3] the target id, -1 = none
+ *                       Everything but status, m and the target id is 0 unless status is 0.  A read's N equals nothing.
+ *                       *kernel_ms (or NULL) = the alignment kernel alone, from device events.  Synchronises `stream`.
+ * mrg_write_a2i_detail  HOST arrays.  Block b = one (miRNA, sample): rows [block_off[b], block_off[b + 1]), the miRNA
+ *                       block_group[b] (its name and canonical sequence in group_names / group_targets), block_frame[b] =
+ *                       {dashes in front of the target, dashes behind it}.  Row r: the read row_read[r] of the arrays, its
+ *                       count, row_flags (bit 0 = verdict, bit 1 = retained by the genome filter) and its diagonal.  Writes the
+ *                       blocks as a2i_editing does; a block with block_text[b] != NULL (block_text itself may be NULL) is that
+ *                       text, written as it is.  *lines (or NULL) = lines written.  Runs of blocks are formatted by worker
+ *                       threads (MIRGE_AMD_TABLE_THREADS, at most 16; MIRGE_AMD_A2I_RUN_BLOCKS = blocks per run, default 256,
+ *                       lowered by tests); the bytes depend on neither.
+ */
+int mrg_a2i_align(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                  const uint64_t *d_nmask, uint64_t n, const int8_t *d_pass_id, const int32_t *d_ref_id,
+                  const uint8_t *d_keep, int32_t canon_pass, int32_t isomir_pass, const int32_t *canon_target,
+                  uint64_t n_canon, const int32_t *isomir_target, uint64_t n_isomir, const uint64_t *target_words,
+                  const uint8_t *target_lens, uint64_t n_targets, uint32_t from_base, uint32_t to_base, uint64_t cap,
+                  uint32_t *d_idx, int32_t *d_rec, uint64_t *counts, float *kernel_ms, void *stream);
+int mrg_write_a2i_detail(const char *path, const uint64_t *reads, uint32_t words_per_read, uint64_t stride,
+                         const uint8_t *lens, const uint64_t *nmask, uint64_t n, uint64_t n_blocks, const uint64_t *block_off,
+                         const int32_t *block_group, const int32_t *block_frame, const char *const *block_text,
+                         const char *const *group_names, const char *const *group_targets, uint64_t n_groups,
+                         const uint32_t *row_read, const uint32_t *row_count, const uint8_t *row_flags, const int32_t *row_d,
+                         uint64_t *lines);
+
+/*
  * -trf: density-peak clustering (Rodriguez-Laio) of the per-sample tRF reports, the O(n^2) parts of
  * utils/writeDataToCSV.py (W2C) :802-1088 for every (sample, tRNA) group of one run at once.
  * Group g owns rows [off[g], off[g+1]) (off: HOST array of n_groups + 1, off[0] = 0), in the order of its

@@ -12,7 +12,8 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
   * `-ad illumina|ion|<sequence>|+N` is applied as trim_file.py does (3' quality trimming,
     cutadapt's 3' adapter search restated, 16-nt minimum);
   * `-ai` reads the genome from `<sp>_genome.mrgfm` / `.fa` or `<sp>_genome.partNNN.mrgfm`
-    (`build_index --max-bases 500000000`) and answers the two genome bowtie runs on the GPU;
+    (`build_index --max-bases 500000000`) and answers the two genome bowtie runs on the GPU, aligns the miRNA reads to
+    their miRNA on the GPU and reports from the arrays (`--ai-host`: through per-read records and Python alignments);
   * `-trf` writes `tRFs.potential.report.tsv`, `tRF.Counts.csv`, `tRF.RP100K.csv`,
     `discarded.reads.summary.assigningtRFs.csv` and the per-sample reports and density-peak clusters
     of `tRFs.samples.tmp/` (mirge_amd.trf_samples, clustered on the GPU); the PDF report is not produced.
@@ -47,6 +48,9 @@ def build_parser():
     p.add_argument("-di", dest="diff_isomirs", action="store_true")
     p.add_argument("-cpu", dest="cpu", metavar="<int>", default="1")
     p.add_argument("-ai", dest="a_to_i", action="store_true")
+    p.add_argument("--ai-host", dest="ai_host", action="store_true",
+                   help="extension: the -ai report through the per-read Python records and alignments instead of the GPU "
+                        "alignment (same files)")
     p.add_argument("-gff", dest="gff_output", action="store_true")
     p.add_argument("--gff-host", dest="gff_host", action="store_true",
                    help="extension: -gff through the per-read Python records instead of the GPU classification (same files)")
@@ -469,7 +473,10 @@ def annotate_main(args, engine_factory=None, materialize=False):
     trf_records = args.trf_output and (long_trna or args.trf_host)
     if not trf_records:
         want -= {2, 3}
-    need_records = gff_records or trf_records or args.a_to_i or (args.diff_isomirs and long_mirna)
+    # -ai: aligned on the GPU and reported from the arrays (Engine.a2i_align, a2i.a_to_i_report_arrays) unless a read beyond
+    # 255 nt was claimed by a miRNA pass, or --ai-host asks for the records
+    ai_records = args.a_to_i and (long_mirna or args.ai_host)
+    need_records = gff_records or trf_records or ai_records or (args.diff_isomirs and long_mirna)
     sub, align = {}, {}
     if need_records:
         sub, align = columnar.read_subset(h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, h_pos, h_mm, npp, want, spike)
@@ -528,9 +535,19 @@ def annotate_main(args, engine_factory=None, materialize=False):
                                    sample_list, columnar.isomir_dic(sub, S), log_dic)
     report.write_counts_csv(os.path.join(outdir, "miR.Counts.csv"), sample_list, mir_dic, log_dic)
     report.write_rpm_csv(os.path.join(outdir, "miR.RPM.csv"), sample_list, mir_dic, log_dic)
-    if args.a_to_i:   # W2C:1221
+    if args.a_to_i and ai_records:   # W2C:1221
         from .a2i import a_to_i_report
         a_to_i_report(outdir, sample_list, log_dic, sub, mir_dic, name_seq, merged_name, removed_ai, genome)
+    elif args.a_to_i:   # from the arrays
+        from . import a2i
+        table = a2i.target_table(npp, merged_name, name_seq, CANON_PASS, ISOMIR_PASS)
+        keep = a2i.keep_mask(h_quant, h_pass, log_dic, CANON_PASS)
+        if world > 1:   # (the gathered host arrays)
+            a_idx, a_rec = engine.a2i_align(table, h_words, h_lens, h_nmask, h_pass, h_ref, keep)
+        else:
+            a_idx, a_rec = engine.a2i_align(table, shard.words, shard.lens, shard.nmask, res.pass_id, res.ref_id, keep)
+        a2i.a_to_i_report_arrays(outdir, sample_list, log_dic, h_words, h_lens, h_nmask, h_quant, h_pass, a_idx, a_rec, table,
+                                 mir_dic, name_seq, removed_ai, genome, canon_pass=CANON_PASS)
     print("Summary Complete (%.2f sec)" % (time.time() - t3))
     print("Annotation of miRge2.0 Completed (%.2f sec)" % (time.time() - t0))
     mdist.barrier()

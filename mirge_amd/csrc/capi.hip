@@ -22,6 +22,7 @@
 #include "pgzip.hpp"
 #include "fastq.hpp"
 #include "fm_index.hpp"
+#include "a2i_align.hpp"
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
@@ -3852,6 +3853,142 @@ int mrg_write_trf_tables(const char* const* paths, const char* const* samples, u
     return fail(MRG_ERR_ARG, "mrg_write_trf_tables: %s", e.what());
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "mrg_write_trf_tables: %s", e.what());
+  }
+}
+
+// ------------------------------------------------------------- -ai
+int mrg_a2i_align(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                  const uint64_t* d_nmask, uint64_t n, const int8_t* d_pass_id, const int32_t* d_ref_id, const uint8_t* d_keep,
+                  int32_t canon_pass, int32_t isomir_pass, const int32_t* canon_target, uint64_t n_canon,
+                  const int32_t* isomir_target, uint64_t n_isomir, const uint64_t* target_words, const uint8_t* target_lens,
+                  uint64_t n_targets, uint32_t from_base, uint32_t to_base, uint64_t cap, uint32_t* d_idx, int32_t* d_rec,
+                  uint64_t* counts, float* kernel_ms, void* stream) {
+  if (!ctx || !counts) return fail(MRG_ERR_ARG, "mrg_a2i_align: null argument");
+  if (kernel_ms) *kernel_ms = 0.0f;
+  if (n && (!d_reads || !d_lens || !d_pass_id || !d_ref_id)) return fail(MRG_ERR_ARG, "mrg_a2i_align: null buffers");
+  if ((n_canon && !canon_target) || (n_isomir && !isomir_target) || (n_targets && (!target_words || !target_lens)))
+    return fail(MRG_ERR_ARG, "mrg_a2i_align: null tables");
+  if (cap && (!d_idx || !d_rec)) return fail(MRG_ERR_ARG, "mrg_a2i_align: null output buffers");
+  if (((uintptr_t)d_rec & 15u) != 0) return fail(MRG_ERR_ARG, "mrg_a2i_align: d_rec must be 16-byte aligned");
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "mrg_a2i_align: words_per_read must be 1, 2, 4 or 8");
+  if (stride < n || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_a2i_align: bad stride / n");
+  if (canon_pass == isomir_pass || canon_pass < 0 || isomir_pass < 0 || canon_pass > 127 || isomir_pass > 127)
+    return fail(MRG_ERR_ARG, "mrg_a2i_align: the two passes must differ and lie in 0..127");
+  if (from_base > 3 || to_base > 3) return fail(MRG_ERR_ARG, "mrg_a2i_align: from_base / to_base are codes 0..3");
+  if (n_canon >= (1ull << 31) || n_isomir >= (1ull << 31) || n_targets >= (1ull << 31))
+    return fail(MRG_ERR_ARG, "mrg_a2i_align: tables too large");
+  // the kernel trusts the tables: every target id is -1 or a target, every target has at most 32 bases
+  for (int t = 0; t < 2; ++t) {
+    const int32_t* tab = t ? isomir_target : canon_target;
+    const uint64_t len = t ? n_isomir : n_canon;
+    for (uint64_t e = 0; e < len; ++e)
+      if (tab[e] < -1 || (tab[e] >= 0 && (uint64_t)tab[e] >= n_targets))
+        return fail(MRG_ERR_ARG, "mrg_a2i_align: entry %llu of the %s table names target %d of %llu", (unsigned long long)e,
+                    t ? "isomiR" : "canonical", tab[e], (unsigned long long)n_targets);
+  }
+  for (uint64_t t = 0; t < n_targets; ++t) {
+    if (target_lens[t] > 32) return fail(MRG_ERR_ARG, "mrg_a2i_align: target %llu has %u bases (at most 32)", (unsigned long long)t, target_lens[t]);
+    if (target_lens[t] < 32 && (target_words[t] >> (2 * target_lens[t])) != 0)
+      return fail(MRG_ERR_ARG, "mrg_a2i_align: target %llu holds bits beyond its length", (unsigned long long)t);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  counts[0] = 0;
+  if (n == 0) return MRG_OK;
+  // context scratch: [canon table | isomiR table | target words | target lengths | flags -> offsets (n + 1) | scan scratch]
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  const uint64_t n_flags = n + 1;
+  const uint64_t o_canon = 0, o_iso = o_canon + up(n_canon * sizeof(int32_t)), o_tw = o_iso + up(n_isomir * sizeof(int32_t)),
+                 o_tl = o_tw + up(n_targets * sizeof(uint64_t)), o_flags = o_tl + up(n_targets),
+                 o_tmp = o_flags + up(n_flags * sizeof(uint32_t)), need_bytes = o_tmp + up(mrg::prims::scan_temp_bytes(n_flags));
+  if (ctx->scratch_bytes < need_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(ctx->scratch);
+    ctx->scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->scratch, need_bytes));
+    ctx->scratch_bytes = need_bytes;
+  }
+  char* base = (char*)ctx->scratch;
+  uint32_t* flags = (uint32_t*)(base + o_flags);
+  // select and order: the exclusive sums of the flags are the rows (as mrg_isomir_classify; one list, in array order)
+  HIP_TRY(mrg::a2i_flags_launch(d_pass_id, d_keep, n, canon_pass, isomir_pass, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n_flags, base + o_tmp, st));
+  uint32_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  counts[0] = total;
+  const uint64_t rows = std::min<uint64_t>(total, cap);
+  if (rows == 0) return MRG_OK;
+  HIP_TRY(mrg::a2i_scatter_launch(d_pass_id, d_keep, n, canon_pass, isomir_pass, flags, cap, d_idx, st));
+  if (n_canon) HIP_TRY(hipMemcpyAsync(base + o_canon, canon_target, n_canon * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (n_isomir) HIP_TRY(hipMemcpyAsync(base + o_iso, isomir_target, n_isomir * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (n_targets) {
+    HIP_TRY(hipMemcpyAsync(base + o_tw, target_words, n_targets * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(base + o_tl, target_lens, n_targets, hipMemcpyHostToDevice, st));
+  }
+  mrg::A2iAlignParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.pass_id = d_pass_id;
+  p.ref_id = d_ref_id;
+  p.idx = d_idx;
+  p.rows = (uint32_t)rows;
+  p.canon_pass = canon_pass;
+  p.canon_target = (const int32_t*)(base + o_canon);
+  p.n_canon = (uint32_t)n_canon;
+  p.isomir_target = (const int32_t*)(base + o_iso);
+  p.n_isomir = (uint32_t)n_isomir;
+  p.target_words = (const uint64_t*)(base + o_tw);
+  p.target_lens = (const uint8_t*)(base + o_tl);
+  p.n_targets = (uint32_t)n_targets;
+  p.from_base = from_base;
+  p.to_base = to_base;
+  p.rec = d_rec;
+  // kernel_ms: a2i_align_kernel alone, between two events on the stream
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipError_t e = hipSuccess;
+  if (kernel_ms) {
+    e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, st);
+  }
+  if (e == hipSuccess) e = mrg::a2i_align_launch(p, st);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev1, st);
+  // (the tables were copied from pageable host memory, which the caller may free on return)
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, ev0, ev1);
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  HIP_TRY(e);
+  return MRG_OK;
+}
+
+int mrg_write_a2i_detail(const char* path, const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens,
+                         const uint64_t* nmask, uint64_t n, uint64_t n_blocks, const uint64_t* block_off, const int32_t* block_group,
+                         const int32_t* block_frame, const char* const* block_text, const char* const* group_names,
+                         const char* const* group_targets, uint64_t n_groups, const uint32_t* row_read, const uint32_t* row_count,
+                         const uint8_t* row_flags, const int32_t* row_d, uint64_t* lines) {
+  if (!path || !block_off) return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: null argument");
+  if (n_blocks && (!block_group || !block_frame || !group_names || !group_targets))
+    return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: null block tables");
+  if (block_off[n_blocks] && (!reads || !lens || !row_read || !row_count || !row_flags || !row_d))
+    return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: null buffers");
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: bad words_per_read / stride");
+  for (uint64_t g = 0; g < n_groups; ++g)
+    if (!group_names[g] || !group_targets[g]) return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: null group name / target");
+  try {
+    const mrg::A2iDetailArgs a{path, reads, words_per_read, stride, lens, nmask, n, n_blocks, block_off, block_group, block_frame,
+                               block_text, group_names, group_targets, n_groups, row_read, row_count, row_flags, row_d};
+    mrg::write_a2i_detail(a, lines);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: %s", e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "mrg_write_a2i_detail: %s", e.what());
   }
 }
 

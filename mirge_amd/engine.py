@@ -596,6 +596,63 @@ class Engine:
         return (idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k], mask.cpu().numpy().view(np.uint64)[:k],
                 int(counts[0]), int(counts[1]))
 
+    def a2i_align(self, table, words, lens, nmask, pass_id, ref_id, keep=None, timings=None, from_base="A", to_base="G",
+                  canon_pass=CANON_PASS, isomir_pass=ISOMIR_PASS):
+        """The rows of the `-ai` report (mrg_a2i_align): the reads claimed by canon_pass or isomir_pass (and, where `keep`
+        is given, with keep != 0), in array order, each aligned to the canonical sequence of its miRNA in `table`
+        (a2i.target_table).  words [W, n] / lens / nmask (or None) / pass_id / ref_id / keep: the device tensors of a
+        ReadSet and a CascadeResult, or host arrays (uploaded).  Returns host arrays (idx uint32 [k], rec int32 [k, 4]:
+        status | verdict << 8 | substring << 9 | m << 16, the diagonal, the edit mask, the target id).  timings: a dict that
+        receives `kernel_ms`, the time of the alignment kernel alone (device events inside the call), and `align_call_ms`,
+        the whole filling call.  The rows are counted by a first call and filled by a second."""
+        torch = _torch()
+        from .a2i import BASE_CODE
+
+        def dev(x, np_dtype, view=None):
+            if x is None or torch.is_tensor(x):
+                return x
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+        words = dev(words, np.uint64, np.int64).contiguous()
+        nmask = dev(nmask, np.uint64, np.int64)
+        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
+        ref_id = dev(ref_id, np.int32).contiguous()
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        if keep is not None:
+            keep = (keep.to(torch.uint8) if torch.is_tensor(keep) else dev(np.asarray(keep) != 0, np.uint8)).contiguous()
+        W, n = int(words.shape[0]), int(words.shape[1])
+        canon_t = np.ascontiguousarray(table.by_pass[canon_pass], dtype=np.int32)
+        iso_t = np.ascontiguousarray(table.by_pass[isomir_pass], dtype=np.int32)
+        t_words = np.ascontiguousarray(table.words, dtype=np.uint64)
+        t_lens = np.ascontiguousarray(table.lens, dtype=np.uint8)
+        counts = (C.c_uint64 * 1)()
+        kernel_ms = C.c_float(0.0)
+
+        def call(cap, idx, rec):
+            check(self._lib.mrg_a2i_align(
+                self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(), n,
+                pass_id.data_ptr(), ref_id.data_ptr(), None if keep is None else keep.data_ptr(), int(canon_pass),
+                int(isomir_pass), canon_t.ctypes.data, canon_t.shape[0], iso_t.ctypes.data, iso_t.shape[0],
+                t_words.ctypes.data, t_lens.ctypes.data, t_lens.shape[0], BASE_CODE[from_base], BASE_CODE[to_base], cap,
+                None if idx is None else idx.data_ptr(), None if rec is None else rec.data_ptr(), counts,
+                None if timings is None else C.byref(kernel_ms), self._stream_ptr()))
+        call(0, None, None)
+        k = int(counts[0])
+        idx = torch.empty(max(k, 1), dtype=torch.int32, device=self.device)
+        rec = torch.empty((max(k, 1), 4), dtype=torch.int32, device=self.device)
+        if k:
+            if timings is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            call(k, idx, rec)
+            if timings is not None:
+                e1.record()
+                e1.synchronize()
+                timings["align_call_ms"] = e0.elapsed_time(e1)
+                timings["kernel_ms"] = float(kernel_ms.value)
+        return idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k]
+
     def trf_classify(self, et, words, lens, nmask, pass_id, mature_pass=2, trailer_pass=3, mature_lib="mature_trna",
                      pre_lib="pre_trna", timings=None):
         """The rows of the `-trf` tables (mrg_trf_classify): the reads claimed by mature_pass in array order, then those
