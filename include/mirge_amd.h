@@ -313,7 +313,8 @@ typedef struct mrg_pass_stats {
   uint32_t kbits_log2; /* log2 of the bits of the 9-mer presence bitmap the pass filtered seed
                           pieces with (18 = the library's full bitmap, 13..17 = folded for a
                           fused launch, 0 = no filter) */
-  uint32_t pair_anchor; /* != 0, pass with ONE seed mismatch (fused launch, large library): reads of
+  uint32_t pair_anchor; /* != 0, pass with ONE seed mismatch (fused launch, or seed launch in wave_seed_kernel with seed
+                          buckets; large library): reads of
                           3 x pair_anchor .. 4 x pair_anchor - 1 seed bases were searched through the
                           three pairs of three anchors, the others through the pigeonhole pieces.
                           != 0, TWO seed mismatches: reads of at least 4 x pair_anchor seed bases

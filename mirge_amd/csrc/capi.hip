@@ -1847,6 +1847,11 @@ int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
       if (with_buckets)
         for (uint32_t q = first; q < end; ++q)
           if (ctx->last_mode[q] == 8u) ctx->last_mode[q] = 9u;
+      // mrg_pass_stats.pair_anchor, as a fused launch reports it: only wave_seed_kernel's instantiation with buckets
+      // parks the reads of 3 A .. 4 A - 1 seed bases for the three anchor pairs
+      for (uint32_t u = 0; u < sp.n_units; ++u)
+        if (sp.impl && with_buckets && sp.unit[u].bpair_anchor)
+          for (uint32_t i : plan[u].members) ctx->last_pair_anchor[i] = sp.unit[u].bpair_anchor;
     }
     const uint32_t lds = mrg::seed_lds_bytes(sp);
     (void)lds;
