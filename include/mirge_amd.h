@@ -1081,13 +1081,31 @@ int mrg_write_trf_tables(const char *const *paths, const char *const *samples, u
  *                                        diagonal d (the best ungapped local score m > 0 ends in one cell only and every path
  *                                        with a gap scores below m);
  *                                    1 = the best ungapped score ends in several cells, 2 = a path with a gap reaches m,
- *                                    3 = m == 0, 4 = unsupported (a read of 0 or more than 32 bases, no usable target);
+ *                                    3 = m == 0, 4 = unsupported (a read of 0 or more than 32 bases, no usable target),
+ *                                    5 = a row of status 1 that mrg_a2i_settle settled (below);
  *                             verdict   = judge_align on the frame; substring = the read occurs in the target
  *                         [1] d = target position - read position
  *                         [2] bit k set: k < target length - 5, target[k] == from_base and read[k - d] == to_base (codes 0..3)
  *                         [3] the target id, -1 = none
- *                       Everything but status, m and the target id is 0 unless status is 0.  A read's N equals nothing.
+ *                       Everything but status, m and the target id is 0 unless status is 0 (or 5).  A read's N equals nothing.
  *                       *kernel_ms (or NULL) = the alignment kernel alone, from device events.  Synchronises `stream`.
+ * mrg_a2i_settle        The rows of status 1 among the k rows d_idx / d_rec (DEVICE) that a filling mrg_a2i_align call wrote,
+ *                       walked once more: where every path with a gap scores below m, `localms` lists first the ungapped
+ *                       frame of one of the tied cells, and the row is rewritten in place as
+ *                         [0] status 5 | verdict << 8 | substring << 9 | m << 16   (m as it was)
+ *                         [1] d   [2] the edit mask   [3] the target id (as it was)
+ *                       exactly as a row of status 0 is filled.  The cell: a best cell is eligible iff no cell above it in
+ *                       the positive run of its diagonal holds m; pairwise2 passes the best score along the last row and
+ *                       the last column and stops listing at the first passed-along cell X whose upper-left neighbour is a
+ *                       best cell; the answer is the last eligible cell before X in (target position, read position) order
+ *                       (DESIGN.md 8.6).  A row of status 1 with a gapped path that reaches m keeps every byte, as does every
+ *                       row of another status, so a second call examines the rows still of status 1 and changes nothing.
+ *                       Reads, lens, nmask, the HOST tables and from_base / to_base as given to mrg_a2i_align (the tables are
+ *                       checked in the same way before any launch; the target of a row is the id in its record; a record
+ *                       whose read or target id is out of range is left as it is).  counts (HOST, 2 values): [0] rows
+ *                       examined (status 1), [1] rows settled.  *kernel_ms (or NULL) = the settling kernel alone.
+ *                       Synchronises `stream`.  The arguments are checked before the context, so a machine without a device
+ *                       names a bad table; a NULL context is an error (there is no host route).
  * mrg_write_a2i_detail  HOST arrays.  Block b = one (miRNA, sample): rows [block_off[b], block_off[b + 1]), the miRNA
  *                       block_group[b] (its name and canonical sequence in group_names / group_targets), block_frame[b] =
  *                       {dashes in front of the target, dashes behind it}.  Row r: the read row_read[r] of the arrays, its
@@ -1103,6 +1121,11 @@ int mrg_a2i_align(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read
                   uint64_t n_canon, const int32_t *isomir_target, uint64_t n_isomir, const uint64_t *target_words,
                   const uint8_t *target_lens, uint64_t n_targets, uint32_t from_base, uint32_t to_base, uint64_t cap,
                   uint32_t *d_idx, int32_t *d_rec, uint64_t *counts, float *kernel_ms, void *stream);
+int mrg_a2i_settle(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                   const uint64_t *d_nmask, uint64_t n, const int32_t *canon_target, uint64_t n_canon,
+                   const int32_t *isomir_target, uint64_t n_isomir, const uint64_t *target_words, const uint8_t *target_lens,
+                   uint64_t n_targets, uint32_t from_base, uint32_t to_base, uint64_t k, const uint32_t *d_idx, int32_t *d_rec,
+                   uint64_t *counts, float *kernel_ms, void *stream);
 int mrg_write_a2i_detail(const char *path, const uint64_t *reads, uint32_t words_per_read, uint64_t stride,
                          const uint8_t *lens, const uint64_t *nmask, uint64_t n, uint64_t n_blocks, const uint64_t *block_off,
                          const int32_t *block_group, const int32_t *block_frame, const char *const *block_text,

@@ -233,6 +233,10 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p,
                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p,
                                 C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_void_p]),
+    "mrg_a2i_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                 C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                 C.c_void_p]),
     "mrg_write_a2i_detail": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_void_p,

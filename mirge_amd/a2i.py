@@ -408,6 +408,7 @@ def a_to_i_report(outputdir, sampleList, logDic, seqDic, mirDic, mirNameSeqDic, 
 REC_INTS = 4
 REC_FLAGS, REC_DIAG, REC_MASK, REC_TARGET = 0, 1, 2, 3
 ST_SIMPLE, ST_ENDS, ST_GAPPED, ST_NOSCORE, ST_UNSUPPORTED = 0, 1, 2, 3, 4
+ST_TIED = 5   # a row of status 1 that mrg_a2i_settle settled (Engine.a2i_align(settle=True)): filled as a row of status 0
 BASE_CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
 
 
@@ -501,10 +502,11 @@ def a_to_i_report_arrays(outputdir, sampleList, logDic, words, lens, nmask, quan
     same three files, the same returned rows.  No Python loop runs over reads: the groups, the RPM selections, the
     frames and the counts are numpy over the records; Python walks the (miRNA, sample) blocks that hold an edited
     position, the sites, and -- through a2i_editing on strings unpacked for that block only -- the blocks whose
-    selection holds a read the kernel did not settle (status other than 0).  Those blocks align only such reads, and each
+    selection holds a read the kernels did not settle (status other than 0 and 5).  Those blocks align only such reads, and each
     of them once, not once per sample: while they run, the module's local_pair is a memo of itself (it is a pure
     function of its arguments) that already holds the frames of the block's simple pairs.
-    timings: a dict that receives `blocks`, `host_blocks`, `host_blocks_s` and `detail_write_s`."""
+    timings: a dict that receives `blocks`, `host_blocks`, `host_blocks_s`, `detail_write_s` and `tied_rows` (the rows of
+    status 5 among those kept)."""
     global local_pair
     import io
     import time
@@ -534,6 +536,7 @@ def a_to_i_report_arrays(outputdir, sampleList, logDic, words, lens, nmask, quan
     status = rec[:, REC_FLAGS] & 0xFF
     verdict = ((rec[:, REC_FLAGS] >> 8) & 1).astype(bool)
     substr = ((rec[:, REC_FLAGS] >> 9) & 1).astype(bool)
+    settled = (status == ST_SIMPLE) | (status == ST_TIED)                # the record holds the frame
     diag = rec[:, REC_DIAG].astype(np.int64)
     mask = rec[:, REC_MASK].view(np.uint32)
     sub_w = np.ascontiguousarray(words[:, idx])
@@ -558,7 +561,7 @@ def a_to_i_report_arrays(outputdir, sampleList, logDic, words, lens, nmask, quan
     n_sel = np.bincount(flat[sel], minlength=G * S)
     sel &= n_sel[flat] > 1                                                # (W2C:1309 len(cnt) > 1; every count is > 0)
     host = np.zeros(G * S, dtype=bool)
-    host[flat[sel & (status != ST_SIMPLE)[:, None]]] = True
+    host[flat[sel & ~settled[:, None]]] = True
     la = np.array([len(t) for t in g_targets], dtype=np.int64)[gid] if k else np.zeros(0, dtype=np.int64)
     lb = lens[idx].astype(np.int64)
 
@@ -635,7 +638,7 @@ def a_to_i_report_arrays(outputdir, sampleList, logDic, words, lens, nmask, quan
             cnt = q[rows, i].tolist()
             text = io.StringIO()
             for seq, row in zip(seqs, rows.tolist()):   # what the kernel settled is not aligned again
-                if status[row] == ST_SIMPLE and (g_targets[g], seq) not in memo:
+                if settled[row] and (g_targets[g], seq) not in memo:
                     d_, la_, lb_ = int(diag[row]), len(g_targets[g]), len(seq)
                     memo[(g_targets[g], seq)] = ("-" * max(0, -d_) + g_targets[g] + "-" * max(0, d_ + lb_ - la_),
                                                  "-" * max(0, d_) + seq + "-" * max(0, la_ - d_ - lb_))
@@ -663,7 +666,7 @@ def a_to_i_report_arrays(outputdir, sampleList, logDic, words, lens, nmask, quan
                      verdict[r_pi].astype(np.uint8) | (retained[r_pi].astype(np.uint8) << 1), diag[r_pi])
     if timings is not None:
         timings.update(blocks=int(blocks.size), host_blocks=int(host[blocks].sum()), host_blocks_s=host_s,
-                       detail_write_s=time.time() - t_write)
+                       detail_write_s=time.time() - t_write, tied_rows=int((status == ST_TIED).sum()))
     return _write_reports(outputdir, sampleList, rpm, site_order, site_values, mirNameSeqDic, removedMiRNAList, genome,
                           end_base)
 

@@ -543,9 +543,10 @@ def annotate_main(args, engine_factory=None, materialize=False):
         table = a2i.target_table(npp, merged_name, name_seq, CANON_PASS, ISOMIR_PASS)
         keep = a2i.keep_mask(h_quant, h_pass, log_dic, CANON_PASS)
         if world > 1:   # (the gathered host arrays)
-            a_idx, a_rec = engine.a2i_align(table, h_words, h_lens, h_nmask, h_pass, h_ref, keep)
+            a_idx, a_rec = engine.a2i_align(table, h_words, h_lens, h_nmask, h_pass, h_ref, keep, settle=True)
         else:
-            a_idx, a_rec = engine.a2i_align(table, shard.words, shard.lens, shard.nmask, res.pass_id, res.ref_id, keep)
+            a_idx, a_rec = engine.a2i_align(table, shard.words, shard.lens, shard.nmask, res.pass_id, res.ref_id, keep,
+                                            settle=True)
         a2i.a_to_i_report_arrays(outdir, sample_list, log_dic, h_words, h_lens, h_nmask, h_quant, h_pass, a_idx, a_rec, table,
                                  mir_dic, name_seq, removed_ai, genome, canon_pass=CANON_PASS)
     print("Summary Complete (%.2f sec)" % (time.time() - t3))

@@ -15,6 +15,7 @@ constexpr int kA2iRecMask = 2;    // bit k: k < la - 5, target[k] == from_base, 
 constexpr int kA2iRecTarget = 3;  // target id (-1 = none)
 // status
 constexpr uint32_t kA2iSimple = 0, kA2iEnds = 1, kA2iGapped = 2, kA2iNoScore = 3, kA2iUnsupported = 4;
+constexpr uint32_t kA2iTied = 5;  // a row of status 1 that mrg_a2i_settle settled: d, verdict, substring and mask as for 0
 
 struct A2iAlignParams {
   const uint64_t* reads;  // [W][stride]; only word 0 is read (a read beyond 32 nt is unsupported)
@@ -43,6 +44,28 @@ hipError_t a2i_flags_launch(const int8_t* pass_id, const uint8_t* keep, uint64_t
 hipError_t a2i_scatter_launch(const int8_t* pass_id, const uint8_t* keep, uint64_t n, int32_t canon_pass, int32_t isomir_pass,
                               const uint32_t* off, uint64_t cap, uint32_t* idx, hipStream_t stream);
 hipError_t a2i_align_launch(const A2iAlignParams& p, hipStream_t stream);
+
+struct A2iSettleParams {
+  const uint64_t* reads;         // as A2iAlignParams
+  const uint64_t* nmask;
+  const uint8_t* lens;
+  uint64_t n_reads;
+  const uint32_t* idx;           // row -> read
+  int32_t* rec;                  // [k][kA2iRecInts], rewritten in place where a row is settled
+  const uint32_t* sel;           // the rows of status 1
+  uint32_t n_sel;
+  const uint64_t* target_words;
+  const uint8_t* target_lens;
+  uint32_t n_targets;
+  uint32_t from_base, to_base;
+  uint32_t* settled;             // += rows settled
+};
+
+// flags[i] = row i of rec has status 1, flags[k] = 0
+hipError_t a2i_tied_select_launch(const int32_t* rec, uint64_t k, uint32_t* flags, hipStream_t stream);
+// sel[off[i]] = i for every row of status 1 (off = exclusive sums of the flags)
+hipError_t a2i_tied_scatter_launch(const int32_t* rec, uint64_t k, const uint32_t* off, uint32_t* sel, hipStream_t stream);
+hipError_t a2i_settle_launch(const A2iSettleParams& p, hipStream_t stream);
 
 struct A2iDetailArgs {
   const char* path;

@@ -3862,6 +3862,25 @@ int mrg_write_trf_tables(const char* const* paths, const char* const* samples, u
 }
 
 // ------------------------------------------------------------- -ai
+// The kernels trust the tables: every target id is -1 or a target, every target has at most 32 bases.  MRG_OK or the failure.
+static int a2i_check_tables(const char* fn, const int32_t* canon_target, uint64_t n_canon, const int32_t* isomir_target,
+                            uint64_t n_isomir, const uint64_t* target_words, const uint8_t* target_lens, uint64_t n_targets) {
+  for (int t = 0; t < 2; ++t) {
+    const int32_t* tab = t ? isomir_target : canon_target;
+    const uint64_t len = t ? n_isomir : n_canon;
+    for (uint64_t e = 0; e < len; ++e)
+      if (tab[e] < -1 || (tab[e] >= 0 && (uint64_t)tab[e] >= n_targets))
+        return fail(MRG_ERR_ARG, "%s: entry %llu of the %s table names target %d of %llu", fn, (unsigned long long)e,
+                    t ? "isomiR" : "canonical", tab[e], (unsigned long long)n_targets);
+  }
+  for (uint64_t t = 0; t < n_targets; ++t) {
+    if (target_lens[t] > 32) return fail(MRG_ERR_ARG, "%s: target %llu has %u bases (at most 32)", fn, (unsigned long long)t, target_lens[t]);
+    if (target_lens[t] < 32 && (target_words[t] >> (2 * target_lens[t])) != 0)
+      return fail(MRG_ERR_ARG, "%s: target %llu holds bits beyond its length", fn, (unsigned long long)t);
+  }
+  return MRG_OK;
+}
+
 int mrg_a2i_align(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
                   const uint64_t* d_nmask, uint64_t n, const int8_t* d_pass_id, const int32_t* d_ref_id, const uint8_t* d_keep,
                   int32_t canon_pass, int32_t isomir_pass, const int32_t* canon_target, uint64_t n_canon,
@@ -3883,20 +3902,8 @@ int mrg_a2i_align(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read
   if (from_base > 3 || to_base > 3) return fail(MRG_ERR_ARG, "mrg_a2i_align: from_base / to_base are codes 0..3");
   if (n_canon >= (1ull << 31) || n_isomir >= (1ull << 31) || n_targets >= (1ull << 31))
     return fail(MRG_ERR_ARG, "mrg_a2i_align: tables too large");
-  // the kernel trusts the tables: every target id is -1 or a target, every target has at most 32 bases
-  for (int t = 0; t < 2; ++t) {
-    const int32_t* tab = t ? isomir_target : canon_target;
-    const uint64_t len = t ? n_isomir : n_canon;
-    for (uint64_t e = 0; e < len; ++e)
-      if (tab[e] < -1 || (tab[e] >= 0 && (uint64_t)tab[e] >= n_targets))
-        return fail(MRG_ERR_ARG, "mrg_a2i_align: entry %llu of the %s table names target %d of %llu", (unsigned long long)e,
-                    t ? "isomiR" : "canonical", tab[e], (unsigned long long)n_targets);
-  }
-  for (uint64_t t = 0; t < n_targets; ++t) {
-    if (target_lens[t] > 32) return fail(MRG_ERR_ARG, "mrg_a2i_align: target %llu has %u bases (at most 32)", (unsigned long long)t, target_lens[t]);
-    if (target_lens[t] < 32 && (target_words[t] >> (2 * target_lens[t])) != 0)
-      return fail(MRG_ERR_ARG, "mrg_a2i_align: target %llu holds bits beyond its length", (unsigned long long)t);
-  }
+  if (int rc = a2i_check_tables("mrg_a2i_align", canon_target, n_canon, isomir_target, n_isomir, target_words, target_lens, n_targets))
+    return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   counts[0] = 0;
@@ -3968,6 +3975,95 @@ int mrg_a2i_align(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
   HIP_TRY(e);
+  return MRG_OK;
+}
+
+int mrg_a2i_settle(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                   const uint64_t* d_nmask, uint64_t n, const int32_t* canon_target, uint64_t n_canon, const int32_t* isomir_target,
+                   uint64_t n_isomir, const uint64_t* target_words, const uint8_t* target_lens, uint64_t n_targets,
+                   uint32_t from_base, uint32_t to_base, uint64_t k, const uint32_t* d_idx, int32_t* d_rec, uint64_t* counts,
+                   float* kernel_ms, void* stream) {
+  if (!counts) return fail(MRG_ERR_ARG, "mrg_a2i_settle: null argument");
+  if (kernel_ms) *kernel_ms = 0.0f;
+  if (k && (!d_reads || !d_lens || !d_idx || !d_rec)) return fail(MRG_ERR_ARG, "mrg_a2i_settle: null buffers");
+  if ((n_canon && !canon_target) || (n_isomir && !isomir_target) || (n_targets && (!target_words || !target_lens)))
+    return fail(MRG_ERR_ARG, "mrg_a2i_settle: null tables");
+  if (((uintptr_t)d_rec & 15u) != 0) return fail(MRG_ERR_ARG, "mrg_a2i_settle: d_rec must be 16-byte aligned");
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "mrg_a2i_settle: words_per_read must be 1, 2, 4 or 8");
+  if (stride < n || n >= (1ull << 31) || k >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_a2i_settle: bad stride / n / k");
+  if (from_base > 3 || to_base > 3) return fail(MRG_ERR_ARG, "mrg_a2i_settle: from_base / to_base are codes 0..3");
+  if (n_canon >= (1ull << 31) || n_isomir >= (1ull << 31) || n_targets >= (1ull << 31))
+    return fail(MRG_ERR_ARG, "mrg_a2i_settle: tables too large");
+  if (int rc = a2i_check_tables("mrg_a2i_settle", canon_target, n_canon, isomir_target, n_isomir, target_words, target_lens, n_targets))
+    return rc;
+  // (the context last: what is wrong with the arguments is said on a machine without a device too)
+  if (!ctx) return fail(MRG_ERR_ARG, "mrg_a2i_settle: null context (the rows are settled on the device, there is no host route)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  counts[0] = counts[1] = 0;
+  if (k == 0 || n == 0 || n_targets == 0) return MRG_OK;
+  // context scratch: [target words | target lengths | rows settled | flags -> offsets (k + 1) | the rows of status 1 | scan scratch]
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  const uint64_t n_flags = k + 1;
+  const uint64_t o_tw = 0, o_tl = o_tw + up(n_targets * sizeof(uint64_t)), o_done = o_tl + up(n_targets),
+                 o_flags = o_done + up(sizeof(uint32_t)), o_sel = o_flags + up(n_flags * sizeof(uint32_t)),
+                 o_tmp = o_sel + up(k * sizeof(uint32_t)), need_bytes = o_tmp + up(mrg::prims::scan_temp_bytes(n_flags));
+  if (ctx->scratch_bytes < need_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(ctx->scratch);
+    ctx->scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->scratch, need_bytes));
+    ctx->scratch_bytes = need_bytes;
+  }
+  char* base = (char*)ctx->scratch;
+  uint32_t* flags = (uint32_t*)(base + o_flags);
+  HIP_TRY(mrg::a2i_tied_select_launch(d_rec, k, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n_flags, base + o_tmp, st));
+  uint32_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, flags + k, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  counts[0] = total;
+  if (total == 0) return MRG_OK;
+  HIP_TRY(mrg::a2i_tied_scatter_launch(d_rec, k, flags, (uint32_t*)(base + o_sel), st));
+  HIP_TRY(hipMemcpyAsync(base + o_tw, target_words, n_targets * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(base + o_tl, target_lens, n_targets, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(base + o_done, 0, sizeof(uint32_t), st));
+  mrg::A2iSettleParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.n_reads = n;
+  p.idx = d_idx;
+  p.rec = d_rec;
+  p.sel = (const uint32_t*)(base + o_sel);
+  p.n_sel = total;
+  p.target_words = (const uint64_t*)(base + o_tw);
+  p.target_lens = (const uint8_t*)(base + o_tl);
+  p.n_targets = (uint32_t)n_targets;
+  p.from_base = from_base;
+  p.to_base = to_base;
+  p.settled = (uint32_t*)(base + o_done);
+  // kernel_ms: a2i_settle_kernel alone, between two events on the stream
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipError_t e = hipSuccess;
+  if (kernel_ms) {
+    e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, st);
+  }
+  if (e == hipSuccess) e = mrg::a2i_settle_launch(p, st);
+  if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev1, st);
+  uint32_t done = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&done, base + o_done, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  // (the tables were copied from pageable host memory, which the caller may free on return)
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, ev0, ev1);
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  HIP_TRY(e);
+  counts[1] = done;
   return MRG_OK;
 }
 

@@ -597,14 +597,17 @@ class Engine:
                 int(counts[0]), int(counts[1]))
 
     def a2i_align(self, table, words, lens, nmask, pass_id, ref_id, keep=None, timings=None, from_base="A", to_base="G",
-                  canon_pass=CANON_PASS, isomir_pass=ISOMIR_PASS):
+                  canon_pass=CANON_PASS, isomir_pass=ISOMIR_PASS, settle=False):
         """The rows of the `-ai` report (mrg_a2i_align): the reads claimed by canon_pass or isomir_pass (and, where `keep`
         is given, with keep != 0), in array order, each aligned to the canonical sequence of its miRNA in `table`
         (a2i.target_table).  words [W, n] / lens / nmask (or None) / pass_id / ref_id / keep: the device tensors of a
         ReadSet and a CascadeResult, or host arrays (uploaded).  Returns host arrays (idx uint32 [k], rec int32 [k, 4]:
         status | verdict << 8 | substring << 9 | m << 16, the diagonal, the edit mask, the target id).  timings: a dict that
         receives `kernel_ms`, the time of the alignment kernel alone (device events inside the call), and `align_call_ms`,
-        the whole filling call.  The rows are counted by a first call and filled by a second."""
+        the whole filling call.  The rows are counted by a first call and filled by a second.
+        settle: before the download, mrg_a2i_settle walks the rows of status 1 (a tie between diagonals) on the device
+        and rewrites those it settles as status 5, filled as a row of status 0; timings then also receives
+        `settle_examined`, `settle_settled` and `settle_kernel_ms`."""
         torch = _torch()
         from .a2i import BASE_CODE
 
@@ -651,6 +654,18 @@ class Engine:
                 e1.synchronize()
                 timings["align_call_ms"] = e0.elapsed_time(e1)
                 timings["kernel_ms"] = float(kernel_ms.value)
+        if settle:
+            done = (C.c_uint64 * 2)()
+            settle_ms = C.c_float(0.0)
+            if k:
+                check(self._lib.mrg_a2i_settle(
+                    self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(), n,
+                    canon_t.ctypes.data, canon_t.shape[0], iso_t.ctypes.data, iso_t.shape[0], t_words.ctypes.data,
+                    t_lens.ctypes.data, t_lens.shape[0], BASE_CODE[from_base], BASE_CODE[to_base], k, idx.data_ptr(),
+                    rec.data_ptr(), done, None if timings is None else C.byref(settle_ms), self._stream_ptr()))
+            if timings is not None:
+                timings.update(settle_examined=int(done[0]), settle_settled=int(done[1]),
+                               settle_kernel_ms=float(settle_ms.value))
         return idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k]
 
     def trf_classify(self, et, words, lens, nmask, pass_id, mature_pass=2, trailer_pass=3, mature_lib="mature_trna",

@@ -15,9 +15,13 @@ Host clocks around each stage; `kernel_ms` is the alignment kernel alone between
 `align_call_ms` the whole filling call, `genome_s` the time inside the genome filters (both routes run them on the GPU),
 `host_blocks_s` the time a2i_editing takes on the `host_blocks` of `blocks` (miRNA, sample) blocks that hold a read the
 kernel did not settle, `detail_write_s` mrg_write_a2i_detail.
-The three files of the two routes are compared byte for byte.  Writes one JSON object to --json (default
-profiles/a2i_report_timing.json) and prints it; `passed` = equal files and the slowest run of (b) faster than the fastest
-run of (a).  Needs a GPU."""
+A third leg, --settle-runs runs of each, alternating: route (b) without and with `settle` (mrg_a2i_settle settles the
+tied pairs on the device before the download); per run also `settle_examined`, `settle_settled`, `settle_kernel_ms` and
+`tied_rows`.  `settle_leg` holds the runs, the median wall times and their ratio.
+The three files of all routes are compared byte for byte.  Writes one JSON object to --json (default
+profiles/a2i_report_timing.json) and prints it; `passed` = equal files, the slowest run of (b) faster than the fastest
+run of (a), and fewer host blocks with `settle` than without.  --record-runs (default --runs) runs route (a) fewer times
+than (b).  Needs a GPU."""
 import argparse
 import json
 import os
@@ -117,7 +121,7 @@ def record_route(w, genome, outdir, sample_list):
     return dict(read_subset_s=t1 - t0, genome_s=g.spent, report_s=t2 - t1 - g.spent, total_s=t2 - t0)
 
 
-def array_route(w, dev, eng, genome, outdir, sample_list):
+def array_route(w, dev, eng, genome, outdir, sample_list, settle=False):
     import torch
     from mirge_amd import a2i
     g = TimedGenome(genome)
@@ -127,16 +131,20 @@ def array_route(w, dev, eng, genome, outdir, sample_list):
     keep = a2i.keep_mask(w["quant"], w["pass_id"], w["log_dic"])
     t1 = time.time()
     timings = {}
-    idx, rec = eng.a2i_align(table, dev["words"], dev["lens"], dev["nmask"], dev["pass_id"], dev["ref_id"], keep, timings=timings)
+    idx, rec = eng.a2i_align(table, dev["words"], dev["lens"], dev["nmask"], dev["pass_id"], dev["ref_id"], keep, timings=timings,
+                             settle=settle)
     t2 = time.time()
     a2i.a_to_i_report_arrays(outdir, sample_list, w["log_dic"], w["words"], w["lens"], w["nmask"], w["quant"], w["pass_id"], idx, rec,
                              table, w["mir_dic"], w["name_seq"], w["removed"], g, timings=timings)
     t3 = time.time()
     status = rec[:, 0] & 0xFF
-    return dict(tables_s=t1 - t0, align_and_download_s=t2 - t1, align_call_ms=timings.get("align_call_ms"),
-                kernel_ms=timings.get("kernel_ms"), genome_s=g.spent, report_s=t3 - t2 - g.spent, total_s=t3 - t0, pairs=int(idx.size),
-                not_simple=int((status != 0).sum()), blocks=timings["blocks"], host_blocks=timings["host_blocks"],
-                host_blocks_s=timings["host_blocks_s"], detail_write_s=timings["detail_write_s"])
+    out = dict(tables_s=t1 - t0, align_and_download_s=t2 - t1, align_call_ms=timings.get("align_call_ms"),
+               kernel_ms=timings.get("kernel_ms"), genome_s=g.spent, report_s=t3 - t2 - g.spent, total_s=t3 - t0, pairs=int(idx.size),
+               not_simple=int(((status != 0) & (status != a2i.ST_TIED)).sum()), blocks=timings["blocks"],
+               host_blocks=timings["host_blocks"], host_blocks_s=timings["host_blocks_s"], detail_write_s=timings["detail_write_s"])
+    if settle:
+        out.update({key: timings[key] for key in ("settle_examined", "settle_settled", "settle_kernel_ms", "tied_rows")})
+    return out
 
 
 def main():
@@ -145,8 +153,12 @@ def main():
     ap.add_argument("--mirnas", type=int, default=2000)
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--record-runs", type=int, default=None)
+    ap.add_argument("--settle-runs", type=int, default=None)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "a2i_report_timing.json"))
     args = ap.parse_args()
+    record_runs = args.runs if args.record_runs is None else args.record_runs
+    settle_runs = args.runs if args.settle_runs is None else args.settle_runs
     import torch
     from mirge_amd import a2i
     from mirge_amd.engine import Engine
@@ -164,20 +176,33 @@ def main():
                mirnas=args.mirnas, samples=args.samples, record_route=[], array_route=[],
                command="python scripts/a2i_report_timing.py " + " ".join(sys.argv[1:]))
     with tempfile.TemporaryDirectory() as d:
-        a_dir, b_dir = os.path.join(d, "a"), os.path.join(d, "b")
+        a_dir, b_dir, c_dir = os.path.join(d, "a"), os.path.join(d, "b"), os.path.join(d, "c")
         os.mkdir(a_dir)
         os.mkdir(b_dir)
-        array_route(w, dev, eng, genome, b_dir, sample_list)    # warm-up: code objects
-        for run in range(args.runs):
-            r = record_route(w, genome, a_dir, sample_list)
-            out["record_route"].append(r)
-            print("run %d record route %.2f s" % (run, r["total_s"]), flush=True)
+        os.mkdir(c_dir)
+        array_route(w, dev, eng, genome, b_dir, sample_list, settle=True)    # warm-up: code objects
+        for run in range(max(args.runs, record_runs)):
+            if run < record_runs:
+                r = record_route(w, genome, a_dir, sample_list)
+                out["record_route"].append(r)
+                print("run %d record route %.2f s" % (run, r["total_s"]), flush=True)
+            if run >= args.runs:
+                continue
             r = array_route(w, dev, eng, genome, b_dir, sample_list)
             out["array_route"].append(r)
             print("run %d array route %.3f s" % (run, r["total_s"]), flush=True)
+        leg = dict(without=[], with_settle=[])
+        for run in range(settle_runs):
+            for key, flag, where in (("without", False, b_dir), ("with_settle", True, c_dir)):
+                r = array_route(w, dev, eng, genome, where, sample_list, settle=flag)
+                leg[key].append(r)
+                print("run %d array route %s settle %.3f s, %d host blocks" % (run, "with" if flag else "without", r["total_s"],
+                                                                               r["host_blocks"]), flush=True)
         same = True
         for fn in FILES:
-            same &= open(os.path.join(a_dir, fn), "rb").read() == open(os.path.join(b_dir, fn), "rb").read()
+            ref = open(os.path.join(b_dir, fn), "rb").read()
+            same &= (not out["record_route"] or open(os.path.join(a_dir, fn), "rb").read() == ref)
+            same &= (not settle_runs or open(os.path.join(c_dir, fn), "rb").read() == ref)
             out.setdefault("file_bytes", []).append(os.path.getsize(os.path.join(b_dir, fn)))
     old = [r["total_s"] for r in out["record_route"]]
     new = [r["total_s"] for r in out["array_route"]]
@@ -185,6 +210,13 @@ def main():
     out["record_fastest_s"], out["array_slowest_s"] = min(old), max(new)
     out["ratio_record_fastest_over_array_slowest"] = round(min(old) / max(new), 1)
     out["passed"] = bool(same and max(new) < min(old))
+    if settle_runs:
+        med = {key: float(np.median([r["total_s"] for r in runs])) for key, runs in leg.items()}
+        leg.update(median_without_s=med["without"], median_with_settle_s=med["with_settle"],
+                   ratio_without_over_with=round(med["without"] / med["with_settle"], 2),
+                   fewer_host_blocks=bool(leg["with_settle"][0]["host_blocks"] < leg["without"][0]["host_blocks"]))
+        out["settle_leg"] = leg
+        out["passed"] = bool(out["passed"] and leg["fewer_host_blocks"])
     text = json.dumps(out)
     with open(args.json, "w") as fh:
         fh.write(text + "\n")
