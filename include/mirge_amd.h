@@ -1060,6 +1060,74 @@ int mrg_write_trf_tables(const char *const *paths, const char *const *samples, u
                          uint64_t *rows);
 
 /*
+ * `annotate -trf`: the (sample, tRNA) blocks of tRFs.samples.tmp/ (W2C:802-874) from the arrays, without one Python object
+ * per read: from the rows of mrg_trf_classify to the row arrays mrg_trf_rho takes, and the two report files of every sample.
+ * mirge_amd/trf_samples.py holds the Python model (sample_trf_dic, sample_reports, load_data_new, Group, layout) whose
+ * results they reproduce exactly.
+ *
+ * An ITEM is a pair (tsv row r, sample s) with kind <= 2 and quant[read][s] > 0; its block is (s, name of the selected
+ * entry); it is a PRINTED ROW when start + length of the whole read <= the template's length (the others overhang: they
+ * count in the block's sums only).  Blocks of a sample go by read count sum descending, then name descending; the printed
+ * rows of a block by (count, start, read) descending, the read as a Python string.  A GROUP is a block with a printed row;
+ * the k-th group of a sample is paired with the name of the sample's k-th block (load_data_new skips empty blocks).
+ *
+ * mrg_trf_rp100k_text    HOST: float("%.3f" % round(x, 3)) of x = 100000.0 * count / denom (0.0 for denom == 0), the RP100K
+ *                        the density peaks see (load_data_new re-reads the report), computed in integers: x = m * 2^e, k =
+ *                        m * 1000 * 2^e rounded to nearest, ties to even; the value is k / 1000.0.  The same function runs
+ *                        on the device.
+ * mrg_trf_sample_groups  DEVICE arrays: the reads [W][stride] (W in {1, 2, 4, 8}), d_lens, d_nmask or NULL, d_quant
+ *                        [n][n_samples], d_rec [k][12] IN THE ORDER OF THE TSV.  HOST: denom[n_samples], entries int32
+ *                        [n_entries][4] (mirge_amd.trf.sample_tables: rank of the entry's name among the distinct names in
+ *                        Python string order, template length or -1, flags: bit 0 = "pre_" in name, bit 1 = "pre" in name,
+ *                        0), n_names.  The call uploads the tables and validates them first (MRG_ERR_ARG).
+ *                        Stages: flags of the printed rows, 64-bit atomic sums / printed counts / lowest entry per (sample,
+ *                        name) cell, exclusive prefix sum and scatter; the dense cell tables are downloaded and ordered into
+ *                        blocks ON THE HOST (n_samples x n_names cells, at most 2^22: MRG_ERR_ARG beyond; k x n_samples
+ *                        must stay below 2^31, so that a row number fits the int32 block table); the rank of every selected read in Python string order by stable radix
+ *                        sorts over 21-base chunks, last chunk first (3 bits per base: end 0, A 1, C 2, G 3, N 4, T 5), as
+ *                        many as the longest selected read needs; the printed rows by two stable sorts, (start, read
+ *                        rank) then (block, count); one lane per printed row writes the layout.
+ *                        counts (HOST uint64[8]) = items, blocks, groups, printed rows, max_len (the longest template
+ *                        among the groups, at least 1), 1 if a printed row holds an N, the first tsv row of an item whose
+ *                        entry has no template (0xFFFFFFFF: none), the longest selected read.  A call with cap_blocks = 0
+ *                        only counts (output pointers may be NULL).  A filling call needs cap_blocks >= blocks and
+ *                        cap_rows >= printed rows, and is MRG_ERR_ARG when an item has no template or max_len > 255.
+ *                        It writes, HOST: blocks int32 [B][6] = sample, representative entry, first and number of printed
+ *                        rows, group or -1, 0; block_sums uint64 [B]; off uint32 [G + 1] (row offsets of the groups);
+ *                        groups int32 [G][2] = its block, the block whose name it is paired with.  DEVICE, as mrg_trf_rho
+ *                        takes them with row stride cap_rows: d_codes / d_nmask_out [ceil(max_len / 32)][cap_rows] (the
+ *                        read shifted by `start` bases into the template frame, zeros elsewhere; d_nmask_out is written
+ *                        only when counts[5] is set), d_span = (start + 1) | (start + length) << 8, d_rpm = the text value
+ *                        above, d_rows uint32 [rows][3] = tsv row, count, type.  kernel_ms (HOST float[4], or NULL): items,
+ *                        read order, row order, pack, between events.  Synchronises `stream`.
+ * mrg_trf_rank           d_rank[off[g] + p] = the group-local row at position p of the stable sort of -rho within group g:
+ *                        one radix sort of (group << 32 | ~bits of rho) over all rows (rho >= 0: the bit pattern is
+ *                        monotone).  What mrg_trf_delta takes as d_rank.  off on the HOST.  Synchronises `stream`.
+ * mrg_write_trf_sample_reports  HOST arrays: the reads, quant, rec and the tables as above, per entry its name, template and
+ *                        aaType (NULL where a table lacks it; needed for representative entries only), the blocks, their
+ *                        sums and the printed rows of mrg_trf_sample_groups.  paths[2 s] = <sample>.potential_tRFs.report,
+ *                        paths[2 s + 1] = <sample>.potential_tRFs.summary.report.  A block's RP100K sum is added over the
+ *                        tsv rows in order, overhanging items included; the summary in print order, from the exact RP100K.
+ *                        Tables that contradict each other are MRG_ERR_ARG.  Runs of blocks are formatted by worker threads
+ *                        (MIRGE_AMD_TABLE_THREADS; MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS = lines per run, default 16384, lowered
+ *                        by tests); the bytes depend on neither setting.
+ */
+double mrg_trf_rp100k_text(uint64_t count, uint64_t denom);
+int mrg_trf_sample_groups(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                          const uint64_t *d_nmask, uint64_t n, const uint32_t *d_quant, uint32_t n_samples, const int32_t *d_rec,
+                          uint64_t k, const uint64_t *denom, const int32_t *entries, uint64_t n_entries, uint32_t n_names,
+                          uint64_t cap_blocks, uint64_t cap_rows, int32_t *blocks, uint64_t *block_sums, uint32_t *off,
+                          int32_t *groups, uint64_t *d_codes, uint64_t *d_nmask_out, uint16_t *d_span, double *d_rpm,
+                          uint32_t *d_rows, uint64_t *counts, float *kernel_ms, void *stream);
+int mrg_trf_rank(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, const float *d_rho, uint32_t *d_rank, void *stream);
+int mrg_write_trf_sample_reports(const char *const *paths, uint32_t n_samples, const uint64_t *denom, const uint64_t *reads,
+                                 uint32_t words_per_read, uint64_t stride, const uint8_t *lens, const uint64_t *nmask, uint64_t n,
+                                 const uint32_t *quant, const int32_t *rec, uint64_t k, const int32_t *entries,
+                                 const char *const *entry_names, const char *const *templates, const char *const *aa_types,
+                                 uint64_t n_entries, uint32_t n_names, const int32_t *blocks, const uint64_t *block_sums,
+                                 uint64_t n_blocks, const uint32_t *rows, uint64_t n_rows);
+
+/*
  * `annotate -ai`: every read claimed by the exact-miRNA or the isomiR pass aligned to the canonical sequence of its (merged)
  * miRNA, and a2IEditing.detail.txt, from the arrays.  mirge_amd/a2i.py holds the Python model (local_pair, judge_align,
  * a2i_editing) whose results the two calls reproduce exactly; DESIGN.md 8.6 holds the argument.

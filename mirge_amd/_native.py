@@ -250,6 +250,18 @@ SIGNATURES = {
                                        C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_uint64,
                                        C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mrg_trf_rp100k_text": (C.c_double, [C.c_uint64, C.c_uint64]),
+    "mrg_trf_sample_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_float), C.c_void_p]),
+    "mrg_trf_rank": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mrg_write_trf_sample_reports": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                               C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                               C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_uint64, C.c_void_p, C.c_uint64]),
     "mrg_pack_reads": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "mrg_trf_rho": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -510,8 +510,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
             trf.collect_trf_content(trf_content, sub, sample_list, trf_tables["trnaStruDic"], pre_seqs,
                                     trf.engine_lister(engine))
             trf.write_trf_tables(outdir, sample_list, log_dic, trf_content, trf_tables, pre_seqs)
-        else:   # from the arrays
-            from . import pack
+        from . import trf_samples   # W2C:802-1088: tRFs.samples.tmp/, density peaks on the GPU
+        if not trf_records:   # from the arrays
             et = trf.entry_tables(npp[2], npp[3], trf_tables, pre_seqs)
             if world > 1:   # (the gathered host arrays)
                 rows = engine.trf_classify(et, h_words, h_lens, h_nmask, h_pass)
@@ -519,14 +519,16 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 rows = engine.trf_classify(et, shard.words, shard.lens, shard.nmask, res.pass_id)
             t_rec, _ = columnar.write_trf_tables(outdir, sample_list, log_dic, h_words, h_lens, h_nmask, h_quant, rows[0],
                                                  rows[1], rows[2], et)
-            t_idx = t_rec[:, 0]
-            t_seqs = pack.unpack_reads(np.ascontiguousarray(h_words[:, t_idx]), h_lens[t_idx],
-                                       None if h_nmask is None else np.ascontiguousarray(h_nmask[:, t_idx]))
-            trf_content.update(trf.content_from_rows(
-                et, t_rec, t_seqs, h_quant[t_idx], [q["maturetrnaReads"] + q["pretrnaReads"] for q in log_dic["quantStats"]]))
-        from . import trf_samples   # W2C:802-1088: tRFs.samples.tmp/, density peaks on the GPU
-        trf_samples.write_trf_samples(outdir, sample_list, trf_content, trf_tables, pre_seqs,
-                                      trf_samples.engine_peaks(engine))
+            # the blocks, their rows' layout and the two report files from the arrays (Engine.trf_sample_groups,
+            # mrg_write_trf_sample_reports); with --gpus N rank 0 passes the gathered host arrays
+            on_device = None if world > 1 or shard.quant is None else (shard.words, shard.lens, shard.nmask, shard.quant)
+            trf_samples.write_trf_samples_arrays(
+                outdir, sample_list, et, trf.sample_tables(et, trf_tables, pre_seqs), t_rec, h_words, h_lens, h_nmask, h_quant,
+                [q["maturetrnaReads"] + q["pretrnaReads"] for q in log_dic["quantStats"]][:S], trf_tables, pre_seqs,
+                trf_samples.engine_groups(engine, on_device), trf_samples.engine_peaks_groups(engine), device_rank=True)
+        else:
+            trf_samples.write_trf_samples(outdir, sample_list, trf_content, trf_tables, pre_seqs,
+                                          trf_samples.engine_peaks(engine))
     if args.diff_isomirs and not long_mirna:
         columnar.write_isomir_tables(os.path.join(outdir, "isomirs.csv"), os.path.join(outdir, "isomirs.samples.csv"), sample_list,
                                      h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, npp[CANON_PASS], log_dic)

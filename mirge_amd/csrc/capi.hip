@@ -29,6 +29,7 @@
 #include "prims.hpp"
 #include "sa_build.hpp"
 #include "tables.hpp"
+#include "trf_groups.hpp"
 #include "trf_peaks.hpp"
 #include "trf_tables.hpp"
 
@@ -3858,6 +3859,283 @@ int mrg_write_trf_tables(const char* const* paths, const char* const* samples, u
     return fail(MRG_ERR_ARG, "mrg_write_trf_tables: %s", e.what());
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "mrg_write_trf_tables: %s", e.what());
+  }
+}
+
+// ------------------------------------------------------------- -trf: the per-sample blocks (csrc/trf_groups.hip)
+double mrg_trf_rp100k_text(uint64_t count, uint64_t denom) { return mrg::trf_rp100k_text(count, denom); }
+
+int mrg_trf_sample_groups(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                          const uint64_t* d_nmask, uint64_t n, const uint32_t* d_quant, uint32_t n_samples, const int32_t* d_rec,
+                          uint64_t k, const uint64_t* denom, const int32_t* entries, uint64_t n_entries, uint32_t n_names,
+                          uint64_t cap_blocks, uint64_t cap_rows, int32_t* blocks, uint64_t* block_sums, uint32_t* off, int32_t* groups,
+                          uint64_t* d_codes, uint64_t* d_nmask_out, uint16_t* d_span, double* d_rpm, uint32_t* d_rows, uint64_t* counts,
+                          float* kernel_ms, void* stream) {
+  const char* fn = "mrg_trf_sample_groups";
+  if (!ctx || !counts || !denom || !n_samples) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0.0f;
+  if (k && (!d_reads || !d_lens || !d_quant || !d_rec)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_entries && !entries) return fail(MRG_ERR_ARG, "%s: null tables", fn);
+  if (cap_blocks && (!blocks || !block_sums || !off || !groups)) return fail(MRG_ERR_ARG, "%s: null output buffers", fn);
+  if (cap_rows && (!d_codes || !d_span || !d_rpm || !d_rows)) return fail(MRG_ERR_ARG, "%s: null output buffers", fn);
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "%s: words_per_read must be 1, 2, 4 or 8", fn);
+  if (stride < n || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: bad stride / n", fn);
+  // (a printed row's number is an int32 of the block table, and every (row, sample) pair may be one)
+  if (n_samples > (1u << 16) || k * n_samples >= (1ull << 31))
+    return fail(MRG_ERR_ARG, "%s: rows x samples must stay below 2^31 (split the samples)", fn);
+  // (the cells are ordered into blocks on the host: a table for tRNA names, not for reads)
+  if (n_entries >= (1ull << 30) || (uint64_t)n_names * n_samples > (1ull << 22))
+    return fail(MRG_ERR_ARG, "%s: too many entries, or more than 2^22 (sample, name) cells", fn);
+  // the kernels trust the entry table: a name id is a name, a template is -1 or a length
+  for (uint64_t e = 0; e < n_entries; ++e) {
+    const int32_t* d = entries + e * mrg::kTrfSampleInts;
+    if (d[mrg::kTrfSampleName] < 0 || (uint32_t)d[mrg::kTrfSampleName] >= n_names || d[mrg::kTrfSampleTemplate] < -1)
+      return fail(MRG_ERR_ARG, "%s: entry %llu: name id or template length out of range", fn, (unsigned long long)e);
+  }
+  for (int i = 0; i < 8; ++i) counts[i] = 0;
+  counts[6] = mrg::kTrfNone;
+  if (cap_blocks) off[0] = 0;
+  if (k == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t S = n_samples, K = (uint32_t)k;
+  const uint64_t total = (uint64_t)S * K, cells = (uint64_t)S * n_names;
+
+  // ---- items: flags of the printed rows, the dense [S][names] sums
+  TrfBuf ib;
+  const uint64_t o_flags = ib.reserve((total + 1) * sizeof(uint32_t)), o_scan = ib.reserve(mrg::prims::scan_temp_bytes(total + 1)),
+                 o_sums = ib.reserve(cells * sizeof(uint64_t)), o_np = ib.reserve(cells * sizeof(uint32_t)),
+                 o_rep = ib.reserve(cells * sizeof(int32_t)), o_stat = ib.reserve(mrg::kTrfStatWords * sizeof(uint32_t)),
+                 o_ent = ib.reserve(n_entries * mrg::kTrfSampleInts * sizeof(int32_t)), o_den = ib.reserve(S * sizeof(uint64_t)),
+                 o_cb = ib.reserve(cells * sizeof(uint32_t));
+  HIP_TRY(ib.alloc());
+  uint32_t* flags = ib.at<uint32_t>(o_flags);
+  uint32_t stat[mrg::kTrfStatWords] = {mrg::kTrfNone, mrg::kTrfNone, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(ib.p + o_stat, stat, sizeof stat, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ib.p + o_ent, entries, n_entries * mrg::kTrfSampleInts * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ib.p + o_den, denom, S * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(ib.p + o_sums, 0, cells * sizeof(uint64_t), st));
+  HIP_TRY(hipMemsetAsync(ib.p + o_np, 0, cells * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(ib.p + o_rep, 0x7F, cells * sizeof(int32_t), st));  // (0x7F7F7F7F: above every entry)
+  HIP_TRY(hipMemsetAsync(flags + total, 0, sizeof(uint32_t), st));
+  mrg::TrfGroupParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.stride = stride;
+  p.n = n;
+  p.W = words_per_read;
+  p.quant = d_quant;
+  p.S = S;
+  p.rec = d_rec;
+  p.k = K;
+  p.entries = ib.at<int32_t>(o_ent);
+  p.n_entries = (uint32_t)n_entries;
+  p.n_names = n_names;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EventGuard {
+    hipEvent_t* ev;
+    ~EventGuard() {
+      for (int i = 0; i < 5; ++i)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+  } guard{ev};
+  if (kernel_ms)
+    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev[0], st));
+  HIP_TRY(mrg::trf_items_launch(p, flags, ib.at<uint64_t>(o_sums), ib.at<uint32_t>(o_np), ib.at<int32_t>(o_rep), ib.at<uint32_t>(o_stat), st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, total + 1, ib.p + o_scan, st));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev[1], st));
+  std::vector<uint64_t> h_sums(cells);
+  std::vector<uint32_t> h_np(cells);
+  std::vector<int32_t> h_rep(cells);
+  uint32_t n_rows = 0;
+  HIP_TRY(hipMemcpyAsync(stat, ib.p + o_stat, sizeof stat, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&n_rows, flags + total, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (cells) {
+    HIP_TRY(hipMemcpyAsync(h_sums.data(), ib.p + o_sums, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_np.data(), ib.p + o_np, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_rep.data(), ib.p + o_rep, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  if (stat[mrg::kTrfStatBadRow] != mrg::kTrfNone)
+    return fail(MRG_ERR_ARG, "%s: row %u: read, entry or start out of range", fn, stat[mrg::kTrfStatBadRow]);
+
+  // ---- blocks, on the host (S x names cells): per sample by read_sum descending, then name descending; a group is a block
+  // with a printed row, and the k-th group of a sample is paired with the name of the sample's k-th block
+  struct Blk {
+    uint32_t s, name, printed;
+    int32_t rep;
+    uint64_t sum;
+  };
+  std::vector<Blk> blk;
+  for (uint32_t s = 0; s < S; ++s) {
+    const size_t first = blk.size();
+    for (uint32_t name = 0; name < n_names; ++name) {
+      const uint64_t c = (uint64_t)s * n_names + name;
+      if (h_rep[c] != 0x7F7F7F7F) blk.push_back(Blk{s, name, h_np[c], h_rep[c], h_sums[c]});
+    }
+    std::sort(blk.begin() + first, blk.end(), [](const Blk& a, const Blk& b) { return a.sum != b.sum ? a.sum > b.sum : a.name > b.name; });
+  }
+  const uint64_t B = blk.size();
+  uint64_t G = 0, max_len = 0;
+  for (const Blk& b : blk)
+    if (b.printed) {
+      ++G;
+      max_len = std::max<uint64_t>(max_len, (uint64_t)std::max(entries[(uint64_t)b.rep * mrg::kTrfSampleInts + mrg::kTrfSampleTemplate], 0));
+    }
+  counts[0] = stat[mrg::kTrfStatItems];
+  counts[1] = B;
+  counts[2] = G;
+  counts[3] = n_rows;
+  counts[4] = G ? max_len : 1;   // (trf_samples.layout: max over the groups and 1)
+  counts[5] = stat[mrg::kTrfStatHasN];
+  counts[6] = stat[mrg::kTrfStatNoTemplate];
+  counts[7] = stat[mrg::kTrfStatMaxLen];
+  if (cap_blocks == 0) return MRG_OK;
+  if (cap_blocks < B || cap_rows < n_rows)
+    return fail(MRG_ERR_ARG, "%s: %llu blocks and %llu rows do not fit the buffers (count first)", fn, (unsigned long long)B,
+                (unsigned long long)n_rows);
+  if (stat[mrg::kTrfStatNoTemplate] != mrg::kTrfNone)
+    return fail(MRG_ERR_ARG, "%s: row %u: the selected tRNA has no template", fn, stat[mrg::kTrfStatNoTemplate]);
+  if (max_len > mrg::kTrfMaxTemplate)
+    return fail(MRG_ERR_ARG, "%s: a template of %llu nt: density peaks take templates of at most %u nt", fn,
+                (unsigned long long)max_len, mrg::kTrfMaxTemplate);
+  if (counts[5] && !d_nmask_out) return fail(MRG_ERR_ARG, "%s: null output buffers", fn);
+  std::vector<uint32_t> cell_block(cells, 0);
+  {
+    uint64_t g = 0, row = 0, b0 = 0, g_in_sample = 0;
+    for (uint64_t b = 0; b < B; ++b) {
+      if (b == 0 || blk[b].s != blk[b - 1].s) {
+        b0 = b;
+        g_in_sample = 0;
+      }
+      cell_block[(uint64_t)blk[b].s * n_names + blk[b].name] = (uint32_t)b;
+      int32_t* o = blocks + b * 6;
+      o[0] = (int32_t)blk[b].s;
+      o[1] = blk[b].rep;
+      o[2] = (int32_t)row;
+      o[3] = (int32_t)blk[b].printed;
+      o[4] = blk[b].printed ? (int32_t)g : -1;
+      o[5] = 0;
+      block_sums[b] = blk[b].sum;
+      if (blk[b].printed) {
+        groups[2 * g] = (int32_t)b;
+        groups[2 * g + 1] = (int32_t)(b0 + g_in_sample);
+        row += blk[b].printed;
+        off[++g] = (uint32_t)row;
+        ++g_in_sample;
+      }
+    }
+    if (row != n_rows) return fail(MRG_ERR_HIP, "%s: the blocks hold %llu printed rows, the flags %u", fn, (unsigned long long)row, n_rows);
+  }
+  if (n_rows == 0) return MRG_OK;
+  HIP_TRY(hipMemcpyAsync(ib.p + o_cb, cell_block.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+
+  // ---- the reads in Python string order: stable sorts of the rows by 21-base chunks, the last chunk first
+  const uint32_t chunks = (stat[mrg::kTrfStatMaxLen] + 20) / 21, rank_bits = bits_for(K), block_bits = bits_for(B);
+  if (8 + rank_bits > 64 || 32 + block_bits > 64) return fail(MRG_ERR_ARG, "%s: the sort keys do not fit 64 bits", fn);
+  const uint64_t m = std::max<uint64_t>(K, n_rows);
+  TrfBuf sb;
+  const uint64_t o_k0 = sb.reserve(m * sizeof(uint64_t)), o_k1 = sb.reserve(m * sizeof(uint64_t)), o_v0 = sb.reserve(m * sizeof(uint32_t)),
+                 o_v1 = sb.reserve(m * sizeof(uint32_t)), o_rank = sb.reserve((uint64_t)K * sizeof(uint32_t)),
+                 o_item = sb.reserve((uint64_t)n_rows * sizeof(uint32_t)), o_tmp = sb.reserve(mrg::prims::radix_temp_bytes(m));
+  HIP_TRY(sb.alloc());
+  uint64_t* keys[2] = {sb.at<uint64_t>(o_k0), sb.at<uint64_t>(o_k1)};
+  uint32_t* vals[2] = {sb.at<uint32_t>(o_v0), sb.at<uint32_t>(o_v1)};
+  uint32_t *rank = sb.at<uint32_t>(o_rank), *item = sb.at<uint32_t>(o_item);
+  HIP_TRY(mrg::trf_item_scatter_launch(flags, total, item, st));
+  int cur = 0;
+  auto sort = [&](uint32_t count, uint32_t bits) -> hipError_t {  // keys[cur], vals[cur] -> keys[cur], vals[cur] of the new cur
+    bool second = false;
+    const hipError_t e = mrg::prims::radix_sort_pairs_u64(keys[cur], keys[cur ^ 1], vals[cur], vals[cur ^ 1], count, bits, sb.p + o_tmp, st, &second);
+    if (second) cur ^= 1;
+    return e;
+  };
+  HIP_TRY(mrg::trf_iota_launch(vals[cur], K, st));
+  for (uint32_t c = chunks; c-- > 0;) {
+    HIP_TRY(mrg::trf_chunk_keys_launch(p, vals[cur], c, keys[cur], st));
+    HIP_TRY(sort(K, 63));
+  }
+  HIP_TRY(mrg::trf_rank_scatter_launch(vals[cur], K, rank, st));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev[2], st));
+
+  // ---- the printed rows by (block, count descending, start descending, read descending): two stable passes
+  HIP_TRY(mrg::trf_order_keys_a_launch(p, item, n_rows, rank, rank_bits, keys[cur], vals[cur], st));
+  HIP_TRY(sort(n_rows, 8 + rank_bits));
+  HIP_TRY(mrg::trf_order_keys_b_launch(p, item, vals[cur], n_rows, ib.at<uint32_t>(o_cb), keys[cur], st));
+  HIP_TRY(sort(n_rows, 32 + block_bits));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev[3], st));
+
+  // ---- pack
+  mrg::TrfPackOut out;
+  out.words = (uint32_t)((counts[4] + 31) / 32);
+  out.row_stride = cap_rows;
+  out.codes = d_codes;
+  out.nmask = counts[5] ? d_nmask_out : nullptr;
+  out.span = d_span;
+  out.rpm = d_rpm;
+  out.row = d_rows;
+  HIP_TRY(mrg::trf_pack_launch(p, item, vals[cur], n_rows, ib.at<uint64_t>(o_den), out, st));
+  if (kernel_ms) HIP_TRY(hipEventRecord(ev[4], st));
+  // (the tables were copied from pageable host memory, and the buffers above are freed on return)
+  HIP_TRY(hipStreamSynchronize(st));
+  if (kernel_ms)
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]));
+  return MRG_OK;
+}
+
+int mrg_trf_rank(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, const float* d_rho, uint32_t* d_rank, void* stream) {
+  if (!ctx || !off || !n_groups) return fail(MRG_ERR_ARG, "mrg_trf_rank: null argument");
+  if (n_groups > (1u << 24) || off[0] != 0) return fail(MRG_ERR_ARG, "mrg_trf_rank: 1..2^24 groups, off[0] = 0");
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (off[g + 1] < off[g]) return fail(MRG_ERR_ARG, "mrg_trf_rank: offsets decrease at group %u", g);
+  const uint32_t n = off[n_groups];
+  if (n && (!d_rho || !d_rank)) return fail(MRG_ERR_ARG, "mrg_trf_rank: null row buffers");
+  if (n == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  TrfBuf b;
+  const uint64_t o_off = b.reserve((n_groups + 1ull) * sizeof(uint32_t)), o_k0 = b.reserve((uint64_t)n * sizeof(uint64_t)),
+                 o_k1 = b.reserve((uint64_t)n * sizeof(uint64_t)), o_v0 = b.reserve((uint64_t)n * sizeof(uint32_t)),
+                 o_v1 = b.reserve((uint64_t)n * sizeof(uint32_t)), o_tmp = b.reserve(mrg::prims::radix_temp_bytes(n));
+  HIP_TRY(b.alloc());
+  HIP_TRY(hipMemcpyAsync(b.p + o_off, off, (n_groups + 1ull) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(mrg::trf_rank_keys_launch(b.at<uint32_t>(o_off), n_groups, d_rho, n, b.at<uint64_t>(o_k0), b.at<uint32_t>(o_v0), st));
+  bool second = false;
+  HIP_TRY(mrg::prims::radix_sort_pairs_u64(b.at<uint64_t>(o_k0), b.at<uint64_t>(o_k1), b.at<uint32_t>(o_v0), b.at<uint32_t>(o_v1), n,
+                                           32 + bits_for(n_groups), b.p + o_tmp, st, &second));
+  HIP_TRY(mrg::trf_rank_local_launch(b.at<uint32_t>(o_off), b.at<uint64_t>(second ? o_k1 : o_k0), b.at<uint32_t>(second ? o_v1 : o_v0), n,
+                                     d_rank, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+int mrg_write_trf_sample_reports(const char* const* paths, uint32_t n_samples, const uint64_t* denom, const uint64_t* reads,
+                                 uint32_t words_per_read, uint64_t stride, const uint8_t* lens, const uint64_t* nmask, uint64_t n,
+                                 const uint32_t* quant, const int32_t* rec, uint64_t k, const int32_t* entries,
+                                 const char* const* entry_names, const char* const* templates, const char* const* aa_types,
+                                 uint64_t n_entries, uint32_t n_names, const int32_t* blocks, const uint64_t* block_sums,
+                                 uint64_t n_blocks, const uint32_t* rows, uint64_t n_rows) {
+  const char* fn = "mrg_write_trf_sample_reports";
+  if (!paths || !denom || !n_samples) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  for (uint32_t s = 0; s < 2 * n_samples; ++s)
+    if (!paths[s]) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (k && (!reads || !lens || !quant || !rec)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if ((n_entries && (!entries || !entry_names || !templates || !aa_types)) || (n_blocks && (!blocks || !block_sums)) || (n_rows && !rows))
+    return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
+  try {
+    const mrg::TrfSampleWriteArgs a{paths, n_samples, denom, reads, words_per_read, stride, lens, nmask, n, quant, rec, k, entries,
+                                    entry_names, templates, aa_types, n_entries, n_names, blocks, block_sums, n_blocks, rows, n_rows};
+    mrg::write_trf_sample_reports(a);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
   }
 }
 

@@ -731,6 +731,83 @@ class Engine:
                 cap = h
         return rec.cpu().numpy()[:k], hits.cpu().numpy()[:h], n2, n3
 
+    def trf_sample_groups(self, st, rec, words, lens, nmask, quant, denom, timings=None):
+        """The (sample, tRNA) blocks of tRFs.samples.tmp/ (mrg_trf_sample_groups) from the rows of trf_classify IN THE ORDER
+        OF THE TSV (columnar.write_trf_tables returns them), `st` = trf.sample_tables, denom[s] = maturetrnaReads +
+        pretrnaReads.  rec / words [W, n] / lens / nmask (or None) / quant [n, S]: device tensors or host arrays (uploaded).
+        Returns a TrfGroups: the downloaded tables and the device tensors mrg_trf_rho takes.  When an item's entry has no
+        template (.no_template_row) or a template exceeds 255 nt (.max_len), only the counts are filled: the caller raises.
+        timings: a dict that receives `groups_count_ms` / `groups_fill_ms` (events around the two calls) and
+        `items_kernel_ms`, `read_order_kernel_ms`, `row_order_kernel_ms`, `pack_kernel_ms` (events inside the filling call)."""
+        torch = _torch()
+
+        def dev(x, np_dtype, view=None):
+            if x is None or torch.is_tensor(x):
+                return x
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+        words = dev(words, np.uint64, np.int64).contiguous()
+        nmask = dev(nmask, np.uint64, np.int64)
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        lens = dev(lens, np.uint8).contiguous()
+        quant = dev(quant, np.uint32, np.int32).contiguous()
+        rec = dev(np.asarray(rec).reshape(-1, 12) if not torch.is_tensor(rec) else rec, np.int32).contiguous()
+        W, n = int(words.shape[0]), int(words.shape[1])
+        S = int(quant.shape[1]) if quant.dim() == 2 else 1
+        k = int(rec.shape[0])
+        denom = np.ascontiguousarray(denom, dtype=np.uint64)
+        if denom.shape[0] != S or int(quant.shape[0]) != n or int(lens.shape[0]) != n:
+            raise ValueError("trf_sample_groups: quant [n, S], lens [n] and denom [S] must match the reads")
+        entries = np.ascontiguousarray(st.entries, dtype=np.int32)
+        counts = (C.c_uint64 * 8)()
+        kernel_ms = (C.c_float * 4)()
+
+        def call(cap_blocks, cap_rows, host, devs):
+            ptr = lambda t: None if t is None else t.data_ptr()
+            check(self._lib.mrg_trf_sample_groups(
+                self._h, words.data_ptr(), W, n, lens.data_ptr(), ptr(nmask), n, quant.data_ptr(), S, rec.data_ptr(), k,
+                denom.ctypes.data, entries.ctypes.data, entries.shape[0], int(st.n_names), cap_blocks, cap_rows,
+                *[None if a is None else a.ctypes.data for a in host], *[ptr(t) for t in devs], counts,
+                None if timings is None else kernel_ms, self._stream_ptr()))
+
+        def timed(key, *a):
+            if timings is None:
+                return call(*a)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call(*a)
+            e1.record()
+            e1.synchronize()
+            timings[key] = e0.elapsed_time(e1)
+        timed("groups_count_ms", 0, 0, (None,) * 4, (None,) * 5)
+        g = TrfGroups()
+        g.n_items, B, G, R = (int(counts[i]) for i in range(4))
+        g.max_len, g.has_n = int(counts[4]), bool(counts[5])
+        g.no_template_row = None if int(counts[6]) == 0xFFFFFFFF else int(counts[6])
+        g.G, g.n = G, R
+        g.blocks, g.block_sums = np.zeros((B, 6), dtype=np.int32), np.zeros(B, dtype=np.uint64)
+        g.off, g.groups = np.zeros(G + 1, dtype=np.uint32), np.zeros((G, 2), dtype=np.int32)
+        g.filled = g.no_template_row is None and g.max_len <= 255
+        if not g.filled:
+            return g
+        Wt = (g.max_len + 31) // 32
+        g.codes_d = torch.zeros(Wt * max(R, 1), dtype=torch.int64, device=self.device)
+        g.nmask_d = torch.zeros(Wt * max(R, 1), dtype=torch.int64, device=self.device) if g.has_n else None
+        g.span_d = torch.zeros(max(R, 1), dtype=torch.int16, device=self.device)
+        g.rpm_d = torch.zeros(max(R, 1), dtype=torch.float64, device=self.device)
+        rows_d = torch.zeros((max(R, 1), 3), dtype=torch.int32, device=self.device)
+        if B:
+            timed("groups_fill_ms", B, R, (g.blocks, g.block_sums, g.off, g.groups),
+                  (g.codes_d, g.nmask_d, g.span_d, g.rpm_d, rows_d))
+            if (int(counts[1]), int(counts[2]), int(counts[3])) != (B, G, R):
+                raise RuntimeError("trf_sample_groups: the counting and the filling call disagree")
+            if timings is not None:
+                for key, v in zip(("items_kernel_ms", "read_order_kernel_ms", "row_order_kernel_ms", "pack_kernel_ms"), kernel_ms):
+                    timings[key] = float(v)
+        g.rows = rows_d.cpu().numpy()[:R].view(np.uint32)
+        return g
+
     def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
                    max_mm_total=2, timings=None):
         """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a
@@ -995,6 +1072,17 @@ class Engine:
         t.nmask = dev(np.asarray(nmask).reshape(-1), np.uint64) if nmask is not None and n else None
         t.span = dev(span if n else np.zeros(1), np.uint16)
         rpm_d = dev(rpm if n else np.zeros(1), np.float64)
+        return self._trf_rho(t, rpm_d, ktab)
+
+    def trf_peaks_groups(self, groups, ktab):
+        """Engine.trf_peaks on the device tensors of a TrfGroups (Engine.trf_sample_groups): no host layout, no upload."""
+        t = TrfPeaks(self, np.ascontiguousarray(groups.off, dtype=np.uint32), groups.max_len)
+        t.codes, t.nmask, t.span = groups.codes_d, groups.nmask_d, groups.span_d
+        return self._trf_rho(t, groups.rpm_d, ktab)
+
+    def _trf_rho(self, t, rpm_d, ktab):
+        torch = _torch()
+        G, n, max_len = t.G, t.n, t.max_len
         kt = np.ascontiguousarray(ktab, dtype=np.float64)
         rho = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
         t.max_dis_d = torch.empty(max(G, 1), dtype=torch.int32, device=self.device)
@@ -1047,8 +1135,39 @@ class Engine:
 PACKED_REF_SAT, PACKED_POS_SAT = 0x3FFFF, 0xFF
 
 
+class TrfGroups:
+    """Result of Engine.trf_sample_groups.  Host: n_items, blocks int32 [B, 6] (sample, representative entry, first and
+    number of printed rows, group or -1, 0), block_sums uint64 [B], off uint32 [G + 1], groups int32 [G, 2] (its block, the
+    block whose name it is paired with), rows uint32 [n, 3] (tsv row, count, type), max_len, has_n, no_template_row.
+    Device: codes_d / nmask_d (None without N) [W][n], span_d, rpm_d; .codes / .nmask / .span / .rpm download them."""
+    codes_d = nmask_d = span_d = rpm_d = None
+    rows = np.zeros((0, 3), dtype=np.uint32)
+
+    def _host(self, t, view, shape):
+        return t.cpu().numpy().view(view).reshape(shape)
+
+    @property
+    def codes(self):
+        W = (self.max_len + 31) // 32
+        return self._host(self.codes_d, np.uint64, (W, -1))[:, :self.n]
+
+    @property
+    def nmask(self):
+        W = (self.max_len + 31) // 32
+        return None if self.nmask_d is None else self._host(self.nmask_d, np.uint64, (W, -1))[:, :self.n]
+
+    @property
+    def span(self):
+        return self._host(self.span_d, np.uint16, (-1,))[:self.n]
+
+    @property
+    def rpm(self):
+        return self._host(self.rpm_d, np.float64, (-1,))[:self.n]
+
+
 class TrfPeaks:
     """Device state of one Engine.trf_peaks batch (see there)."""
+    rank_d = None
 
     def __init__(self, engine, off, max_len):
         self.engine, self.off, self.max_len = engine, off, int(max_len)
@@ -1058,14 +1177,29 @@ class TrfPeaks:
     def nmask_ptr(self):
         return self.nmask.data_ptr() if self.nmask is not None else None
 
-    def min_distance(self, rank):
-        """min_distance (W2C:509-533): rank = each group's rows (group-local) in rank order, flat like the rows.
-        Returns (delta, nneigh) int32[n]: distance to / group-local row of the nearest row ranked above, -1 for
-        the top row of a group."""
+    def rank(self):
+        """Each group's rows (group-local) in rank order -- the stable sort of -rho -- flat like the rows (mrg_trf_rank).
+        Stays on the device for min_distance(None); returned as uint32[n]."""
         torch = _torch()
         e = self.engine
-        rank_d = torch.from_numpy(np.ascontiguousarray(rank if self.n else np.zeros(1), dtype=np.uint32)
-                                  .view(np.int32)).to(e.device)
+        self.rank_d = torch.zeros(max(self.n, 1), dtype=torch.int32, device=e.device)
+        if self.G:
+            check(e._lib.mrg_trf_rank(e._h, self.off_c, self.G, self.rho_d.data_ptr(), self.rank_d.data_ptr(), e._stream_ptr()))
+        return self.rank_d.cpu().numpy()[:self.n].view(np.uint32)
+
+    def min_distance(self, rank=None):
+        """min_distance (W2C:509-533): rank = each group's rows (group-local) in rank order, flat like the rows (None:
+        what rank() left on the device).  Returns (delta, nneigh) int32[n]: distance to / group-local row of the nearest
+        row ranked above, -1 for the top row of a group."""
+        torch = _torch()
+        e = self.engine
+        if rank is None:
+            if self.rank_d is None:
+                raise ValueError("min_distance(None) needs rank() first")
+            rank_d = self.rank_d
+        else:
+            rank_d = torch.from_numpy(np.ascontiguousarray(rank if self.n else np.zeros(1), dtype=np.uint32)
+                                      .view(np.int32)).to(e.device)
         delta = torch.empty(max(self.n, 1), dtype=torch.int32, device=e.device)
         nneigh = torch.empty(max(self.n, 1), dtype=torch.int32, device=e.device)
         check(e._lib.mrg_trf_delta(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),

@@ -14,9 +14,9 @@ Restates, on small host data:
 The listings come from the GPU (`Engine.list_best` = mrg_list_best_count/fill); tests can pass
 any `lister(reads, library_key, max_mismatches) -> [[(entry name, 0-based offset), ...], ...]`.
 
-The command line runs the array route (entry_tables, row_order, raise_unresolved and content_from_rows below +
+The command line runs the array route (entry_tables, row_order, raise_unresolved and sample_tables below +
 mrg_trf_classify + mrg_write_trf_tables); the functions above them are its model and serve reads beyond 255 nt, a
-`choose` other than min and `--trf-host`.
+`choose` other than min and `--trf-host`, as content_from_rows does for trf_samples.write_trf_samples.
 
 The per-sample `tRFs.samples.tmp/*` reports and their density-peak clustering (W2C:802-1088), which
 start from the trfContentDic that write_trf_tables leaves, are mirge_amd.trf_samples.
@@ -536,3 +536,32 @@ def content_from_rows(et, rec, seqs, quant, denom):
                             et.names[row[1]]: {"tRFType": TRF_TYPES[row[4]], "start": row[2], "end": row[3],
                                                "cigar": "undifined"}}
     return content
+
+
+class SampleTables:
+    """sample_tables' result, over the entries of entry_tables: entries int32 [E, 4] = (rank of the entry's name among the
+    distinct names in Python string order, template length or -1, flags: 1 = "pre_" in name, 2 = "pre" in name, 0); names =
+    the distinct names in that order; templates per entry (None where the lookup raises), aa_types per entry (et's)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def sample_tables(et, tables, pre_seqs):
+    """Per entry, everything trf_samples.sample_trf_dic and sample_reports ask of an entry: the block it belongs to (entries
+    of equal names are one block), its template (`pre_seqs[name]` if "pre" in name else `stru[name]["seq"]`: the two
+    spellings "pre" / "pre_" stay two columns, as in entry_tables) and the amino acid of the summary."""
+    import numpy as np
+    stru = tables["trnaStruDic"]
+    names = sorted(set(et.names))
+    rank = {x: r for r, x in enumerate(names)}
+    entries = np.zeros((len(et.names), 4), dtype=np.int32)
+    templates = []
+    for e, name in enumerate(et.names):
+        try:
+            t = pre_seqs[name] if "pre" in name else stru[name]["seq"]
+        except KeyError:
+            t = None
+        templates.append(t)
+        entries[e] = (rank[name], -1 if t is None else len(t), ("pre_" in name) | (("pre" in name) << 1), 0)
+    return SampleTables(entries=entries, names=names, templates=templates, aa_types=list(et.aa_types), n_names=len(names))

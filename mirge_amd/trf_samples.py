@@ -199,41 +199,55 @@ def run_peaks(groups, peaks):
     with rho, delta, nneigh, sort_rho_idx (the reference's arrays, index 0 = the dummy), cl, NCLUST, ccenter
     and bord_rho."""
     args = layout(groups)
-    off, n_all = args[0], int(args[0][-1])
-    state = peaks(*args, gaussian_table())
+    return peaks_results(args[0], peaks(*args, gaussian_table()))
+
+
+def peaks_results(off, state, device_rank=False):
+    """run_peaks after the rho pass, for groups given by their row offsets alone.  The rank order is a stable argsort
+    of -rho per group here, as run_peaks has always done; with device_rank it is the backend's (state.rank():
+    mrg_trf_rank on the GPU, where the rank then stays for min_distance(None); only the array route asks for it).
+    rho is downloaded either way: the label pass below reads it."""
+    n_groups, n_all = len(off) - 1, int(off[-1])
+    sizes = np.diff(np.asarray(off).astype(np.int64))
     rho_all = np.asarray(state.rho, dtype=np.float32)
     max_dis = np.asarray(state.max_dis)
     # min_distance's rank order (W2C:521): stable sort of -rho, the dummy index 0 (rho = -1) last
-    res, rank = [], np.zeros(n_all, dtype=np.uint32)
-    for k, g in enumerate(groups):
+    from_backend = bool(device_rank)
+    res, rank = [], (np.asarray(state.rank()) if from_backend else np.zeros(n_all, dtype=np.uint32))
+    for k in range(n_groups):
         a, b = int(off[k]), int(off[k + 1])
-        rho = np.empty(g.n + 1, dtype=np.float32)
+        rho = np.empty(int(sizes[k]) + 1, dtype=np.float32)
         rho[0] = -1.0
         rho[1:] = rho_all[a:b]
-        order = np.argsort(-rho, kind="stable")
-        assert order[-1] == 0
-        rank[a:b] = order[:-1] - 1
+        if from_backend:
+            order = np.zeros(int(sizes[k]) + 1, dtype=np.int64)
+            order[:-1] = rank[a:b].astype(np.int64) + 1
+        else:
+            order = np.argsort(-rho, kind="stable")
+            assert order[-1] == 0
+            rank[a:b] = order[:-1] - 1
         res.append({"rho": rho, "sort_rho_idx": order, "max_dis": int(max_dis[k])})
-    delta_all, nneigh_all = state.min_distance(rank)
-    bord_off = np.zeros(len(groups) + 1, dtype=np.uint32)
+    delta_all, nneigh_all = state.min_distance(None if from_backend else rank)
+    bord_off = np.zeros(n_groups + 1, dtype=np.uint32)
     labels = np.zeros(n_all, dtype=np.int32)
-    for k, g in enumerate(groups):
+    for k in range(n_groups):
+        gn = int(sizes[k])
         a, b = int(off[k]), int(off[k + 1])
         r = res[k]
         top = int(r["sort_rho_idx"][0])
-        dl = np.empty(g.n + 1, dtype=np.float64)
+        dl = np.empty(gn + 1, dtype=np.float64)
         dl[0] = 0.0
         dl[1:] = delta_all[a:b]
         dl[top] = -1.0
         dl[top] = dl.max()                                           # W2C:532
-        nn = np.zeros(g.n + 1, dtype=np.int32)
+        nn = np.zeros(gn + 1, dtype=np.int32)
         nn[1:] = nneigh_all[a:b] + 1
         nn[top] = 0
         rho = r["rho"]
         delta = dl.astype(np.float32)
         # cluster centers (W2C:883-893)
         centers = (np.nonzero((rho[1:] >= RHOMIN) & (delta[1:] >= DELTAMIN))[0] + 1).tolist()
-        cl = np.zeros(g.n + 1) - 1
+        cl = np.zeros(gn + 1) - 1
         ccenter = {}
         for c, idx in enumerate(centers, 1):
             cl[idx] = c
@@ -246,7 +260,7 @@ def run_peaks(groups, peaks):
             ccenter[1] = idx
         # assignation (W2C:910-912): in rank order, a row takes its nearest denser neighbour's label
         cl_l, order, nn_l = cl.tolist(), r["sort_rho_idx"].tolist(), nn.tolist()
-        for i in range(g.n):
+        for i in range(gn):
             s = order[i]
             if cl_l[s] == -1:
                 cl_l[s] = cl_l[nn_l[s]]
@@ -371,40 +385,194 @@ def write_trf_samples(outputdir, sampleList, trfContentDic, tables, pretrnaNameS
         groups += [Group(rows) for rows in blocks]
     res = run_peaks(groups, peaks) if groups else []
     for sample, names, g0, nb in per_sample:
-        unified_sel, names_sel, name_dic = [], [], {}
-        with open(os.path.join(tdir, sample + ".potential_tRFs.clusters.detail"), "w") as out1:
-            for k in range(nb):
-                name = names[k]
-                con, content, sum_rpm = cluster_text(name, groups[g0 + k], res[g0 + k])
-                out1.write(con)
-                name_dic[name] = content
-                if sum_rpm >= RP100K_CUTOFF:
-                    names_sel.append(name)
-                    if "pre" in name:
-                        name = "_".join(name.split("_")[1:-1])
-                    if name not in unified_sel:
-                        unified_sel.append(name)
-        with open(os.path.join(tdir, sample + ".tRFs.report.tsv"), "w") as out2:
-            out2.write("tRNA name\ttRNA sequence\ttRF sequence\ttRF mismatch\ttRF type\ttRF coordinate\tRead count\t"
-                       "RP100K\n")
-            for t in unified_sel:
-                if t in names_sel:
-                    seq = stru[t]["seq"]
-                    for c in name_dic[t]:
-                        st, pos = detect_mismatch(c[0], seq, c[2])
-                        out2.write(t + "\t" + seq + "\t" + c[0] + "\t" + ":".join([st, pos]) + "\t" + c[1] + "\t" + c[2]
-                                   + "\t" + str(c[3]) + "\t" + "%.2f" % round(c[4], 2) + "\n")
-                pre = "pre_" + t + "_trailer"
-                if pre in names_sel:
-                    seq = pretrnaNameSeqDic[pre]
-                    for c in name_dic[pre]:
-                        new_pos = ":".join([c[2].split(":")[0], str(int(c[2].split(":")[1]) - 3)])
-                        st, pos = detect_mismatch(c[0][:-3], seq, new_pos)
-                        out2.write(t + "\t" + seq + "\t" + c[0] + "\t" + ":".join([st, pos]) + "\t" + c[1] + "\t" + c[2]
-                                   + "\t" + str(c[3]) + "\t" + "%.2f" % round(c[4], 2) + "\n")
+        _write_clusters(tdir, sample, ((names[k], groups[g0 + k], res[g0 + k]) for k in range(nb)), stru, pretrnaNameSeqDic)
     return tdir
+
+
+def _write_clusters(tdir, sample, named_groups, stru, pretrnaNameSeqDic):
+    """W2C:914-1088 for one sample: .clusters.detail and .tRFs.report.tsv from (name, group, peaks result) triples."""
+    unified_sel, names_sel, name_dic = [], [], {}
+    with open(os.path.join(tdir, sample + ".potential_tRFs.clusters.detail"), "w") as out1:
+        for name, group, r in named_groups:
+            con, content, sum_rpm = cluster_text(name, group, r)
+            out1.write(con)
+            name_dic[name] = content
+            if sum_rpm >= RP100K_CUTOFF:
+                names_sel.append(name)
+                if "pre" in name:
+                    name = "_".join(name.split("_")[1:-1])
+                if name not in unified_sel:
+                    unified_sel.append(name)
+    with open(os.path.join(tdir, sample + ".tRFs.report.tsv"), "w") as out2:
+        out2.write("tRNA name\ttRNA sequence\ttRF sequence\ttRF mismatch\ttRF type\ttRF coordinate\tRead count\t"
+                   "RP100K\n")
+        for t in unified_sel:
+            if t in names_sel:
+                seq = stru[t]["seq"]
+                for c in name_dic[t]:
+                    st, pos = detect_mismatch(c[0], seq, c[2])
+                    out2.write(t + "\t" + seq + "\t" + c[0] + "\t" + ":".join([st, pos]) + "\t" + c[1] + "\t" + c[2]
+                               + "\t" + str(c[3]) + "\t" + "%.2f" % round(c[4], 2) + "\n")
+            pre = "pre_" + t + "_trailer"
+            if pre in names_sel:
+                seq = pretrnaNameSeqDic[pre]
+                for c in name_dic[pre]:
+                    new_pos = ":".join([c[2].split(":")[0], str(int(c[2].split(":")[1]) - 3)])
+                    st, pos = detect_mismatch(c[0][:-3], seq, new_pos)
+                    out2.write(t + "\t" + seq + "\t" + c[0] + "\t" + ":".join([st, pos]) + "\t" + c[1] + "\t" + c[2]
+                               + "\t" + str(c[3]) + "\t" + "%.2f" % round(c[4], 2) + "\n")
 
 
 def engine_peaks(engine):
     """The density-peak backend on the GPU."""
     return engine.trf_peaks
+
+
+# ---------------------------------------------------------------- the array route (mrg_trf_sample_groups)
+class _Lazy:
+    """A read-only sequence whose items are made when they are asked for."""
+
+    def __init__(self, n, make):
+        self.n, self.make = n, make
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        if not -self.n <= i < self.n:
+            raise IndexError(i)
+        return self.make(i % self.n)
+
+
+_BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+class ArrayGroup:
+    """Group's stand-in on the rows [a, b) of the device layout (host copies): what peaks_results' label pass and
+    cluster_text ask of a group.  `chars` is decoded from the packed rows; a row becomes a string only when
+    cluster_text prints it."""
+
+    def __init__(self, codes, nmask, span, rpm, rows, a, b, L):
+        from .trf import TRF_TYPES
+        self.n, self.L = b - a, int(L)
+        cols = np.arange(self.L)
+        sh = (2 * (cols & 31)).astype(np.uint64)[None, :]
+        self.chars = _BASES[((codes[cols >> 5, a:b].T >> sh) & np.uint64(3)).astype(np.intp)]
+        if nmask is not None:
+            self.chars[((nmask[cols >> 5, a:b].T >> sh) & np.uint64(1)).astype(bool)] = ord("N")
+        self.first = (span[a:b] & 0xFF).astype(np.int64)
+        self.last = (span[a:b] >> 8).astype(np.int64)
+        self.chars[(cols[None, :] + 1 < self.first[:, None]) | (cols[None, :] + 1 > self.last[:, None])] = ord("-")
+        self.rpm = np.asarray(rpm[a:b], dtype=np.float64)
+        self.counts = rows[a:b, 1].tolist()
+        types = rows[a:b, 2]
+        self.types = _Lazy(self.n, lambda i: TRF_TYPES[types[i]])
+        self.seqs = _Lazy(self.n, lambda i: self.chars[i].tobytes().decode("ascii"))
+
+    distance_to = Group.distance_to
+
+
+def layout_peaks(fn):
+    """A `peaks(off, codes, nmask, span, rpm, max_len, ktab)` backend (Engine.trf_peaks, the tests' model) as the
+    `peaks(groups, ktab)` backend of write_trf_samples_arrays."""
+    return lambda g, ktab: fn(g.off, g.codes, g.nmask, g.span, g.rpm, g.max_len, ktab)
+
+
+def engine_groups(engine, device=None):
+    """The `groups` backend on the GPU.  device: (words, lens, nmask, quant) tensors that already hold the host arrays
+    (a single-process run's ReadSet), used in their place."""
+    def groups(st, rec, words, lens, nmask, quant, denom, timings=None):
+        if device is not None:
+            words, lens, nmask, quant = device
+        return engine.trf_sample_groups(st, rec, words, lens, nmask, quant, denom, timings=timings)
+    return groups
+
+
+def engine_peaks_groups(engine):
+    """The density-peak backend on the device tensors of engine_groups' result."""
+    return engine.trf_peaks_groups
+
+
+def write_trf_sample_reports(tdir, sampleList, st, et, g, rec, words, lens, nmask, quant, denom):
+    """<sample>.potential_tRFs.report and .summary.report of every sample from the arrays and the tables of the
+    `groups` backend, by the native writer (mrg_write_trf_sample_reports): the files sample_reports gives."""
+    import ctypes as C
+
+    from . import _native
+    lib = _native.load()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    quant = np.ascontiguousarray(quant, dtype=np.uint32).reshape(n, -1)
+    S = len(sampleList)
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, 12)
+    denom = np.ascontiguousarray(denom, dtype=np.uint64)
+    if quant.shape[1] != S or denom.shape[0] != S:
+        raise ValueError("write_trf_sample_reports: quant [n, S] and denom [S] must match the samples")
+    entries = np.ascontiguousarray(st.entries, dtype=np.int32)
+    blocks = np.ascontiguousarray(g.blocks, dtype=np.int32).reshape(-1, 6)
+    sums = np.ascontiguousarray(g.block_sums, dtype=np.uint64)
+    rows = np.ascontiguousarray(g.rows, dtype=np.uint32).reshape(-1, 3)
+    paths = (C.c_char_p * (2 * S))(*[os.fsencode(os.path.join(tdir, s + suffix)) for s in sampleList
+                                      for suffix in (".potential_tRFs.report", ".potential_tRFs.summary.report")])
+
+    def strings(items):
+        return (C.c_char_p * max(len(items), 1))(*[None if x is None else x.encode() for x in items])
+    _native.check(lib.mrg_write_trf_sample_reports(
+        paths, S, denom.ctypes.data, words.ctypes.data, W, n, lens.ctypes.data, None if nm is None else nm.ctypes.data, n,
+        quant.ctypes.data, rec.ctypes.data, rec.shape[0], entries.ctypes.data, strings(et.names), strings(st.templates),
+        strings(st.aa_types), entries.shape[0], int(st.n_names), blocks.ctypes.data, sums.ctypes.data, blocks.shape[0],
+        rows.ctypes.data, rows.shape[0]))
+
+
+def write_trf_samples_arrays(outputdir, sampleList, et, st, rec, words, lens, nmask, quant, denom, tables, pretrnaNameSeqDic,
+                             groups, peaks, timings=None, device_rank=False):
+    """write_trf_samples from the arrays: the four files of every sample under <outputdir>/tRFs.samples.tmp/, byte for
+    byte, without a Python object per read.  et / st = trf.entry_tables / trf.sample_tables; rec = the rows of
+    Engine.trf_classify in the order of the tsv (columnar.write_trf_tables returns them); words / lens / nmask /
+    quant = the host arrays of the reads; denom[s] = maturetrnaReads + pretrnaReads.  `groups(st, rec, words, lens,
+    nmask, quant, denom, timings=)` is the block backend (engine_groups(engine) on the GPU, tests/trf_groups_model.py
+    in the CPU tests), `peaks(groups' result, ktab)` the density-peak backend (engine_peaks_groups(engine), or
+    layout_peaks(fn) around a backend of write_trf_samples); device_rank: take the rank order from that backend's
+    rank() (mrg_trf_rank) instead of the host argsort.  The two report files are written natively; the label
+    pass of the peaks, .clusters.detail and .tRFs.report.tsv still walk the groups here, on ArrayGroup."""
+    import time
+    stru = tables["trnaStruDic"]
+    rec = np.asarray(rec).reshape(-1, 12)
+    t0 = time.perf_counter()
+    g = groups(st, rec, words, lens, nmask, quant, denom, timings=timings)
+    if g.no_template_row is not None:      # what sample_trf_dic raises at the first such read, before anything is written
+        raise et.errors[(int(rec[g.no_template_row, 1]), "length")]
+    if g.max_len > MAX_TEMPLATE:
+        raise ValueError("trf_samples: a template of %d nt: density peaks take templates of at most %d nt"
+                         % (g.max_len, MAX_TEMPLATE))
+    t1 = time.perf_counter()
+    tdir = os.path.join(outputdir, "tRFs.samples.tmp")
+    os.makedirs(tdir, exist_ok=True)
+    write_trf_sample_reports(tdir, sampleList, st, et, g, rec, words, lens, nmask, quant, denom)
+    t2 = time.perf_counter()
+    off = np.asarray(g.off, dtype=np.uint32)
+    n_groups = len(off) - 1
+    if n_groups:
+        state = peaks(g, gaussian_table())
+        res = peaks_results(off, state, device_rank=device_rank)
+    else:
+        res = []
+    t3 = time.perf_counter()
+    blocks, pairs = np.asarray(g.blocks).reshape(-1, 6), np.asarray(g.groups).reshape(-1, 2)
+    if n_groups:
+        codes, nm, span, rpm, rows = g.codes, g.nmask, g.span, g.rpm, np.asarray(g.rows).reshape(-1, 3)
+    group_sample = blocks[pairs[:, 0], 0] if n_groups else np.zeros(0, dtype=np.int32)
+    for si, sample in enumerate(sampleList):
+        def named(si=si):
+            for k in np.nonzero(group_sample == si)[0].tolist():
+                own, paired = int(pairs[k, 0]), int(pairs[k, 1])
+                L = int(st.entries[blocks[own, 1], 1])
+                yield (et.names[blocks[paired, 1]], ArrayGroup(codes, nm, span, rpm, rows, int(off[k]), int(off[k + 1]), L),
+                       res[k])
+        _write_clusters(tdir, sample, named(), stru, pretrnaNameSeqDic)
+    if timings is not None:
+        t4 = time.perf_counter()
+        timings.update(groups_s=t1 - t0, reports_s=t2 - t1, peaks_s=t3 - t2, clusters_s=t4 - t3)
+    return tdir
