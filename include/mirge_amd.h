@@ -1239,6 +1239,68 @@ int mrg_trf_border(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, uint32_
                    const uint64_t *d_nmask, const uint16_t *d_span, const float *d_rho, const int32_t *d_label,
                    const uint32_t *bord_off, float *d_bord, void *stream);
 
+/*
+ * -trf: what follows the three passes above -- cluster centres, every row's label, core and halo, and the two files that
+ * list the clusters -- from the arrays (the label pass of peaks_results, cluster_text and _write_clusters of
+ * mirge_amd/trf_samples.py, whose results the calls reproduce exactly).  off as above, on the HOST.
+ *
+ * mrg_trf_assign  d_rho, d_rank, d_delta, d_nneigh as mrg_trf_rho / mrg_trf_rank / mrg_trf_delta left them (read only).
+ *                 Per group: top = d_rank[off[g]]; the top's delta counts as max(0, delta of every other row) (0 in a
+ *                 one-row group) and it has no neighbour.  CENTRES are the rows with rho >= 5.0f and delta >= 8, numbered
+ *                 1..NCLUST in ROW order; a group without centre whose largest delta is <= 8 and largest rho >= 5.0f takes
+ *                 its first row of maximal rho as cluster 1 (W2C:895-908).  d_label[i] (int32) = the number of the first
+ *                 centre on the chain i, nneigh[i], nneigh[nneigh[i]], ...; -1 when the chain ends in a top row that is no
+ *                 centre.  (The reference assigns in rank order; nneigh always ranks above its row, so the result is a
+ *                 function of the forest alone.)  Found by pointer doubling over the rows of all groups at once, in
+ *                 ceil(log2(largest group)) + 1 rounds fixed on the host, every index checked against its group before it
+ *                 is followed.  A first rank entry or a nneigh outside its group, a row that names itself, and rows still
+ *                 open after the last round (a cycle) are MRG_ERR_ARG: the host arrays are left alone and d_label is zeroed
+ *                 (0 is no label).  HOST outputs: nclust[n_groups]; cen_off[n_groups + 1] (cen_off[n_groups] = all centres);
+ *                 centers[] = the group-local row of every centre, cluster 1 first, written when cap_centers >=
+ *                 cen_off[n_groups] (a call with cap_centers = 0 only counts; off[n_groups] always suffices).
+ * mrg_trf_halo    after mrg_trf_border (d_label may be passed to it as it is).  cen_off / centers as above, bord_off / d_bord
+ *                 as given to and left by mrg_trf_border (groups with NCLUST > 1 need NCLUST + 1 slots), all checked on the
+ *                 host first.  d_counts[i * count_stride] = the read count of row i (uint32; the d_rows of
+ *                 mrg_trf_sample_groups with d_rows + 1 and stride 3).  Row i of label c >= 1 is CORE unless NCLUST > 1 and
+ *                 rho[i] < d_bord[bord_off[g] + c], or its getDistance to the centre of c exceeds 8; a row of label -1 is
+ *                 never core and belongs to no cluster.  d_core[i] (uint8).  tallies (HOST uint64 [cen_off[n_groups]][4], by
+ *                 64-bit atomic adds) = members, core rows, read count in the core, read count in the halo of every cluster.
+ *                 d_order (uint32 [n]) = the rows sorted by (group, label - 1; label -1 last), stable: a cluster's members
+ *                 are contiguous and in row order.  The RP100K sums are floating point and are NOT taken here.  A label
+ *                 that names no cluster of its group is MRG_ERR_ARG.
+ * mrg_write_trf_cluster_reports  HOST arrays: the row layout (codes / nmask [W][stride], span, rpm, rows [n][3] = tsv row,
+ *                 count, type), off, and per group its sample (ascending), the bases of its own template, the name it is
+ *                 paired with, the tRNA it is reported under (the name, or "_".join(name.split("_")[1:-1]) when "pre" is in
+ *                 the name), trnaStruDic[name]["seq"] and pretrnaNameSeqDic[name] (NULL where the table lacks the name);
+ *                 labels, core, order, nclust, cen_off, centers, tallies as above.  paths[2 s] =
+ *                 <sample>.potential_tRFs.clusters.detail, paths[2 s + 1] = <sample>.tRFs.report.tsv.  Every RP100K sum is
+ *                 added in the Python's order by the one thread that owns the group; the integer tallies are added again and
+ *                 compared (a mismatch, or tables that contradict each other, is MRG_ERR_ARG).  status (HOST int64[2]):
+ *                 {0, 0} = written; {1, g} = the record route's KeyError, {2, g} = its IndexError (detect_mismatch on a
+ *                 template shorter than the tRF) at group g: the call returns MRG_OK and has written nothing.  Runs of
+ *                 groups are formatted by worker threads (MIRGE_AMD_TABLE_THREADS, at most 16;
+ *                 MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS = rows per run); the bytes depend on neither.
+ * mrg_py3_float_repr  Python 3's repr(value) (shortest digits that read back, ".0" on whole numbers, exponent form below
+ *                 1e-4 and from 1e16) into out[cap], cap >= 32, NUL-terminated: what "+".join(str(x) ...) prints.
+ */
+int mrg_trf_assign(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, const float *d_rho, const uint32_t *d_rank,
+                   const int32_t *d_delta, const int32_t *d_nneigh, int32_t *d_label, uint32_t *nclust, uint64_t cap_centers,
+                   uint32_t *cen_off, uint32_t *centers, void *stream);
+int mrg_trf_halo(mrg_ctx *ctx, const uint32_t *off, uint32_t n_groups, uint32_t max_len, const uint64_t *d_codes,
+                 const uint64_t *d_nmask, const uint16_t *d_span, const float *d_rho, const int32_t *d_label,
+                 const uint32_t *d_counts, uint32_t count_stride, const uint32_t *cen_off, const uint32_t *centers,
+                 const uint32_t *bord_off, const float *d_bord, uint8_t *d_core, uint32_t *d_order, uint64_t *tallies,
+                 void *stream);
+int mrg_write_trf_cluster_reports(const char *const *paths, uint32_t n_samples, const uint64_t *codes, const uint64_t *nmask,
+                                  uint32_t max_len, uint64_t stride, const uint16_t *span, const double *rpm,
+                                  const uint32_t *rows, uint64_t n_rows, const uint32_t *off, uint32_t n_groups,
+                                  const int32_t *group_sample, const int32_t *group_len, const char *const *group_names,
+                                  const char *const *group_keys, const char *const *group_mature,
+                                  const char *const *group_trailer, const int32_t *labels, const uint8_t *core,
+                                  const uint32_t *order, const uint32_t *nclust, const uint32_t *cen_off,
+                                  const uint32_t *centers, const uint64_t *tallies, int64_t *status);
+int mrg_py3_float_repr(double value, char *out, uint64_t cap);
+
 /* Packing helper used by hosts without numpy: ASCII reads -> SoA words. */
 int mrg_pack_reads(const char *const *seqs, uint64_t n, uint32_t words_per_read,
                    uint64_t *reads, uint8_t *lens, uint64_t *nmask, int *has_n);

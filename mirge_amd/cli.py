@@ -520,12 +520,14 @@ def annotate_main(args, engine_factory=None, materialize=False):
             t_rec, _ = columnar.write_trf_tables(outdir, sample_list, log_dic, h_words, h_lens, h_nmask, h_quant, rows[0],
                                                  rows[1], rows[2], et)
             # the blocks, their rows' layout and the two report files from the arrays (Engine.trf_sample_groups,
-            # mrg_write_trf_sample_reports); with --gpus N rank 0 passes the gathered host arrays
+            # mrg_write_trf_sample_reports), centres, labels and halos on the device (mrg_trf_assign / mrg_trf_halo) and the two
+            # cluster files from the arrays (mrg_write_trf_cluster_reports); with --gpus N rank 0 passes the gathered host arrays
             on_device = None if world > 1 or shard.quant is None else (shard.words, shard.lens, shard.nmask, shard.quant)
             trf_samples.write_trf_samples_arrays(
                 outdir, sample_list, et, trf.sample_tables(et, trf_tables, pre_seqs), t_rec, h_words, h_lens, h_nmask, h_quant,
                 [q["maturetrnaReads"] + q["pretrnaReads"] for q in log_dic["quantStats"]][:S], trf_tables, pre_seqs,
-                trf_samples.engine_groups(engine, on_device), trf_samples.engine_peaks_groups(engine), device_rank=True)
+                trf_samples.engine_groups(engine, on_device), trf_samples.engine_peaks_groups(engine), device_rank=True,
+                device_labels=True)
         else:
             trf_samples.write_trf_samples(outdir, sample_list, trf_content, trf_tables, pre_seqs,
                                           trf_samples.engine_peaks(engine))

@@ -30,6 +30,7 @@
 #include "sa_build.hpp"
 #include "tables.hpp"
 #include "trf_groups.hpp"
+#include "trf_labels.hpp"
 #include "trf_peaks.hpp"
 #include "trf_tables.hpp"
 
@@ -4576,6 +4577,185 @@ int mrg_trf_border(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_
   hipError_t e = bord_off[n_groups] ? hipMemsetAsync(d_bord, 0, bord_off[n_groups] * sizeof(float), st) : hipSuccess;
   if (e == hipSuccess) e = mrg::trf_border_launch(L, d_rho, d_label, (const uint32_t*)bo, d_bord, st);
   return trf_finish(meta, e, st);
+}
+
+// ---------------------------------------------------------------- -trf centres, labels, halos (csrc/trf_labels.hip)
+static int trf_check_off(const char* fn, const uint32_t* off, uint32_t n_groups) {
+  if (n_groups > (1u << 24) || off[0] != 0) return fail(MRG_ERR_ARG, "%s: 1..2^24 groups, off[0] = 0", fn);
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (off[g + 1] < off[g]) return fail(MRG_ERR_ARG, "%s: offsets decrease at group %u", fn, g);
+  return MRG_OK;
+}
+
+int mrg_trf_assign(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, const float* d_rho, const uint32_t* d_rank,
+                   const int32_t* d_delta, const int32_t* d_nneigh, int32_t* d_label, uint32_t* nclust, uint64_t cap_centers,
+                   uint32_t* cen_off, uint32_t* centers, void* stream) {
+  const char* fn = "mrg_trf_assign";
+  if (!ctx || !off || !n_groups || !nclust || !cen_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (int rc = trf_check_off(fn, off, n_groups)) return rc;
+  const uint32_t n = off[n_groups], G = n_groups;
+  if (n && (!d_rho || !d_rank || !d_delta || !d_nneigh || !d_label)) return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
+  if (cap_centers && !centers) return fail(MRG_ERR_ARG, "%s: null centre buffer", fn);
+  if (n == 0) {
+    std::memset(nclust, 0, G * sizeof(uint32_t));
+    std::memset(cen_off, 0, (G + 1ull) * sizeof(uint32_t));
+    return MRG_OK;
+  }
+  uint32_t largest = 1;
+  for (uint32_t g = 0; g < G; ++g) largest = std::max(largest, off[g + 1] - off[g]);
+  const uint32_t rounds = bits_for(largest - 1) + 1;  // ceil(log2(largest group)) + 1: a chain has fewer steps than rows
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  TrfBuf b;
+  const uint64_t o_off = b.reserve((G + 1ull) * 4), o_grp = b.reserve(n * 4ull), o_zero = b.reserve(0), o_gdelta = b.reserve(G * 4ull),
+                 o_grho = b.reserve(G * 4ull), o_err = b.reserve(4), o_fb = b.reserve(G * 4ull), o_flags = b.reserve((n + 1ull) * 4),
+                 o_ncl = b.reserve((G + 1ull) * 4), o_lab0 = b.reserve(n * 4ull), o_lab1 = b.reserve(n * 4ull),
+                 o_nxt0 = b.reserve(n * 4ull), o_nxt1 = b.reserve(n * 4ull), o_cen = b.reserve(n * 4ull),
+                 o_tmp = b.reserve(std::max(mrg::prims::scan_temp_bytes(n + 1ull), mrg::prims::scan_temp_bytes(G + 1ull)));
+  HIP_TRY(b.alloc());
+  HIP_TRY(hipMemcpyAsync(b.p + o_off, off, (G + 1ull) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(b.p + o_zero, 0, o_fb - o_zero, st));  // gdelta, grho, err
+  HIP_TRY(hipMemsetAsync(b.p + o_fb, 0xFF, G * 4ull, st));
+  const mrg::TrfAssignIn in{b.at<uint32_t>(o_off), G, n, d_rho, d_rank, d_delta, d_nneigh};
+  uint32_t *grp = b.at<uint32_t>(o_grp), *gdelta = b.at<uint32_t>(o_gdelta), *grho = b.at<uint32_t>(o_grho), *err = b.at<uint32_t>(o_err),
+           *fb = b.at<uint32_t>(o_fb), *flags = b.at<uint32_t>(o_flags), *ncl = b.at<uint32_t>(o_ncl), *cen = b.at<uint32_t>(o_cen);
+  int32_t* lab[2] = {b.at<int32_t>(o_lab0), b.at<int32_t>(o_lab1)};
+  uint32_t* nxt[2] = {b.at<uint32_t>(o_nxt0), b.at<uint32_t>(o_nxt1)};
+  HIP_TRY(mrg::trf_assign_stats_launch(in, grp, gdelta, grho, err, st));
+  HIP_TRY(mrg::trf_assign_flags_launch(in, grp, gdelta, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1ull, b.p + o_tmp, st));
+  HIP_TRY(mrg::trf_assign_fallback_launch(in, grp, flags, gdelta, grho, fb, st));
+  HIP_TRY(mrg::trf_assign_nclust_launch(in, flags, fb, ncl, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(ncl, ncl, G + 1ull, b.p + o_tmp, st));
+  HIP_TRY(mrg::trf_assign_init_launch(in, grp, flags, fb, ncl, lab[0], nxt[0], cen, err, st));
+  int cur = 0;
+  for (uint32_t r = 0; r < rounds; ++r, cur ^= 1) HIP_TRY(mrg::trf_assign_round_launch(in, grp, lab[cur], nxt[cur], lab[cur ^ 1], nxt[cur ^ 1], st));
+  HIP_TRY(mrg::trf_assign_finish_launch(n, lab[cur], d_label, err, st));
+  uint32_t h_err = 0;
+  std::vector<uint32_t> h_off(G + 1ull);
+  HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_off.data(), ncl, (G + 1ull) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_err) {
+    HIP_TRY(hipMemsetAsync(d_label, 0, n * 4ull, st));  // (0 is no label)
+    HIP_TRY(hipStreamSynchronize(st));
+    return fail(MRG_ERR_ARG, "%s: %s", fn,
+                (h_err & mrg::kTrfErrTop)         ? "the first rank entry of a group is none of its rows"
+                : (h_err & mrg::kTrfErrNeighbour) ? "a nneigh lies outside its group"
+                                                  : "the nneigh of some rows form a cycle");
+  }
+  const uint64_t total = h_off[G];
+  if (total > n) return fail(MRG_ERR_HIP, "%s: more centres than rows", fn);
+  if (total && cap_centers >= total) {
+    HIP_TRY(hipMemcpyAsync(centers, cen, total * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  std::memcpy(cen_off, h_off.data(), (G + 1ull) * 4);
+  for (uint32_t g = 0; g < G; ++g) nclust[g] = h_off[g + 1] - h_off[g];
+  return MRG_OK;
+}
+
+int mrg_trf_halo(mrg_ctx* ctx, const uint32_t* off, uint32_t n_groups, uint32_t max_len, const uint64_t* d_codes,
+                 const uint64_t* d_nmask, const uint16_t* d_span, const float* d_rho, const int32_t* d_label,
+                 const uint32_t* d_counts, uint32_t count_stride, const uint32_t* cen_off, const uint32_t* centers,
+                 const uint32_t* bord_off, const float* d_bord, uint8_t* d_core, uint32_t* d_order, uint64_t* tallies,
+                 void* stream) {
+  const char* fn = "mrg_trf_halo";
+  if (!ctx || !off || !n_groups || !cen_off || !bord_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (max_len < 1 || max_len > 255) return fail(MRG_ERR_ARG, "%s: templates of 1..255 nt (got %u)", fn, max_len);
+  if (int rc = trf_check_off(fn, off, n_groups)) return rc;
+  const uint32_t n = off[n_groups], G = n_groups;
+  if (n && (!d_codes || !d_span || !d_rho || !d_label || !d_counts || !d_core || !d_order || !count_stride))
+    return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
+  if (cen_off[0] != 0 || bord_off[0] != 0) return fail(MRG_ERR_ARG, "%s: cen_off[0] = bord_off[0] = 0", fn);
+  uint32_t most = 0;
+  for (uint32_t g = 0; g < G; ++g)  // (all of them first: centers[] is as long as cen_off[n_groups] says)
+    if (cen_off[g + 1] < cen_off[g] || bord_off[g + 1] < bord_off[g]) return fail(MRG_ERR_ARG, "%s: offsets decrease at group %u", fn, g);
+  for (uint32_t g = 0; g < G; ++g) {
+    const uint32_t nc = cen_off[g + 1] - cen_off[g], size = off[g + 1] - off[g];
+    if (nc > size) return fail(MRG_ERR_ARG, "%s: group %u has more centres than rows", fn, g);
+    if (nc && !centers) return fail(MRG_ERR_ARG, "%s: null centres", fn);
+    for (uint32_t c = 0; c < nc; ++c)
+      if (centers[cen_off[g] + c] >= size) return fail(MRG_ERR_ARG, "%s: a centre of group %u is none of its rows", fn, g);
+    if (nc > 1 && bord_off[g + 1] - bord_off[g] != nc + 1)
+      return fail(MRG_ERR_ARG, "%s: group %u needs NCLUST + 1 border slots", fn, g);
+    most = std::max(most, nc);
+  }
+  const uint32_t C_all = cen_off[G];
+  if ((C_all && !tallies) || (bord_off[G] && !d_bord)) return fail(MRG_ERR_ARG, "%s: null tally / border buffers", fn);
+  if (n == 0) return MRG_OK;
+  const uint32_t slot_bits = bits_for(most), key_bits = slot_bits + bits_for(G);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  TrfBuf b;
+  const uint64_t o_off = b.reserve((G + 1ull) * 4), o_coff = b.reserve((G + 1ull) * 4), o_boff = b.reserve((G + 1ull) * 4),
+                 o_cen = b.reserve(C_all * 4ull), o_zero = b.reserve(0), o_tally = b.reserve(C_all * 32ull), o_err = b.reserve(4),
+                 o_k0 = b.reserve(n * 8ull), o_k1 = b.reserve(n * 8ull), o_v0 = b.reserve(n * 4ull), o_v1 = b.reserve(n * 4ull),
+                 o_tmp = b.reserve(mrg::prims::radix_temp_bytes(n));
+  HIP_TRY(b.alloc());
+  HIP_TRY(hipMemcpyAsync(b.p + o_off, off, (G + 1ull) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b.p + o_coff, cen_off, (G + 1ull) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b.p + o_boff, bord_off, (G + 1ull) * 4, hipMemcpyHostToDevice, st));
+  if (C_all) HIP_TRY(hipMemcpyAsync(b.p + o_cen, centers, C_all * 4ull, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(b.p + o_zero, 0, o_k0 - o_zero, st));  // tallies, err
+  const mrg::TrfHaloIn in{b.at<uint32_t>(o_off), G, n, n, (max_len + 31) / 32, d_codes, d_nmask, d_span, d_rho, d_label, d_counts,
+                          count_stride, b.at<uint32_t>(o_coff), b.at<uint32_t>(o_cen), b.at<uint32_t>(o_boff), d_bord};
+  HIP_TRY(mrg::trf_halo_launch(in, slot_bits, d_core, b.at<unsigned long long>(o_tally), b.at<uint64_t>(o_k0), b.at<uint32_t>(o_v0),
+                               b.at<uint32_t>(o_err), st));
+  bool second = false;
+  HIP_TRY(mrg::prims::radix_sort_pairs_u64(b.at<uint64_t>(o_k0), b.at<uint64_t>(o_k1), b.at<uint32_t>(o_v0), b.at<uint32_t>(o_v1), n,
+                                           key_bits, b.p + o_tmp, st, &second));
+  HIP_TRY(hipMemcpyAsync(d_order, b.p + (second ? o_v1 : o_v0), n * 4ull, hipMemcpyDeviceToDevice, st));
+  uint32_t h_err = 0;
+  std::vector<uint64_t> h_tally(4ull * C_all);
+  HIP_TRY(hipMemcpyAsync(&h_err, b.p + o_err, 4, hipMemcpyDeviceToHost, st));
+  if (C_all) HIP_TRY(hipMemcpyAsync(h_tally.data(), b.p + o_tally, C_all * 32ull, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_err) return fail(MRG_ERR_ARG, "%s: a label names no cluster of its group", fn);
+  if (C_all) std::memcpy(tallies, h_tally.data(), C_all * 32ull);
+  return MRG_OK;
+}
+
+int mrg_write_trf_cluster_reports(const char* const* paths, uint32_t n_samples, const uint64_t* codes, const uint64_t* nmask,
+                                  uint32_t max_len, uint64_t stride, const uint16_t* span, const double* rpm, const uint32_t* rows,
+                                  uint64_t n_rows, const uint32_t* off, uint32_t n_groups, const int32_t* group_sample,
+                                  const int32_t* group_len, const char* const* group_names, const char* const* group_keys,
+                                  const char* const* group_mature, const char* const* group_trailer, const int32_t* labels,
+                                  const uint8_t* core, const uint32_t* order, const uint32_t* nclust, const uint32_t* cen_off,
+                                  const uint32_t* centers, const uint64_t* tallies, int64_t* status) {
+  const char* fn = "mrg_write_trf_cluster_reports";
+  if (!paths || !n_samples || !off || !status) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  for (uint32_t s = 0; s < 2 * n_samples; ++s)
+    if (!paths[s]) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_groups && (!group_sample || !group_len || !group_names || !group_keys || !group_mature || !group_trailer || !nclust || !cen_off))
+    return fail(MRG_ERR_ARG, "%s: null group tables", fn);
+  if (n_rows && (!codes || !span || !rpm || !rows || !labels || !core || !order)) return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
+  if (max_len < 1 || max_len > 255 || stride < n_rows || n_rows >= (1ull << 32)) return fail(MRG_ERR_ARG, "%s: bad max_len / stride", fn);
+  if (off[0] != 0) return fail(MRG_ERR_ARG, "%s: off[0] = 0", fn);
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (off[g + 1] < off[g]) return fail(MRG_ERR_ARG, "%s: offsets decrease at group %u", fn, g);
+  if (off[n_groups] != n_rows) return fail(MRG_ERR_ARG, "%s: the offsets do not cover the rows", fn);
+  if (n_groups && cen_off[n_groups] && (!centers || !tallies)) return fail(MRG_ERR_ARG, "%s: null centres / tallies", fn);
+  status[0] = status[1] = 0;
+  try {
+    const mrg::TrfClusterWriteArgs a{paths, n_samples, codes, nmask, max_len, stride, span, rpm, rows, n_rows, off, n_groups,
+                                     group_sample, group_len, group_names, group_keys, group_mature, group_trailer, labels, core,
+                                     order, nclust, cen_off, centers, tallies, status};
+    mrg::write_trf_cluster_reports(a);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+int mrg_py3_float_repr(double value, char* out, uint64_t cap) {
+  if (!out || cap < 32) return fail(MRG_ERR_ARG, "mrg_py3_float_repr: a buffer of at least 32 bytes is required");
+  const std::string s = mrg::py3_float_repr(value);
+  if (s.size() + 1 > cap) return fail(MRG_ERR_ARG, "mrg_py3_float_repr: buffer too small");
+  std::memcpy(out, s.c_str(), s.size() + 1);
+  return MRG_OK;
 }
 
 }  // extern "C"

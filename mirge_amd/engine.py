@@ -805,6 +805,7 @@ class Engine:
             if timings is not None:
                 for key, v in zip(("items_kernel_ms", "read_order_kernel_ms", "row_order_kernel_ms", "pack_kernel_ms"), kernel_ms):
                     timings[key] = float(v)
+        g.rows_d = rows_d
         g.rows = rows_d.cpu().numpy()[:R].view(np.uint32)
         return g
 
@@ -1078,6 +1079,7 @@ class Engine:
         """Engine.trf_peaks on the device tensors of a TrfGroups (Engine.trf_sample_groups): no host layout, no upload."""
         t = TrfPeaks(self, np.ascontiguousarray(groups.off, dtype=np.uint32), groups.max_len)
         t.codes, t.nmask, t.span = groups.codes_d, groups.nmask_d, groups.span_d
+        t.counts_d = None if groups.rows_d is None else groups.rows_d[:, 1]
         return self._trf_rho(t, groups.rpm_d, ktab)
 
     def _trf_rho(self, t, rpm_d, ktab):
@@ -1139,8 +1141,8 @@ class TrfGroups:
     """Result of Engine.trf_sample_groups.  Host: n_items, blocks int32 [B, 6] (sample, representative entry, first and
     number of printed rows, group or -1, 0), block_sums uint64 [B], off uint32 [G + 1], groups int32 [G, 2] (its block, the
     block whose name it is paired with), rows uint32 [n, 3] (tsv row, count, type), max_len, has_n, no_template_row.
-    Device: codes_d / nmask_d (None without N) [W][n], span_d, rpm_d; .codes / .nmask / .span / .rpm download them."""
-    codes_d = nmask_d = span_d = rpm_d = None
+    Device: codes_d / nmask_d (None without N) [W][n], span_d, rpm_d, rows_d; .codes / .nmask / .span / .rpm download them."""
+    codes_d = nmask_d = span_d = rpm_d = rows_d = None
     rows = np.zeros((0, 3), dtype=np.uint32)
 
     def _host(self, t, view, shape):
@@ -1167,7 +1169,7 @@ class TrfGroups:
 
 class TrfPeaks:
     """Device state of one Engine.trf_peaks batch (see there)."""
-    rank_d = None
+    rank_d = delta_d = nneigh_d = label_d = bord_d = counts_d = None
 
     def __init__(self, engine, off, max_len):
         self.engine, self.off, self.max_len = engine, off, int(max_len)
@@ -1190,7 +1192,7 @@ class TrfPeaks:
     def min_distance(self, rank=None):
         """min_distance (W2C:509-533): rank = each group's rows (group-local) in rank order, flat like the rows (None:
         what rank() left on the device).  Returns (delta, nneigh) int32[n]: distance to / group-local row of the nearest
-        row ranked above, -1 for the top row of a group."""
+        row ranked above, -1 for the top row of a group.  Both stay on the device for assign()."""
         torch = _torch()
         e = self.engine
         if rank is None:
@@ -1205,21 +1207,76 @@ class TrfPeaks:
         check(e._lib.mrg_trf_delta(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),
                                    self.span.data_ptr(), rank_d.data_ptr(), self.max_dis_d.data_ptr(),
                                    delta.data_ptr(), nneigh.data_ptr(), e._stream_ptr()))
+        self.delta_d, self.nneigh_d = delta, nneigh
         return delta.cpu().numpy()[:self.n], nneigh.cpu().numpy()[:self.n]
 
+    def assign(self):
+        """Cluster centres and labels (mrg_trf_assign) from what rank() and min_distance() left on the device.  Returns
+        (nclust uint32[G], cen_off uint32[G + 1], centers uint32[cen_off[-1]]: the group-local row of every centre, cluster 1
+        first); the labels (int32[n], -1 or 1..NCLUST) stay on the device for border(None, ...) and halo(); .labels()
+        downloads them."""
+        torch = _torch()
+        e = self.engine
+        if self.rank_d is None or self.delta_d is None:
+            raise ValueError("assign() needs rank() and min_distance() first")
+        nclust, cen_off = np.zeros(self.G, dtype=np.uint32), np.zeros(self.G + 1, dtype=np.uint32)
+        centers = np.zeros(max(self.n, 1), dtype=np.uint32)
+        label = torch.zeros(max(self.n, 1), dtype=torch.int32, device=e.device)
+        if self.G:
+            check(e._lib.mrg_trf_assign(e._h, self.off_c, self.G, self.rho_d.data_ptr(), self.rank_d.data_ptr(),
+                                        self.delta_d.data_ptr(), self.nneigh_d.data_ptr(), label.data_ptr(), nclust.ctypes.data,
+                                        self.n, cen_off.ctypes.data, centers.ctypes.data, e._stream_ptr()))
+        self.label_d, self.cen_off, self.centers = label, cen_off, centers[:int(cen_off[-1])]
+        return nclust, cen_off, self.centers
+
+    def labels(self):
+        return self.label_d.cpu().numpy()[:self.n]
+
     def border(self, labels, bord_off):
-        """Border densities (W2C:951-961): labels int32[n] (-1 or 1..NCLUST), bord_off[G+1] (NCLUST + 1 slots
-        per group, none where NCLUST <= 1).  Returns float32[bord_off[-1]]."""
+        """Border densities (W2C:951-961): labels int32[n] (-1 or 1..NCLUST; None: what assign() left on the device),
+        bord_off[G+1] (NCLUST + 1 slots per group, none where NCLUST <= 1).  Returns float32[bord_off[-1]]."""
         torch = _torch()
         e = self.engine
         bo = np.ascontiguousarray(bord_off, dtype=np.uint32)
         nb = int(bo[-1])
-        lab = torch.from_numpy(np.ascontiguousarray(labels if self.n else np.zeros(1), dtype=np.int32)).to(e.device)
+        if labels is None:
+            if self.label_d is None:
+                raise ValueError("border(None, ...) needs assign() first")
+            lab = self.label_d
+        else:
+            lab = torch.from_numpy(np.ascontiguousarray(labels if self.n else np.zeros(1), dtype=np.int32)).to(e.device)
         bord = torch.empty(max(nb, 1), dtype=torch.float32, device=e.device)
         check(e._lib.mrg_trf_border(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),
                                     self.span.data_ptr(), self.rho_d.data_ptr(), lab.data_ptr(),
                                     bo.ctypes.data_as(C.POINTER(C.c_uint32)), bord.data_ptr(), e._stream_ptr()))
+        self.bord_d, self.bord_off = bord, bo
         return bord.cpu().numpy()[:nb]
+
+    def halo(self, counts=None):
+        """Core / halo of every row and the tallies of every cluster (mrg_trf_halo), after assign() and border(None, ...).
+        counts: the read count of every row (uint32[n]; None: the rows that Engine.trf_sample_groups left on the device).
+        Returns (core uint8[n], order uint32[n]: the rows by (group, cluster; label -1 last), a cluster's members in row
+        order; tallies uint64[cen_off[-1], 4]: members, core rows, read count in the core, read count in the halo)."""
+        torch = _torch()
+        e = self.engine
+        if self.label_d is None or self.bord_d is None:
+            raise ValueError("halo() needs assign() and border() first")
+        if counts is None:
+            if self.counts_d is None:
+                raise ValueError("halo() needs the read counts of the rows")
+            cnt = self.counts_d
+        else:
+            cnt = torch.from_numpy(np.ascontiguousarray(counts if self.n else np.zeros(1), dtype=np.uint32).view(np.int32)).to(e.device)
+        core = torch.zeros(max(self.n, 1), dtype=torch.uint8, device=e.device)
+        order = torch.zeros(max(self.n, 1), dtype=torch.int32, device=e.device)
+        tallies = np.zeros((len(self.centers), 4), dtype=np.uint64)
+        if self.G:
+            check(e._lib.mrg_trf_halo(e._h, self.off_c, self.G, self.max_len, self.codes.data_ptr(), self.nmask_ptr(),
+                                      self.span.data_ptr(), self.rho_d.data_ptr(), self.label_d.data_ptr(), cnt.data_ptr(),
+                                      int(cnt.stride(0)), self.cen_off.ctypes.data, self.centers.ctypes.data,
+                                      self.bord_off.ctypes.data, self.bord_d.data_ptr(), core.data_ptr(), order.data_ptr(),
+                                      tallies.ctypes.data, e._stream_ptr()))
+        return core.cpu().numpy()[:self.n], order.cpu().numpy()[:self.n].view(np.uint32), tallies
 
 
 def unpack_assignments(packed):

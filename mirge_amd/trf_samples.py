@@ -526,8 +526,59 @@ def write_trf_sample_reports(tdir, sampleList, st, et, g, rec, words, lens, nmas
         rows.ctypes.data, rows.shape[0]))
 
 
+def write_trf_cluster_reports(tdir, sampleList, g, names, group_len, group_sample, stru, pretrnaNameSeqDic, labels, core, order,
+                              nclust, cen_off, centers, tallies):
+    """<sample>.potential_tRFs.clusters.detail and .tRFs.report.tsv of every sample from the downloaded layout of the `groups`
+    backend and the arrays of assign() / halo(), by the native writer (mrg_write_trf_cluster_reports): the files
+    _write_clusters gives.  names[k] = the name group k is paired with.  Names and templates are resolved per group here;
+    a lookup the record route would miss raises its KeyError before a file is written."""
+    import ctypes as C
+
+    from . import _native
+    lib = _native.load()
+    G, n = len(names), int(g.off[-1])
+    max_len = max(int(g.max_len), 1)
+    W = (max_len + 31) // 32
+    if n:
+        codes = np.ascontiguousarray(g.codes, dtype=np.uint64).reshape(W, -1)
+        nm = None if g.nmask is None else np.ascontiguousarray(g.nmask, dtype=np.uint64).reshape(W, -1)
+        span, rpm = np.ascontiguousarray(g.span, dtype=np.uint16), np.ascontiguousarray(g.rpm, dtype=np.float64)
+        rows = np.ascontiguousarray(g.rows, dtype=np.uint32).reshape(-1, 3)
+    else:
+        codes, nm, span, rpm, rows = np.zeros((W, 1), np.uint64), None, np.zeros(1, np.uint16), np.zeros(1), np.zeros((1, 3), np.uint32)
+    off = np.ascontiguousarray(g.off, dtype=np.uint32)
+    per_name = {}
+    for name in set(names):
+        per_name[name] = ("_".join(name.split("_")[1:-1]) if "pre" in name else name,
+                          stru[name]["seq"] if name in stru else None, pretrnaNameSeqDic.get(name))
+
+    def strings(items):
+        return (C.c_char_p * max(len(items), 1))(*[None if x is None else x.encode() for x in items])
+    arrays = [np.ascontiguousarray(x, dtype=dt) for x, dt in
+              ((group_sample, np.int32), (group_len, np.int32), (labels, np.int32), (core, np.uint8), (order, np.uint32),
+               (nclust, np.uint32), (cen_off, np.uint32), (centers, np.uint32), (tallies, np.uint64))]
+    gs, gl, lab, co, order, nclust, cen_off, centers, tallies = arrays
+    if not (len(gs) == len(gl) == len(nclust) == G == len(off) - 1 == len(cen_off) - 1 and len(lab) == len(co) == len(order) == n
+            and len(centers) == int(cen_off[-1]) and tallies.size == 4 * len(centers) and len(span) >= n and len(rpm) >= n
+            and rows.shape[0] >= n and codes.shape[1] >= n):
+        raise ValueError("write_trf_cluster_reports: the arrays do not match the groups")
+    paths = (C.c_char_p * (2 * len(sampleList)))(*[os.fsencode(os.path.join(tdir, s + suffix)) for s in sampleList
+                                                    for suffix in (".potential_tRFs.clusters.detail", ".tRFs.report.tsv")])
+    status = np.zeros(2, dtype=np.int64)
+    _native.check(lib.mrg_write_trf_cluster_reports(
+        paths, len(sampleList), codes.ctypes.data, None if nm is None else nm.ctypes.data, max_len, codes.shape[1],
+        span.ctypes.data, rpm.ctypes.data, rows.ctypes.data, n, off.ctypes.data, G, gs.ctypes.data, gl.ctypes.data,
+        strings(names), strings([per_name[x][0] for x in names]), strings([per_name[x][1] for x in names]),
+        strings([per_name[x][2] for x in names]), lab.ctypes.data, co.ctypes.data, order.ctypes.data, nclust.ctypes.data,
+        cen_off.ctypes.data, centers.ctypes.data, tallies.ctypes.data, status.ctypes.data))
+    if status[0] == 1:
+        raise KeyError(names[int(status[1])])
+    if status[0] == 2:
+        raise IndexError("string index out of range")
+
+
 def write_trf_samples_arrays(outputdir, sampleList, et, st, rec, words, lens, nmask, quant, denom, tables, pretrnaNameSeqDic,
-                             groups, peaks, timings=None, device_rank=False):
+                             groups, peaks, timings=None, device_rank=False, device_labels=False):
     """write_trf_samples from the arrays: the four files of every sample under <outputdir>/tRFs.samples.tmp/, byte for
     byte, without a Python object per read.  et / st = trf.entry_tables / trf.sample_tables; rec = the rows of
     Engine.trf_classify in the order of the tsv (columnar.write_trf_tables returns them); words / lens / nmask /
@@ -535,8 +586,11 @@ def write_trf_samples_arrays(outputdir, sampleList, et, st, rec, words, lens, nm
     nmask, quant, denom, timings=)` is the block backend (engine_groups(engine) on the GPU, tests/trf_groups_model.py
     in the CPU tests), `peaks(groups' result, ktab)` the density-peak backend (engine_peaks_groups(engine), or
     layout_peaks(fn) around a backend of write_trf_samples); device_rank: take the rank order from that backend's
-    rank() (mrg_trf_rank) instead of the host argsort.  The two report files are written natively; the label
-    pass of the peaks, .clusters.detail and .tRFs.report.tsv still walk the groups here, on ArrayGroup."""
+    rank() (mrg_trf_rank) instead of the host argsort.  The two report files are written natively.  device_labels: the
+    centres, labels and halos come from that backend too (rank(), min_distance(None), assign(), border(None, bord_off),
+    halo(): mrg_trf_assign / mrg_trf_halo on the GPU) and .clusters.detail / .tRFs.report.tsv from the native writer
+    (mrg_write_trf_cluster_reports), with no Python per row or cluster; without it the label pass of the peaks and those
+    two files walk the groups here, on ArrayGroup."""
     import time
     stru = tables["trnaStruDic"]
     rec = np.asarray(rec).reshape(-1, 12)
@@ -554,13 +608,43 @@ def write_trf_samples_arrays(outputdir, sampleList, et, st, rec, words, lens, nm
     t2 = time.perf_counter()
     off = np.asarray(g.off, dtype=np.uint32)
     n_groups = len(off) - 1
+    blocks, pairs = np.asarray(g.blocks).reshape(-1, 6), np.asarray(g.groups).reshape(-1, 2)
+    if device_labels:
+        entries = np.asarray(st.entries)
+        nclust, cen_off, centers = np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
+        labels, core, order, tallies = np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros((0, 4), np.uint64)
+        if n_groups:
+            state = peaks(g, gaussian_table())
+            state.rank()
+            state.min_distance(None)
+            nclust, cen_off, centers = state.assign()
+            slots = np.where(np.asarray(nclust) > 1, np.asarray(nclust).astype(np.uint64) + 1, 0)
+            bord_off = np.zeros(n_groups + 1, dtype=np.uint32)
+            bord_off[1:] = np.cumsum(slots, dtype=np.uint64)
+            state.border(None, bord_off)
+            # (the read counts: the backend's own device copy where it has one)
+            core, order, tallies = state.halo(None if getattr(state, "counts_d", None) is not None
+                                              else np.asarray(g.rows).reshape(-1, 3)[:, 1])
+            labels = state.labels()
+        t3 = time.perf_counter()
+        if n_groups:
+            own, paired = blocks[pairs[:, 0]], blocks[pairs[:, 1]]
+            names = [et.names[e] for e in paired[:, 1].tolist()]
+            group_len, group_sample = entries[own[:, 1], 1], own[:, 0]
+        else:
+            names, group_len, group_sample = [], np.zeros(0, np.int32), np.zeros(0, np.int32)
+        write_trf_cluster_reports(tdir, sampleList, g, names, group_len, group_sample, stru, pretrnaNameSeqDic, labels, core, order,
+                                  nclust, cen_off, centers, tallies)
+        if timings is not None:
+            t4 = time.perf_counter()
+            timings.update(groups_s=t1 - t0, reports_s=t2 - t1, peaks_s=t3 - t2, clusters_s=t4 - t3)
+        return tdir
     if n_groups:
         state = peaks(g, gaussian_table())
         res = peaks_results(off, state, device_rank=device_rank)
     else:
         res = []
     t3 = time.perf_counter()
-    blocks, pairs = np.asarray(g.blocks).reshape(-1, 6), np.asarray(g.groups).reshape(-1, 2)
     if n_groups:
         codes, nm, span, rpm, rows = g.codes, g.nmask, g.span, g.rpm, np.asarray(g.rows).reshape(-1, 3)
     group_sample = blocks[pairs[:, 0], 0] if n_groups else np.zeros(0, dtype=np.int32)

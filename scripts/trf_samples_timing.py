@@ -12,7 +12,8 @@ download, `reports_s` the native writer, `peaks_s` the three density-peak passes
 `clusters_s` .clusters.detail and .tRFs.report.tsv in Python); device events around the counting and the filling call and,
 inside the filling call, around its four stages.  Every file of tRFs.samples.tmp/ is compared byte for byte between the
 routes.  Writes one JSON object to --json (default profiles/trf_samples_timing.json) and prints it; `passed` = equal files
-and the slowest run of (b) not slower than the fastest run of (a).  Needs a GPU."""
+and the slowest run of (b) not slower than the fastest run of (a).  --labels: see labels_leg (writes
+profiles/trf_samples_timing_labels.json).  Needs a GPU."""
 import argparse
 import json
 import os
@@ -39,7 +40,7 @@ def parent_route(w, et, t_rec, eng, outdir, sample_list, denom):
     return dict(content_from_rows_s=t1 - t0, write_trf_samples_s=t2 - t1, total_s=t2 - t0)
 
 
-def array_route(w, dev, et, t_rec, eng, outdir, sample_list, denom):
+def array_route(w, dev, et, t_rec, eng, outdir, sample_list, denom, device_labels=False):
     import torch
     from mirge_amd import trf, trf_samples
     torch.cuda.synchronize()
@@ -49,9 +50,71 @@ def array_route(w, dev, et, t_rec, eng, outdir, sample_list, denom):
     timings = {}
     trf_samples.write_trf_samples_arrays(outdir, sample_list, et, st, t_rec, w["words"], w["lens"], None, w["quant"], denom,
                                          w["tables"], w["pre"], trf_samples.engine_groups(eng, dev),
-                                         trf_samples.engine_peaks_groups(eng), timings=timings, device_rank=True)
+                                         trf_samples.engine_peaks_groups(eng), timings=timings, device_rank=True,
+                                         device_labels=device_labels)
     t2 = time.time()
     return dict(sample_tables_s=t1 - t0, total_s=t2 - t0, **{k: float(v) for k, v in timings.items()})
+
+
+def labels_leg(args, w, on_device, et, t_rec, eng, d, sample_list, denom):
+    """--labels: the array route with the label pass and the two cluster files in Python (device_labels=False, the parent's)
+    against the same route with mrg_trf_assign / mrg_trf_halo / mrg_write_trf_cluster_reports (device_labels=True): --runs
+    runs of each, alternating, after a warm-up of both; `peaks_s + clusters_s` of every run, the medians, device events around
+    the new calls, and all files compared byte for byte.  The world's reads are random and its RP100K small: as it is, no group
+    has a cluster (`clusters` = 0); --denom-div raises the RP100K of both routes alike until there are."""
+    import torch
+    from mirge_amd import trf, trf_samples
+    dirs = {False: os.path.join(d, "labels_off"), True: os.path.join(d, "labels_on")}
+    for flag in (False, True):
+        os.mkdir(dirs[flag])
+        array_route(w, on_device, et, t_rec, eng, dirs[flag], sample_list, denom, flag)      # warm-up
+    out = dict(what="annotate -trf: peaks_s + clusters_s of the array route, labels and cluster files in Python (parent) or from "
+                    "the arrays (device_labels)", reads=args.reads, trnas=args.trnas, samples=args.samples, denom_div=args.denom_div, parent=[], device_labels=[],
+               command="python scripts/trf_samples_timing.py " + " ".join(sys.argv[1:]))
+    for run in range(args.runs):
+        for flag, key in ((False, "parent"), (True, "device_labels")):
+            r = array_route(w, on_device, et, t_rec, eng, dirs[flag], sample_list, denom, flag)
+            r["peaks_plus_clusters_s"] = r["peaks_s"] + r["clusters_s"]
+            out[key].append(r)
+            print("run %d %s: peaks %.3f s + clusters %.3f s" % (run, key, r["peaks_s"], r["clusters_s"]), flush=True)
+    ta, tb = (os.path.join(dirs[f], "tRFs.samples.tmp") for f in (False, True))
+    names = sorted(os.listdir(ta))
+    same = names == sorted(os.listdir(tb)) and len(names) == 4 * args.samples
+    for fn in names:
+        same = same and open(os.path.join(ta, fn), "rb").read() == open(os.path.join(tb, fn), "rb").read()
+    assert same, "the files of the two routes differ"
+    # the new device calls alone, between events
+    g = eng.trf_sample_groups(trf.sample_tables(et, w["tables"], w["pre"]), t_rec, *on_device, denom)
+    state = eng.trf_peaks_groups(g, trf_samples.gaussian_table())
+    state.rank()
+    state.min_distance(None)
+    ms = {}
+
+    def timed(key, fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = fn()
+        e1.record()
+        e1.synchronize()
+        ms.setdefault(key, []).append(e0.elapsed_time(e1))
+        return res
+    for _ in range(args.runs + 1):
+        nclust = timed("assign_ms", state.assign)[0]
+        bord_off = np.zeros(len(nclust) + 1, dtype=np.uint32)
+        bord_off[1:] = np.cumsum(np.where(nclust > 1, nclust.astype(np.uint64) + 1, 0))
+        timed("border_ms", lambda: state.border(None, bord_off))
+        timed("halo_ms", lambda: state.halo())
+    med = lambda v: float(np.median(v))
+    out.update(files_equal=bool(same), groups=int(g.G), rows=int(g.n), clusters=int(len(state.centers)),
+               device_calls_ms={k: [round(x, 3) for x in v[1:]] for k, v in ms.items()},
+               parent_median_s=med([r["peaks_plus_clusters_s"] for r in out["parent"]]),
+               device_labels_median_s=med([r["peaks_plus_clusters_s"] for r in out["device_labels"]]))
+    out["passed"] = bool(same and out["device_labels_median_s"] < out["parent_median_s"])
+    text = json.dumps(out)
+    with open(args.json, "w") as fh:
+        fh.write(text + "\n")
+    print(text)
+    return 0 if out["passed"] else 1
 
 
 def main():
@@ -60,8 +123,13 @@ def main():
     ap.add_argument("--trnas", type=int, default=4000)
     ap.add_argument("--samples", type=int, default=2)
     ap.add_argument("--runs", type=int, default=3)
-    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "trf_samples_timing.json"))
+    ap.add_argument("--labels", action="store_true", help="time the label pass and the cluster files: Python against the arrays")
+    ap.add_argument("--denom-div", type=int, default=1, help="with --labels: divide the RP100K denominators, so that the random "
+                    "reads of the world reach the density of cluster centres (rho >= 5); 1 = the world as it is, without cluster")
+    ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.json is None:
+        args.json = os.path.join(ROOT, "profiles", "trf_samples_timing_labels.json" if args.labels else "trf_samples_timing.json")
     import torch
     from trf_tables_timing import synthesize
     from mirge_amd import columnar, trf
@@ -88,6 +156,9 @@ def main():
         rec, hits, n2, _ = eng.trf_classify(et, dev["words"], dev["lens"], None, dev["pass_id"])
         t_rec, _ = columnar.write_trf_tables(d, sample_list, w["log_dic"], w["words"], w["lens"], None, w["quant"], rec, hits, n2, et)
         on_device = (dev["words"], dev["lens"], None, dev["quant"])
+        if args.labels:
+            denom = [max(1, x // args.denom_div) for x in denom]
+            return labels_leg(args, w, on_device, et, t_rec, eng, d, sample_list, denom)
         array_route(w, on_device, et, t_rec, eng, b_dir, sample_list, denom)    # warm-up: code objects
         print("warm-up done", flush=True)
         for run in range(args.runs):
