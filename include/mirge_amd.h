@@ -1128,6 +1128,49 @@ int mrg_write_trf_sample_reports(const char *const *paths, uint32_t n_samples, c
                                  uint64_t n_blocks, const uint32_t *rows, uint64_t n_rows);
 
 /*
+ * `annotate -tcf`: <sample>.trim.collapse.fa from the arrays.  The file holds every distinct read of the sample as
+ * ">seq<i>_<count>\n<sequence>\n", i = 1.., by count and then by sequence, both descending (quantReads.py:26-44:
+ * sorted((count, seq)) reversed); the sequence compares as a Python string: A < C < G < N < T, a proper prefix first.
+ * DESIGN.md 8.9 holds the argument.
+ *
+ * mrg_collapsed_order_temp_bytes  HOST: the bytes of device scratch mrg_seq_rank (*rank_bytes) and mrg_collapsed_order
+ *                       (*order_bytes) need for n reads (n < 2^31).
+ * mrg_seq_rank          DEVICE arrays: the reads [W][stride] (W in {1, 2, 4, 8}), d_lens, d_nmask or NULL.  d_rank[u] = the
+ *                       position of read u among the n reads in ascending string order (equal reads in either order: the
+ *                       ranks are a permutation of 0 .. n - 1 all the same).  max_len <= min(255, 32 W) bounds the lengths:
+ *                       a longer read is MRG_ERR_ARG (found on the device; d_rank is then undefined).  Stable radix sorts of
+ *                       (key, read) over ceil(max_len / 21) chunks of 21 bases, the last chunk first (at least one), each
+ *                       over the 3 x (bases of the chunk below max_len) bits it can occupy: 3 bits per base, end of read 0,
+ *                       A 1, C 2, G 3, N 4, T 5, first base highest.  The number of launches depends on max_len and n only.
+ *                       Bits of the words and of the mask at and beyond a read's length are not looked at.  n == 0 and null
+ *                       pointers are MRG_ERR_ARG.  d_tmp: *rank_bytes bytes, 8-byte aligned.  Synchronises `stream`.
+ * mrg_collapsed_order   DEVICE: d_quant [n][n_samples], d_rank of mrg_seq_rank.  d_order[j], j < *rows, = the read at line
+ *                       pair j of sample `sample`: the reads with a count there by (count, rank) descending; *rows (HOST) =
+ *                       their number, also when cap < *rows, which is MRG_ERR_ARG and writes no row.  Flags, exclusive prefix
+ *                       sum, scatter of count << bits(n - 1) | rank, one radix sort over those bits and the bits of the
+ *                       column's largest count (any uint32), delivered backwards.  n == 0, n_samples == 0, sample >=
+ *                       n_samples and null pointers are MRG_ERR_ARG.  d_tmp: *order_bytes bytes, 8-byte aligned.
+ *                       Synchronises `stream`.
+ * mrg_write_collapsed_fasta  HOST arrays: the reads, lens, nmask or NULL, quant, and order [k] as above; extra rows
+ *                       (extra_seqs[e], extra_counts[e]), e < n_extra, by (count, sequence) descending: the reads beyond 255 nt,
+ *                       which the packed arrays do not hold, merged in by the same comparison.  Returns the rows written (k +
+ *                       n_extra), or a negative error: order and the extra rows are checked before the file is opened, and an
+ *                       entry >= n, a read without a count in the sample, an extra row without a count or out of order is
+ *                       MRG_ERR_ARG and writes nothing.
+ */
+int mrg_collapsed_order_temp_bytes(uint64_t n, uint64_t *rank_bytes, uint64_t *order_bytes);
+int mrg_seq_rank(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                 const uint64_t *d_nmask, uint64_t n, uint32_t max_len, uint32_t *d_rank, void *d_tmp, uint64_t tmp_bytes,
+                 void *stream);
+int mrg_collapsed_order(mrg_ctx *ctx, const uint32_t *d_quant, uint64_t n, uint32_t n_samples, uint32_t sample,
+                        const uint32_t *d_rank, uint32_t *d_order, uint64_t cap, uint64_t *rows, void *d_tmp, uint64_t tmp_bytes,
+                        void *stream);
+int64_t mrg_write_collapsed_fasta(const char *path, const uint64_t *reads, uint32_t words_per_read, uint64_t stride,
+                                  const uint8_t *lens, const uint64_t *nmask, uint64_t n, const uint32_t *quant,
+                                  uint32_t n_samples, uint32_t sample, const uint32_t *order, uint64_t k,
+                                  const char *const *extra_seqs, const uint64_t *extra_counts, uint64_t n_extra);
+
+/*
  * `annotate -ai`: every read claimed by the exact-miRNA or the isomiR pass aligned to the canonical sequence of its (merged)
  * miRNA, and a2IEditing.detail.txt, from the arrays.  mirge_amd/a2i.py holds the Python model (local_pair, judge_align,
  * a2i_editing) whose results the two calls reproduce exactly; DESIGN.md 8.6 holds the argument.

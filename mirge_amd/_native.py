@@ -262,6 +262,14 @@ SIGNATURES = {
                                                C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                                C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_uint64, C.c_void_p, C.c_uint64]),
+    "mrg_collapsed_order_temp_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mrg_seq_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                               C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_collapsed_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_write_collapsed_fasta": (C.c_int64, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                              C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64]),
     "mrg_pack_reads": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "mrg_trf_rho": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -45,6 +45,9 @@ def build_parser():
     p.add_argument("-phred64", action="store_true")
     p.add_argument("-spikeIn", dest="spikeIn", action="store_true")
     p.add_argument("-tcf", dest="trimmed_collapsed_fa", action="store_true")
+    p.add_argument("--tcf-host", dest="tcf_host", action="store_true",
+                   help="extension: the -tcf files through a Python object per read and the host sort instead of the GPU "
+                        "order and the native writer (same files)")
     p.add_argument("-di", dest="diff_isomirs", action="store_true")
     p.add_argument("-cpu", dest="cpu", metavar="<int>", default="1")
     p.add_argument("-ai", dest="a_to_i", action="store_true")
@@ -445,17 +448,16 @@ def annotate_main(args, engine_factory=None, materialize=False):
     npp = columnar.names_by_pass(engine, spike)
 
     if args.trimmed_collapsed_fa:  # QNT:26-44: per sample, by count then sequence, descending
-        from . import pack
-        for i, name in enumerate(sample_list):
-            idx = np.nonzero(h_quant[:, i])[0]
-            seqs = pack.unpack_reads(np.ascontiguousarray(h_words[:, idx]), h_lens[idx],
-                                     None if h_nmask is None else np.ascontiguousarray(h_nmask[:, idx]))
-            rows = sorted(zip(h_quant[idx, i].tolist(), seqs), reverse=True)
-            rows += sorted(((q[i], s) for s, q in long_counts.items() if q[i]), reverse=True)
-            rows.sort(reverse=True)
-            with open(os.path.join(outdir, os.path.splitext(name)[0] + ".trim.collapse.fa"), "w") as fh:
-                for k, (c, s) in enumerate(rows):
-                    fh.write(">seq%d_%d\n%s\n" % (k + 1, c, s))
+        # ordered on the GPU and written from the arrays (Engine.collapsed_order, columnar.write_collapsed_fa; the reads beyond
+        # 255 nt are merged in by the writer) unless the engine has no such call, or --tcf-host asks for the per-read route
+        if hasattr(engine, "collapsed_order") and not args.tcf_host:
+            if world > 1 or shard.quant is None:   # (the gathered host arrays)
+                orders = engine.collapsed_order(h_words, h_lens, h_nmask, h_quant)
+            else:
+                orders = engine.collapsed_order(shard.words, shard.lens, shard.nmask, shard.quant)
+            columnar.write_collapsed_fa(outdir, sample_list, h_words, h_lens, h_nmask, h_quant, orders, long_counts)
+        else:
+            report.write_collapsed_fa_host(outdir, sample_list, h_words, h_lens, h_nmask, h_quant, long_counts)
 
     report.write_annotation_report_csv(os.path.join(outdir, "annotation.report.csv"), sample_list, log_dic, spike)
     columnar.write_read_tables(outdir, names, sample_list, h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, npp,

@@ -18,6 +18,8 @@ downstream consumers actually look at are turned into the reference's shapes:
   write_isomir_gff     the per-sample GFF files from the rows of Engine.isomir_classify (W2C:621-646;
                        mrg_write_isomir_gff)
   write_trf_tables     the four tRF tables from the rows of Engine.trf_classify (W2C:648-800; mrg_write_trf_tables)
+  write_collapsed_fa   <sample>.trim.collapse.fa from the orders of Engine.collapsed_order (QNT:26-44;
+                       mrg_write_collapsed_fasta)
   mirna_read_subset    the miRNA-claimed subset, optionally only what the -ai grouping keeps
   full_seq_dic         everything as the reference's seqDic (small inputs, tests)
 """
@@ -264,6 +266,34 @@ def write_trf_tables(outdir, sample_list, log_dic, words, lens, nmask, quant, re
         strings(et.names), strings(et.aa_types), strings(et.anticodons), desc.shape[0], clusters.ctypes.data, clusters.shape[0],
         strings(et.merged_list), len(et.merged_list), C.byref(rows)))
     return rec, int(rows.value)
+
+
+def write_collapsed_fa(outdir, sample_list, words, lens, nmask, quant, orders, long_counts=None):
+    """<sample>.trim.collapse.fa of every sample (QNT:26-44) from the arrays and the orders of Engine.collapsed_order, by the
+    native writer (mrg_write_collapsed_fasta): the files report.write_collapsed_fa_host writes, byte for byte.  long_counts:
+    {sequence: counts per sample} of the reads beyond 255 nt, which the packed arrays do not hold; the writer merges them in.
+    Returns the rows written per sample."""
+    lib = _native.load()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    quant = np.ascontiguousarray(quant, dtype=np.uint32)
+    S = quant.shape[1] if quant.ndim == 2 else 1
+    rows = []
+    for i, name in enumerate(sample_list):
+        order = np.ascontiguousarray(orders[i], dtype=np.uint32)
+        extra = sorted(((int(q[i]), s) for s, q in (long_counts or {}).items() if q[i]), reverse=True)
+        seqs = (C.c_char_p * max(len(extra), 1))(*[s.encode("ascii") for _, s in extra])
+        counts = np.array([c for c, _ in extra], dtype=np.uint64)
+        got = lib.mrg_write_collapsed_fasta(
+            os.fsencode(os.path.join(outdir, os.path.splitext(name)[0] + ".trim.collapse.fa")), words.ctypes.data, W, n,
+            lens.ctypes.data, None if nm is None else nm.ctypes.data, n, quant.ctypes.data, S, i, order.ctypes.data,
+            order.shape[0], seqs, counts.ctypes.data, len(extra))
+        if got < 0:
+            check(int(got))
+        rows.append(int(got))
+    return rows
 
 
 def mirna_read_subset(engine, cols, words, lens, nmask, quant, log_dic=None, spike_in=False, for_a2i=False):

@@ -23,6 +23,7 @@
 #include "fastq.hpp"
 #include "fm_index.hpp"
 #include "a2i_align.hpp"
+#include "collapsed_order.hpp"
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
@@ -4133,6 +4134,150 @@ int mrg_write_trf_sample_reports(const char* const* paths, uint32_t n_samples, c
                                     entry_names, templates, aa_types, n_entries, n_names, blocks, block_sums, n_blocks, rows, n_rows};
     mrg::write_trf_sample_reports(a);
     return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+// ------------------------------------------------------------- -tcf (csrc/collapsed_order.hip)
+extern "C++" {
+namespace {
+
+struct SeqScratch {  // the caller's scratch, carved into 256-byte aligned pieces
+  uint64_t k0, k1, v0, v1, flags, scan, sort, stat, total;
+  // with_flags: the flags of a sample column and their scan (mrg_collapsed_order)
+  SeqScratch(uint64_t n, bool with_flags) {
+    uint64_t used = 0;
+    auto reserve = [&](uint64_t bytes) {
+      const uint64_t at = used;
+      used += (std::max<uint64_t>(bytes, 1) + 255) & ~255ull;
+      return at;
+    };
+    k0 = reserve(n * sizeof(uint64_t));
+    k1 = reserve(n * sizeof(uint64_t));
+    v0 = reserve(n * sizeof(uint32_t));
+    v1 = reserve(n * sizeof(uint32_t));
+    flags = with_flags ? reserve((n + 1) * sizeof(uint32_t)) : 0;
+    scan = with_flags ? reserve(mrg::prims::scan_temp_bytes(n + 1)) : 0;
+    sort = reserve(mrg::prims::radix_temp_bytes(n));
+    stat = reserve(mrg::kSeqStatWords * sizeof(uint32_t));
+    total = used;
+  }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int mrg_collapsed_order_temp_bytes(uint64_t n, uint64_t* rank_bytes, uint64_t* order_bytes) {
+  if (!rank_bytes || !order_bytes) return fail(MRG_ERR_ARG, "mrg_collapsed_order_temp_bytes: null argument");
+  if (n >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_collapsed_order_temp_bytes: %llu reads; the limit is 2^31 - 1", (unsigned long long)n);
+  *rank_bytes = SeqScratch(n, false).total;
+  *order_bytes = SeqScratch(n, true).total;
+  return MRG_OK;
+}
+
+int mrg_seq_rank(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                 const uint64_t* d_nmask, uint64_t n, uint32_t max_len, uint32_t* d_rank, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_seq_rank";
+  if (!ctx || !d_reads || !d_lens || !d_rank || !d_tmp) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n == 0) return fail(MRG_ERR_ARG, "%s: no reads", fn);
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "%s: words_per_read must be 1, 2, 4 or 8", fn);
+  if (stride < n || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: bad stride / n", fn);
+  if (max_len > 255 || max_len > 32 * words_per_read)
+    return fail(MRG_ERR_ARG, "%s: max_len %u: at most 255 and what %u words hold", fn, max_len, words_per_read);
+  const SeqScratch sc((uint64_t)n, false);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_collapsed_order_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)d_tmp;
+  uint64_t* keys[2] = {(uint64_t*)(base + sc.k0), (uint64_t*)(base + sc.k1)};
+  uint32_t* vals[2] = {(uint32_t*)(base + sc.v0), (uint32_t*)(base + sc.v1)};
+  uint32_t* stat = (uint32_t*)(base + sc.stat);
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kSeqStatWords * sizeof(uint32_t), st));
+  mrg::SeqRankParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.stride = stride;
+  p.n = (uint32_t)n;
+  p.W = words_per_read;
+  p.max_len = max_len;
+  // stable sorts by 21-base chunks, the last chunk first: as many launches as max_len asks for, whatever the reads hold
+  const uint32_t chunks = std::max(1u, (max_len + mrg::kSeqChunkBases - 1) / mrg::kSeqChunkBases);
+  int cur = 0;
+  HIP_TRY(mrg::seq_iota_launch(vals[cur], p.n, st));
+  for (uint32_t c = chunks; c-- > 0;) {
+    const uint32_t width = std::min(mrg::kSeqChunkBases, max_len - mrg::kSeqChunkBases * c);
+    HIP_TRY(mrg::seq_chunk_keys_launch(p, vals[cur], c, keys[cur], stat, st));
+    bool second = false;
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[cur], keys[cur ^ 1], vals[cur], vals[cur ^ 1], p.n, 3 * width, base + sc.sort, st, &second));
+    if (second) cur ^= 1;
+  }
+  HIP_TRY(mrg::seq_rank_scatter_launch(vals[cur], p.n, d_rank, st));
+  uint32_t h_stat[mrg::kSeqStatWords] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_stat[mrg::kSeqStatTooLong]) return fail(MRG_ERR_ARG, "%s: a read is longer than max_len %u, or than its %u words hold", fn, max_len, words_per_read);
+  return MRG_OK;
+}
+
+int mrg_collapsed_order(mrg_ctx* ctx, const uint32_t* d_quant, uint64_t n, uint32_t n_samples, uint32_t sample, const uint32_t* d_rank,
+                        uint32_t* d_order, uint64_t cap, uint64_t* rows, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_collapsed_order";
+  if (!ctx || !d_quant || !d_rank || !rows || !d_tmp) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *rows = 0;
+  if (cap && !d_order) return fail(MRG_ERR_ARG, "%s: null output buffer", fn);
+  if (n == 0 || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: 1 .. 2^31 - 1 reads", fn);
+  if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
+  const SeqScratch sc(n, true);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_collapsed_order_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)d_tmp;
+  uint64_t *k0 = (uint64_t*)(base + sc.k0), *k1 = (uint64_t*)(base + sc.k1);
+  uint32_t *v0 = (uint32_t*)(base + sc.v0), *v1 = (uint32_t*)(base + sc.v1);
+  uint32_t *flags = (uint32_t*)(base + sc.flags), *stat = (uint32_t*)(base + sc.stat);
+  const uint32_t N = (uint32_t)n;
+  // ---- the reads of the sample: flag, exclusive sums, scatter
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kSeqStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::collapsed_flags_launch(d_quant, N, n_samples, sample, flags, stat, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, base + sc.scan, st));
+  uint32_t k = 0, h_stat[mrg::kSeqStatWords] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(&k, flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (k > N) return fail(MRG_ERR_HIP, "%s: %u rows of %u reads", fn, k, N);
+  *rows = k;
+  if (cap < k) return fail(MRG_ERR_ARG, "%s: %u rows do not fit a buffer of %llu", fn, k, (unsigned long long)cap);
+  if (k == 0) return MRG_OK;
+  // ---- count << rank_bits | rank ascending, delivered backwards: only the bits the largest count and n - 1 occupy
+  const uint32_t rank_bits = bits_for(n - 1), count_bits = bits_for(h_stat[mrg::kSeqStatMaxCount]);
+  HIP_TRY(mrg::collapsed_keys_launch(flags, d_quant, N, n_samples, sample, d_rank, rank_bits, k0, v0, st));
+  bool second = false;
+  HIP_TRY(mrg::prims::radix_sort_pairs_u64(k0, k1, v0, v1, k, rank_bits + count_bits, base + sc.sort, st, &second));
+  HIP_TRY(mrg::collapsed_reverse_launch(second ? v1 : v0, k, d_order, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+int64_t mrg_write_collapsed_fasta(const char* path, const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens,
+                                  const uint64_t* nmask, uint64_t n, const uint32_t* quant, uint32_t n_samples, uint32_t sample,
+                                  const uint32_t* order, uint64_t k, const char* const* extra_seqs, const uint64_t* extra_counts,
+                                  uint64_t n_extra) {
+  const char* fn = "mrg_write_collapsed_fasta";
+  if (!path) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (k && (!reads || !lens || !quant || !order)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_extra && (!extra_seqs || !extra_counts)) return fail(MRG_ERR_ARG, "%s: null extra rows", fn);
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
+  if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
+  try {
+    const mrg::CollapsedFaArgs a{path, reads, words_per_read, stride, lens, nmask, n, quant, n_samples, sample, order, k,
+                                 extra_seqs, extra_counts, n_extra};
+    return (int64_t)mrg::write_collapsed_fasta(a);
   } catch (const std::invalid_argument& e) {
     return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
   } catch (const std::exception& e) {

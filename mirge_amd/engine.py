@@ -809,6 +809,80 @@ class Engine:
         g.rows = rows_d.cpu().numpy()[:R].view(np.uint32)
         return g
 
+    def seq_rank(self, words, lens, nmask, max_len=None):
+        """rank[u] = the position of packed read u in ascending Python string order (mrg_seq_rank): a device uint32 tensor
+        (int32 storage).  words [W, n] / lens / nmask (or None): device tensors or host arrays (uploaded), n >= 1.
+        max_len: a bound on the lengths (None: the longest read, read back from the device)."""
+        torch = _torch()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        W, n = int(words.shape[0]), int(words.shape[1])
+        if int(lens.shape[0]) != n or (nmask is not None and tuple(nmask.shape) != (W, n)):
+            raise ValueError("seq_rank: words [W, n], lens [n] and nmask [W, n] must match")
+        if max_len is None:
+            max_len = int(lens.max()) if n else 0
+        need = (C.c_uint64(), C.c_uint64())
+        check(self._lib.mrg_collapsed_order_temp_bytes(n, C.byref(need[0]), C.byref(need[1])))
+        tmp = torch.empty(int(need[0].value), dtype=torch.uint8, device=self.device)
+        rank = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        check(self._lib.mrg_seq_rank(self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(),
+                                     n, int(max_len), rank.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return rank[:n]
+
+    def _dev_reads(self, words, lens, nmask):
+        torch = _torch()
+
+        def dev(x, np_dtype, view=None):
+            if x is None or torch.is_tensor(x):
+                return x
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+        words = dev(words, np.uint64, np.int64).contiguous()
+        nmask = dev(nmask, np.uint64, np.int64)
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        return words, dev(lens, np.uint8).contiguous(), nmask
+
+    def collapsed_order(self, words, lens, nmask, quant, timings=None):
+        """The order of every sample's <sample>.trim.collapse.fa (mrg_seq_rank once, mrg_collapsed_order per sample column):
+        a list of S host uint32 arrays, order[s][k] = the read at line pair k of sample s -- the reads with quant[u, s] > 0 by
+        (count, sequence) descending, the sequence as a Python string.  words [W, n] / lens / nmask (or None) / quant [n, S]:
+        device tensors or host arrays (uploaded).  timings: a dict that receives `rank_ms` (the string rank, shared by the
+        samples) and `order_ms` (all the samples, their downloads included), between device events."""
+        torch = _torch()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        if not torch.is_tensor(quant):
+            quant = torch.from_numpy(np.ascontiguousarray(quant, dtype=np.uint32).view(np.int32)).to(self.device)
+        quant = quant.contiguous()
+        n = int(words.shape[1])
+        S = int(quant.shape[1]) if quant.dim() == 2 else 1
+        if int(quant.shape[0]) != n or int(lens.shape[0]) != n:
+            raise ValueError("collapsed_order: quant [n, S] and lens [n] must match the reads")
+        if timings is not None:
+            timings.update(rank_ms=0.0, order_ms=0.0)
+        if n == 0:
+            return [np.zeros(0, dtype=np.uint32) for _ in range(S)]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timings is not None else None
+        if ev:
+            ev[0].record()
+        rank = self.seq_rank(words, lens, nmask)
+        if ev:
+            ev[1].record()
+        need = (C.c_uint64(), C.c_uint64())
+        check(self._lib.mrg_collapsed_order_temp_bytes(n, C.byref(need[0]), C.byref(need[1])))
+        tmp = torch.empty(int(need[1].value), dtype=torch.uint8, device=self.device)
+        order = torch.empty(n, dtype=torch.int32, device=self.device)
+        rows = C.c_uint64(0)
+        out = []
+        for s in range(S):
+            check(self._lib.mrg_collapsed_order(self._h, quant.data_ptr(), n, S, s, rank.data_ptr(), order.data_ptr(), n,
+                                                C.byref(rows), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+            out.append(order[:int(rows.value)].cpu().numpy().view(np.uint32))
+        if ev:
+            ev[2].record()
+            ev[2].synchronize()
+            timings.update(rank_ms=ev[0].elapsed_time(ev[1]), order_ms=ev[1].elapsed_time(ev[2]))
+        return out
+
     def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
                    max_mm_total=2, timings=None):
         """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a

@@ -5,6 +5,7 @@
   isomirs.csv / isomirs.samples.csv (-di)   writeDataToCSV.py:582-619 (grouping),
                                             :1090-1170 (entropy), calcEntropy :344-351
   annotation.report.csv            generateReport.py:104-108, :191-200
+  <sample>.trim.collapse.fa (-tcf) quantReads.py:26-44 (the host route, `--tcf-host`)
 
 Host-side: these are M-sized or N-row text tables, streamed row by row (no dict
 copy), so they also work from the columnar arrays at 10^8 rows.
@@ -180,6 +181,24 @@ ANNOTATION_REPORT_HEADER = ("File name(s),Total Input Reads,Trimmed Reads(all),T
                             "All miRNA Reads,Filtered miRNA Reads,Unique miRNAs,Hairpin miRNAs,"
                             "mature tRNA Reads,primary tRNA Reads,snoRNA Reads,rRNA Reads,ncRNA others,"
                             "mRNA Reads,Remaining Reads\n")
+
+
+def write_collapsed_fa_host(outdir, sample_list, h_words, h_lens, h_nmask, h_quant, long_counts):
+    """<sample>.trim.collapse.fa of every sample (-tcf) on the host, a Python object per read: the statement of the files
+    (QNT:26-44: per sample, by count then sequence, descending) and the `--tcf-host` route.  The default route is
+    Engine.collapsed_order + columnar.write_collapsed_fa."""
+    import numpy as np
+    from . import pack
+    for i, name in enumerate(sample_list):
+        idx = np.nonzero(h_quant[:, i])[0]
+        seqs = pack.unpack_reads(np.ascontiguousarray(h_words[:, idx]), h_lens[idx],
+                                 None if h_nmask is None else np.ascontiguousarray(h_nmask[:, idx]))
+        rows = sorted(zip(h_quant[idx, i].tolist(), seqs), reverse=True)
+        rows += sorted(((q[i], s) for s, q in long_counts.items() if q[i]), reverse=True)
+        rows.sort(reverse=True)
+        with open(os.path.join(outdir, os.path.splitext(name)[0] + ".trim.collapse.fa"), "w") as fh:
+            for k, (c, s) in enumerate(rows):
+                fh.write(">seq%d_%d\n%s\n" % (k + 1, c, s))
 
 
 def write_annotation_report_csv(path, sampleList, logDic, spikeIn=False):
