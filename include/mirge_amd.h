@@ -1171,6 +1171,60 @@ int64_t mrg_write_collapsed_fasta(const char *path, const uint64_t *reads, uint3
                                   const char *const *extra_seqs, const uint64_t *extra_counts, uint64_t n_extra);
 
 /*
+ * Predict mode's candidate reads: what the reference's utils/convert2Fasta.py makes of unmapped.csv, from the arrays
+ * `annotate` holds.  With the reads in array order (the row order of unmapped.csv), total = the sum of a read's sample
+ * columns and len its length, the RAW list is the unmapped reads (pass_id < 0) with total >= 1, numbered 1, 2, .. in array
+ * order, and the FILTERED list those with min_len <= len <= max_len and total >= count_cutoff, numbered likewise.  The
+ * files hold ">mir<number>_<count>\n<sequence>\n" per row.  DESIGN.md 8.10 holds the rules.
+ *
+ * mrg_predict_reads_temp_bytes  HOST: the bytes of device scratch the three device calls need for n reads (n < 2^31).
+ * mrg_predict_select    DEVICE arrays: d_pass_id [n], d_lens [n], d_quant [n][n_samples].  d_total[u] = the read's total
+ *                       (every read, uint64); d_raw_no[u] / d_sel_no[u] = its number in the raw / filtered list, 0 when
+ *                       it is not in it; *n_raw, *n_sel (HOST) = the lengths of the lists.  One lane per read sums the
+ *                       columns of a row below 16 sample columns, 16 neighbouring lanes from 16 on; a flag pass, two
+ *                       exclusive prefix sums, a numbering pass.  n == 0 gives two empty lists.  n_samples == 0,
+ *                       min_len > max_len, count_cutoff == 0 and null pointers are MRG_ERR_ARG.  Synchronises `stream`.
+ * mrg_predict_sample_reads  DEVICE: one sample column and one list (d_no = d_raw_no with threshold 1, or d_sel_no with
+ *                       threshold count_cutoff): the reads u with d_no[u] != 0 and quant[u][sample] >= threshold in array
+ *                       order as rows (d_idx = u, d_num = d_no[u], d_cnt = quant[u][sample]); *rows (HOST) = their number,
+ *                       also when cap < *rows, which is MRG_ERR_ARG and writes no row.
+ * mrg_predict_gather    DEVICE: the reads d_idx[j], j < k, as a compact packed set: d_out_reads [W][k], d_out_lens [k],
+ *                       d_out_nmask [W][k] (or NULL; zeros where d_nmask is NULL) and d_out_counts[j] = the read's count in
+ *                       `sample`, or its total for sample == 0xFFFFFFFF.  An index >= n, a read longer than its words hold
+ *                       or a total of 2^32 and more is MRG_ERR_ARG (found on the device; the outputs are then undefined).
+ * mrg_write_predict_fasta  HOST arrays: the reads, lens, nmask or NULL, and the rows (idx, num, counts) [k] of a list;
+ *                       counts are uint32 (count_bytes 4) or uint64 (8).  Extra rows (extra_seqs, extra_nums, extra_counts),
+ *                       in file order after the packed rows: the reads beyond 255 nt.  Returns the rows written, or a negative
+ *                       error: the whole list is checked before the file is opened, and an index >= n, a number of 0,
+ *                       numbers or indices that do not increase (the extra rows' numbers continue the packed ones) are
+ *                       MRG_ERR_ARG and write nothing (an I/O error, MRG_ERR_IO, is met with the file open and can leave it
+ *                       truncated).  Runs of rows are formatted by worker threads
+ *                       (MIRGE_AMD_TABLE_THREADS, at most 16; MIRGE_AMD_PREDICT_BLOCK_ROWS = rows per run, lowered by tests).
+ * mrg_predict_read_names  HOST: the names "mir<num>_<count>" of k rows, one after the other: name j is blob[offsets[j] ..
+ *                       offsets[j + 1]) (offsets [k + 1]); *blob_bytes = the bytes of all names.  blob NULL sizes the buffer;
+ *                       a blob smaller than that is MRG_ERR_ARG.
+ */
+int mrg_predict_reads_temp_bytes(uint64_t n, uint64_t *bytes);
+int mrg_predict_select(mrg_ctx *ctx, const int8_t *d_pass_id, const uint8_t *d_lens, const uint32_t *d_quant, uint64_t n,
+                       uint32_t n_samples, uint32_t min_len, uint32_t max_len, uint64_t count_cutoff, uint64_t *d_total,
+                       uint32_t *d_raw_no, uint32_t *d_sel_no, uint64_t *n_raw, uint64_t *n_sel, void *d_tmp,
+                       uint64_t tmp_bytes, void *stream);
+int mrg_predict_sample_reads(mrg_ctx *ctx, const uint32_t *d_quant, uint64_t n, uint32_t n_samples, uint32_t sample,
+                             const uint32_t *d_no, uint64_t threshold, uint32_t *d_idx, uint32_t *d_num, uint32_t *d_cnt,
+                             uint64_t cap, uint64_t *rows, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_gather(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t *d_lens,
+                       const uint64_t *d_nmask, uint64_t n, const uint32_t *d_quant, uint32_t n_samples, uint32_t sample,
+                       const uint32_t *d_idx, uint64_t k, uint64_t *d_out_reads, uint8_t *d_out_lens, uint64_t *d_out_nmask,
+                       uint32_t *d_out_counts, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int64_t mrg_write_predict_fasta(const char *path, const uint64_t *reads, uint32_t words_per_read, uint64_t stride,
+                                const uint8_t *lens, const uint64_t *nmask, uint64_t n, const uint32_t *idx,
+                                const uint32_t *num, const void *counts, uint32_t count_bytes, uint64_t k,
+                                const char *const *extra_seqs, const uint64_t *extra_nums, const uint64_t *extra_counts,
+                                uint64_t n_extra);
+int mrg_predict_read_names(const uint32_t *num, const void *counts, uint32_t count_bytes, uint64_t k, char *blob,
+                           uint64_t blob_cap, uint64_t *offsets, uint64_t *blob_bytes);
+
+/*
  * `annotate -ai`: every read claimed by the exact-miRNA or the isomiR pass aligned to the canonical sequence of its (merged)
  * miRNA, and a2IEditing.detail.txt, from the arrays.  mirge_amd/a2i.py holds the Python model (local_pair, judge_align,
  * a2i_editing) whose results the two calls reproduce exactly; DESIGN.md 8.6 holds the argument.

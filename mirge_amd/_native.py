@@ -270,6 +270,21 @@ SIGNATURES = {
     "mrg_write_collapsed_fasta": (C.c_int64, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                               C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                               C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64]),
+    "mrg_predict_reads_temp_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mrg_predict_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_predict_sample_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                                           C.c_uint64, C.c_void_p]),
+    "mrg_predict_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_write_predict_fasta": (C.c_int64, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_char_p),
+                                            C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mrg_predict_read_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.POINTER(C.c_uint64)]),
     "mrg_pack_reads": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "mrg_trf_rho": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

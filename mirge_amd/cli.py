@@ -17,6 +17,11 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
   * `-trf` writes `tRFs.potential.report.tsv`, `tRF.Counts.csv`, `tRF.RP100K.csv`,
     `discarded.reads.summary.assigningtRFs.csv` and the per-sample reports and density-peak clusters
     of `tRFs.samples.tmp/` (mirge_amd.trf_samples, clustered on the GPU); the PDF report is not produced.
+  * `--novel-reads` (with the reference's predict-mode `-minl 16 -maxl 25 -cc 2`) writes `unmapped_tmp/` with the FASTA
+    files convert2Fasta makes of unmapped.csv, picked and numbered on the GPU from the arrays; `--novel-clusters` (with
+    `-ml 3 -sl 25 -olc 14`; implies `--novel-reads`) moves each sample's two files to
+    `unmapped_tmp/unmapped_mirna_<sample>_tmp/` and writes that sample's `..._vs_genome_sorted_clusters.tsv` and
+    `..._vs_genome_sorted.sam` next to them (the genome as for `-ai`; reads of at most 255 nt: `-maxl` above 255 exits 1).
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -61,6 +66,18 @@ def build_parser():
     p.add_argument("--trf-host", dest="trf_host", action="store_true",
                    help="extension: the -trf tables through the per-read Python records instead of the GPU typing and "
                         "assignment (same files)")
+    p.add_argument("--novel-reads", dest="novel_reads", action="store_true",
+                   help="extension: predict mode's candidate reads from the arrays -- unmapped_tmp/ with the FASTA files "
+                        "convert2Fasta writes for unmapped.csv (-minl / -maxl / -cc)")
+    p.add_argument("--novel-clusters", dest="novel_clusters", action="store_true",
+                   help="extension: --novel-reads, then per sample the genome mapping and the location clusters of its "
+                        "candidate reads on the GPU (-ml / -sl / -olc), in unmapped_tmp/unmapped_mirna_<sample>_tmp/")
+    p.add_argument("-minl", default="16", dest="minLength", metavar="<int>")
+    p.add_argument("-maxl", default="25", dest="maxLength", metavar="<int>")
+    p.add_argument("-cc", default="2", dest="countCutoff", metavar="<int>")
+    p.add_argument("-ml", default="3", dest="mapping_loc", metavar="<int>")
+    p.add_argument("-sl", default="25", dest="seedLength", metavar="<int>")
+    p.add_argument("-olc", default="14", dest="overlapLenCutoff", metavar="<int>")
     p.add_argument("--gpu", type=int, default=0, help="device index (default 0)")
     p.add_argument("--device-ingest", action="store_true",
                    help="split, trim and pack the FASTQ records on the GPU (raw text blocks are uploaded; `-ad none` / `-ad +N` "
@@ -173,6 +190,33 @@ def annotate_main(args, engine_factory=None, materialize=False):
     sp, lib = args.species, args.libraryPath
     if args.trf_output and sp != "human":  # MAIN:161-163
         _die("tRF detection is only supported for the species of human. Please check it.")
+    novel_clusters = bool(getattr(args, "novel_clusters", False))
+    novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
+    novel_genome = None
+
+    def novel_die(msg, out=sys.stderr):   # every rank of `--gpus N` leaves with status 1; rank 0 says why, as for -ai
+        if rank == 0:
+            print(msg, file=out)
+        sys.exit(1)
+    if novel_reads:
+        try:
+            novel_min, novel_max, novel_cc = int(args.minLength), int(args.maxLength), int(args.countCutoff)
+            mapping_loc, seed_len, overlap = int(args.mapping_loc), int(args.seedLength), int(args.overlapLenCutoff)
+        except ValueError:
+            novel_die("The values of -minl, -maxl, -cc, -ml, -sl and -olc must be integers. Please check them.")
+        if novel_min < 0 or novel_min > novel_max or novel_cc < 1:
+            novel_die("-minl must not exceed -maxl and -cc must be at least 1. Please check them.")
+    if novel_clusters:
+        if novel_max > 255:
+            novel_die("-maxl %d: the genome stage of --novel-clusters takes reads of at most 255 nt. Please check it." % novel_max)
+        if mapping_loc < 0 or seed_len < 5 or overlap < 1:
+            novel_die("-ml must be >= 0, -sl >= 5 and -olc >= 1. Please check them.")
+        import glob
+        novel_genome = os.path.join(lib, sp, "index.Libs", "%s_genome" % sp)
+        if not (any(os.path.isfile(novel_genome + e) for e in (".mrgfm", ".fa", ".fasta"))
+                or glob.glob(glob.escape(novel_genome) + ".part[0-9]*.mrgfm")):
+            novel_die("The index file of %s_genome (.mrgfm, .fa or .partNNN.mrgfm) is not located at %s, "
+                      "please check it." % (sp, os.path.join(lib, sp, "index.Libs")), sys.stdout)
     trf_tables, trf_content = None, None
     if args.trf_output:
         from . import trf
@@ -462,6 +506,32 @@ def annotate_main(args, engine_factory=None, materialize=False):
     report.write_annotation_report_csv(os.path.join(outdir, "annotation.report.csv"), sample_list, log_dic, spike)
     columnar.write_read_tables(outdir, names, sample_list, h_words, h_lens, h_nmask, h_quant, h_pass, h_ref, npp,
                                extra=long_res)
+    if novel_reads:   # convert2Fasta over unmapped.csv (MAIN:502) and, with --novel-clusters, MAIN:521-548, from the arrays
+        from . import predict
+        tmp_dir = os.path.join(outdir, "unmapped_tmp")
+        os.makedirs(tmp_dir)
+        on_device = not (world > 1 or shard.quant is None)   # (else the gathered host arrays)
+        a_pass, a_lens, a_quant = (res.pass_id, shard.lens, shard.quant) if on_device else (h_pass, h_lens, h_quant)
+        lists = predict.candidate_lists(engine, a_pass, a_lens, a_quant, novel_min, novel_max, novel_cc)
+        long_rows = []   # the unmapped reads beyond 255 nt: the last rows of unmapped.csv, in this order
+        if long_res is not None:
+            long_rows = [(seq, long_res[1][k]) for k, seq in enumerate(long_res[0]) if int(long_res[2][k]) < 0]
+        predict.write_candidate_reads(tmp_dir, sample_list, h_words, h_lens, h_nmask, lists, novel_min, novel_max, novel_cc,
+                                      long_rows)
+        if novel_clusters:
+            a_reads = (shard.words, shard.lens, shard.nmask) if on_device else (h_words, h_lens, h_nmask)
+            stems = [predict.sample_stem(name) for name in sample_list]
+            for s, stem in enumerate(stems):
+                if stem in stems[s + 1:]:   # (a later sample wrote this stem's files)
+                    continue
+                sub = os.path.join(tmp_dir, "unmapped_mirna_%s_tmp" % stem)
+                os.makedirs(sub)
+                for fn in ("unmapped_mirna_%s.fa" % stem, "unmapped_mirna_%s_raw.fa" % stem):
+                    os.replace(os.path.join(tmp_dir, fn), os.path.join(sub, fn))
+                idx, num, _cnt = lists["sample_sel"][s]
+                g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
+                predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
+                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem))
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

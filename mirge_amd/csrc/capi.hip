@@ -27,6 +27,7 @@
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
+#include "predict_reads.hpp"
 #include "prims.hpp"
 #include "sa_build.hpp"
 #include "tables.hpp"
@@ -4283,6 +4284,192 @@ int64_t mrg_write_collapsed_fasta(const char* path, const uint64_t* reads, uint3
   } catch (const std::exception& e) {
     return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
   }
+}
+
+// ------------------------------------------------------------- predict mode's candidate reads (csrc/predict_reads.hip)
+extern "C++" {
+namespace {
+
+struct PredictScratch {  // the caller's scratch, carved into 256-byte aligned pieces
+  uint64_t raw, sel, scan, stat, total;
+  explicit PredictScratch(uint64_t n) {
+    uint64_t used = 0;
+    auto reserve = [&](uint64_t bytes) {
+      const uint64_t at = used;
+      used += (std::max<uint64_t>(bytes, 1) + 255) & ~255ull;
+      return at;
+    };
+    raw = reserve((n + 1) * sizeof(uint32_t));
+    sel = reserve((n + 1) * sizeof(uint32_t));
+    scan = reserve(mrg::prims::scan_temp_bytes(n + 1));
+    stat = reserve(mrg::kPredictStatWords * sizeof(uint32_t));
+    total = used;
+  }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int mrg_predict_reads_temp_bytes(uint64_t n, uint64_t* bytes) {
+  if (!bytes) return fail(MRG_ERR_ARG, "mrg_predict_reads_temp_bytes: null argument");
+  if (n >= (1ull << 31)) return fail(MRG_ERR_ARG, "mrg_predict_reads_temp_bytes: %llu reads; the limit is 2^31 - 1", (unsigned long long)n);
+  *bytes = PredictScratch(n).total;
+  return MRG_OK;
+}
+
+int mrg_predict_select(mrg_ctx* ctx, const int8_t* d_pass_id, const uint8_t* d_lens, const uint32_t* d_quant, uint64_t n,
+                       uint32_t n_samples, uint32_t min_len, uint32_t max_len, uint64_t count_cutoff, uint64_t* d_total,
+                       uint32_t* d_raw_no, uint32_t* d_sel_no, uint64_t* n_raw, uint64_t* n_sel, void* d_tmp, uint64_t tmp_bytes,
+                       void* stream) {
+  const char* fn = "mrg_predict_select";
+  if (!ctx || !n_raw || !n_sel || !d_tmp) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_raw = *n_sel = 0;
+  if (n && (!d_pass_id || !d_lens || !d_quant || !d_total || !d_raw_no || !d_sel_no)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: %llu reads; the limit is 2^31 - 1", fn, (unsigned long long)n);
+  if (n_samples == 0) return fail(MRG_ERR_ARG, "%s: no sample column", fn);
+  if (min_len > max_len) return fail(MRG_ERR_ARG, "%s: the length window %u .. %u is empty", fn, min_len, max_len);
+  if (count_cutoff == 0) return fail(MRG_ERR_ARG, "%s: the count cutoff must be at least 1", fn);
+  const PredictScratch sc(n);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)d_tmp;
+  uint32_t *raw = (uint32_t*)(base + sc.raw), *sel = (uint32_t*)(base + sc.sel);
+  mrg::PredictSelectParams p;
+  p.pass_id = d_pass_id;
+  p.lens = d_lens;
+  p.quant = d_quant;
+  p.n = (uint32_t)n;
+  p.S = n_samples;
+  p.min_len = min_len;
+  p.max_len = max_len;
+  p.cutoff = count_cutoff;
+  HIP_TRY(mrg::predict_flags_launch(p, d_total, raw, sel, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(raw, raw, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(sel, sel, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::predict_numbers_launch(raw, sel, p.n, d_raw_no, d_sel_no, st));
+  uint32_t k[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&k[0], raw + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&k[1], sel + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (k[0] > n || k[1] > k[0]) return fail(MRG_ERR_HIP, "%s: %u raw and %u filtered rows of %llu reads", fn, k[0], k[1], (unsigned long long)n);
+  *n_raw = k[0];
+  *n_sel = k[1];
+  return MRG_OK;
+}
+
+int mrg_predict_sample_reads(mrg_ctx* ctx, const uint32_t* d_quant, uint64_t n, uint32_t n_samples, uint32_t sample,
+                             const uint32_t* d_no, uint64_t threshold, uint32_t* d_idx, uint32_t* d_num, uint32_t* d_cnt, uint64_t cap,
+                             uint64_t* rows, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_sample_reads";
+  if (!ctx || !rows || !d_tmp) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *rows = 0;
+  if (n && (!d_quant || !d_no)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (cap && (!d_idx || !d_num || !d_cnt)) return fail(MRG_ERR_ARG, "%s: null output buffer", fn);
+  if (n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: %llu reads; the limit is 2^31 - 1", fn, (unsigned long long)n);
+  if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
+  if (threshold == 0) return fail(MRG_ERR_ARG, "%s: the threshold must be at least 1", fn);
+  const PredictScratch sc(n);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)d_tmp;
+  uint32_t* flags = (uint32_t*)(base + sc.raw);
+  const uint32_t N = (uint32_t)n;
+  // ---- count: flag, exclusive sums
+  HIP_TRY(mrg::predict_sample_flags_launch(d_quant, d_no, N, n_samples, sample, threshold, flags, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, base + sc.scan, st));
+  uint32_t k = 0;
+  HIP_TRY(hipMemcpyAsync(&k, flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (k > N) return fail(MRG_ERR_HIP, "%s: %u rows of %u reads", fn, k, N);
+  *rows = k;
+  if (cap < k) return fail(MRG_ERR_ARG, "%s: %u rows do not fit a buffer of %llu", fn, k, (unsigned long long)cap);
+  if (k == 0) return MRG_OK;
+  // ---- fill: scatter in array order
+  HIP_TRY(mrg::predict_sample_fill_launch(flags, d_quant, d_no, N, n_samples, sample, d_idx, d_num, d_cnt, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+int mrg_predict_gather(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                       const uint64_t* d_nmask, uint64_t n, const uint32_t* d_quant, uint32_t n_samples, uint32_t sample,
+                       const uint32_t* d_idx, uint64_t k, uint64_t* d_out_reads, uint8_t* d_out_lens, uint64_t* d_out_nmask,
+                       uint32_t* d_out_counts, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_gather";
+  if (!ctx || !d_tmp) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (k && (!d_reads || !d_lens || !d_quant || !d_idx || !d_out_reads || !d_out_lens || !d_out_counts))
+    return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8)
+    return fail(MRG_ERR_ARG, "%s: words_per_read must be 1, 2, 4 or 8", fn);
+  if (stride < n || n >= (1ull << 31) || k > n) return fail(MRG_ERR_ARG, "%s: bad stride / n / k", fn);
+  if (n_samples == 0 || (sample >= n_samples && sample != mrg::kPredictTotalAll)) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
+  const PredictScratch sc(n);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  if (k == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = (uint32_t*)((char*)d_tmp + sc.stat);
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPredictStatWords * sizeof(uint32_t), st));
+  mrg::PredictGatherParams p;
+  p.reads = d_reads;
+  p.nmask = d_nmask;
+  p.lens = d_lens;
+  p.quant = d_quant;
+  p.idx = d_idx;
+  p.stride = stride;
+  p.n = (uint32_t)n;
+  p.W = words_per_read;
+  p.S = n_samples;
+  p.sample = sample;
+  p.k = (uint32_t)k;
+  p.out_reads = d_out_reads;
+  p.out_nmask = d_out_nmask;
+  p.out_lens = d_out_lens;
+  p.out_counts = d_out_counts;
+  HIP_TRY(mrg::predict_gather_launch(p, stat, st));
+  uint32_t h_stat[mrg::kPredictStatWords] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_stat[mrg::kPredictStatBadIndex]) return fail(MRG_ERR_ARG, "%s: an index is no read of %llu", fn, (unsigned long long)n);
+  if (h_stat[mrg::kPredictStatTooLong]) return fail(MRG_ERR_ARG, "%s: a read is longer than its %u words hold", fn, words_per_read);
+  if (h_stat[mrg::kPredictStatOverflow]) return fail(MRG_ERR_ARG, "%s: a read's total count does not fit 32 bits", fn);
+  return MRG_OK;
+}
+
+int64_t mrg_write_predict_fasta(const char* path, const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens,
+                                const uint64_t* nmask, uint64_t n, const uint32_t* idx, const uint32_t* num, const void* counts,
+                                uint32_t count_bytes, uint64_t k, const char* const* extra_seqs, const uint64_t* extra_nums,
+                                const uint64_t* extra_counts, uint64_t n_extra) {
+  const char* fn = "mrg_write_predict_fasta";
+  if (!path) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (k && (!reads || !lens || !idx || !num || !counts)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_extra && (!extra_seqs || !extra_nums || !extra_counts)) return fail(MRG_ERR_ARG, "%s: null extra rows", fn);
+  if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
+    return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
+  if (count_bytes != 4 && count_bytes != 8) return fail(MRG_ERR_ARG, "%s: count_bytes must be 4 or 8", fn);
+  try {
+    const mrg::PredictFastaArgs a{path, reads, words_per_read, stride, lens, nmask, n, idx, num, counts, count_bytes, k,
+                                  extra_seqs, extra_nums, extra_counts, n_extra};
+    return (int64_t)mrg::write_predict_fasta(a);
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+int mrg_predict_read_names(const uint32_t* num, const void* counts, uint32_t count_bytes, uint64_t k, char* blob, uint64_t blob_cap,
+                           uint64_t* offsets, uint64_t* blob_bytes) {
+  const char* fn = "mrg_predict_read_names";
+  if (!offsets || !blob_bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *blob_bytes = 0;
+  if (k && (!num || !counts)) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (count_bytes != 4 && count_bytes != 8) return fail(MRG_ERR_ARG, "%s: count_bytes must be 4 or 8", fn);
+  *blob_bytes = mrg::predict_read_names(num, counts, count_bytes, k, blob, blob_cap, offsets);
+  if (blob && blob_cap < *blob_bytes) return fail(MRG_ERR_ARG, "%s: %llu bytes of names do not fit a buffer of %llu", fn,
+                                                  (unsigned long long)*blob_bytes, (unsigned long long)blob_cap);
+  return MRG_OK;
 }
 
 // ------------------------------------------------------------- -ai

@@ -883,6 +883,102 @@ class Engine:
             timings.update(rank_ms=ev[0].elapsed_time(ev[1]), order_ms=ev[1].elapsed_time(ev[2]))
         return out
 
+    def _dev_u32(self, x, what="the array"):
+        """A device tensor as it is, a host array as uint32 in int32 storage on the device."""
+        torch = _torch()
+        if torch.is_tensor(x):
+            return self._expect(x, torch.int32, what).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint32).view(np.int32)).to(self.device)
+
+    @staticmethod
+    def _expect(t, dtype, what):
+        """The device tensor `t`, or TypeError when its elements are not `dtype`: the kernels read raw memory."""
+        if t.dtype != dtype:
+            raise TypeError("%s must be a %s tensor, not %s" % (what, dtype, t.dtype))
+        return t
+
+    def _predict_tmp(self, n):
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_reads_temp_bytes(n, C.byref(need)))
+        torch = _torch()
+        return torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+
+    def predict_select(self, pass_id, lens, quant, min_len=16, max_len=25, count_cutoff=2):
+        """Predict mode's candidate reads (mrg_predict_select; the rules of convert2Fasta.py over unmapped.csv): of the
+        unmapped reads (pass_id < 0) the raw list holds those whose counts sum to 1 or more, the filtered list those with
+        min_len <= length <= max_len whose counts sum to count_cutoff or more, both numbered from 1 in array order.
+        pass_id [n] / lens [n] / quant [n, S]: device tensors or host arrays (uploaded).  Returns a dict of device tensors
+        total (int64 [n], every read's sum), raw_no and sel_no (uint32 in int32 storage [n]: the read's number in the
+        list, 0 outside it) and the ints n_raw, n_sel."""
+        torch = _torch()
+        if not torch.is_tensor(pass_id):
+            pass_id = torch.from_numpy(np.ascontiguousarray(pass_id, dtype=np.int8)).to(self.device)
+        if not torch.is_tensor(lens):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.uint8)).to(self.device)
+        pass_id = self._expect(pass_id, torch.int8, "predict_select: pass_id").contiguous()
+        lens = self._expect(lens, torch.uint8, "predict_select: lens").contiguous()
+        quant = self._dev_u32(quant, "predict_select: quant")
+        n = int(lens.shape[0])
+        S = int(quant.shape[1]) if quant.dim() == 2 else 1
+        if int(quant.shape[0]) != n or int(pass_id.shape[0]) != n:
+            raise ValueError("predict_select: pass_id [n], lens [n] and quant [n, S] must match")
+        tmp = self._predict_tmp(n)
+        total = torch.zeros(max(n, 1), dtype=torch.int64, device=self.device)
+        raw_no = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        sel_no = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        n_raw, n_sel = C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.mrg_predict_select(self._h, pass_id.data_ptr(), lens.data_ptr(), quant.data_ptr(), n, S, int(min_len),
+                                           int(max_len), int(count_cutoff), total.data_ptr(), raw_no.data_ptr(), sel_no.data_ptr(),
+                                           C.byref(n_raw), C.byref(n_sel), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return dict(total=total[:n], raw_no=raw_no[:n], sel_no=sel_no[:n], n_raw=int(n_raw.value), n_sel=int(n_sel.value))
+
+    def predict_sample_reads(self, quant, numbers, sample, threshold):
+        """One sample's rows of a list of predict_select (mrg_predict_sample_reads): the reads u with numbers[u] != 0 and
+        quant[u, sample] >= threshold, in array order.  numbers: raw_no with threshold 1, or sel_no with the count cutoff.
+        quant [n, S] / numbers [n]: device tensors or host arrays.  Returns device tensors (index, number, count), uint32 in
+        int32 storage."""
+        torch = _torch()
+        quant, numbers = self._dev_u32(quant, "predict_sample_reads: quant"), self._dev_u32(numbers, "predict_sample_reads: numbers")
+        n = int(numbers.shape[0])
+        S = int(quant.shape[1]) if quant.dim() == 2 else 1
+        if int(quant.shape[0]) != n:
+            raise ValueError("predict_sample_reads: quant [n, S] and numbers [n] must match")
+        tmp = self._predict_tmp(n)
+        out = [torch.empty(max(n, 1), dtype=torch.int32, device=self.device) for _ in range(3)]
+        rows = C.c_uint64(0)
+        check(self._lib.mrg_predict_sample_reads(self._h, quant.data_ptr(), n, S, int(sample), numbers.data_ptr(), int(threshold),
+                                                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), n, C.byref(rows),
+                                                 tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        k = int(rows.value)
+        return out[0][:k], out[1][:k], out[2][:k]
+
+    def predict_gather(self, words, lens, nmask, quant, index, sample=None):
+        """The reads index[j] as a compact packed set (mrg_predict_gather), what ReadSet.from_device and cluster_valid take:
+        device tensors (words [W, k], lens [k], nmask [W, k] or None, counts [k] uint32 in int32 storage), counts = the
+        reads' counts in `sample` (None: their totals, which must fit 32 bits).  words / lens / nmask / quant / index:
+        device tensors or host arrays."""
+        torch = _torch()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        self._expect(words, torch.int64, "predict_gather: words")
+        self._expect(lens, torch.uint8, "predict_gather: lens")
+        if nmask is not None:
+            self._expect(nmask, torch.int64, "predict_gather: nmask")
+        quant, index = self._dev_u32(quant, "predict_gather: quant"), self._dev_u32(index, "predict_gather: index")
+        W, n, k = int(words.shape[0]), int(words.shape[1]), int(index.shape[0])
+        S = int(quant.shape[1]) if quant.dim() == 2 else 1
+        if int(quant.shape[0]) != n or int(lens.shape[0]) != n or (nmask is not None and tuple(nmask.shape) != (W, n)):
+            raise ValueError("predict_gather: words [W, n], lens [n], nmask [W, n] and quant [n, S] must match")
+        tmp = self._predict_tmp(n)
+        o_words = torch.zeros((W, k), dtype=torch.int64, device=self.device)
+        o_nmask = None if nmask is None else torch.zeros((W, k), dtype=torch.int64, device=self.device)
+        o_lens = torch.zeros(k, dtype=torch.uint8, device=self.device)
+        o_counts = torch.zeros(k, dtype=torch.int32, device=self.device)
+        check(self._lib.mrg_predict_gather(
+            self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(), n, quant.data_ptr(), S,
+            0xFFFFFFFF if sample is None else int(sample), index.data_ptr(), k, o_words.data_ptr(), o_lens.data_ptr(),
+            None if o_nmask is None else o_nmask.data_ptr(), o_counts.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return o_words, o_lens, o_nmask, o_counts
+
     def list_valid(self, reads, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
                    max_mm_total=2, timings=None):
         """The bowtie front end's listing (mrg_list_valid_count / _fill): every valid alignment of each read of a

@@ -107,6 +107,21 @@ def pack_ragged(seqs):
     return words, (nmask if any_n else None), word_off, lens.astype(np.uint32)
 
 
+def unpack_blob(words, lens, nmask=None):
+    """The reads' letters one after the other and their offsets (bytes, uint64 [n + 1]): what unpack_reads returns, joined,
+    without a Python string per read (the native writers take such a pair)."""
+    words = np.asarray(words, dtype=np.uint64)
+    W, n = words.shape
+    lens = np.asarray(lens).astype(np.int64)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(lens, out=off[1:])
+    width = int(lens.max()) if n else 0
+    if width == 0:
+        return b"", off
+    chars = _letters(words, nmask, n, width)
+    return chars[np.arange(width)[None, :] < lens[:, None]].tobytes(), off
+
+
 def unpack_reads(words, lens, nmask=None):
     """Inverse of pack_reads (reports, tests, the dict-shaped host path): vectorised over reads."""
     words = np.asarray(words, dtype=np.uint64)
@@ -117,6 +132,12 @@ def unpack_reads(words, lens, nmask=None):
     width = int(lens.max()) if n else 0
     if width == 0:
         return [""] * n
+    blob = _letters(words, nmask, n, width).tobytes()
+    return [blob[r * width:r * width + L].decode("ascii") for r, L in enumerate(lens.tolist())]
+
+
+def _letters(words, nmask, n, width):
+    """uint8 [n, width]: the letters of the first `width` bases of every read."""
     letters = np.frombuffer(b"ACGT", dtype=np.uint8)
     chars = np.empty((n, width), dtype=np.uint8)
     for w in range((width + 31) // 32):
@@ -127,8 +148,7 @@ def unpack_reads(words, lens, nmask=None):
             isn = ((np.asarray(nmask, dtype=np.uint64)[w][:, None] >> sh[None, :]) & np.uint64(1)).astype(bool)
             grid[isn] = ord("N")
         chars[:, 32 * w:32 * w + nb] = grid
-    blob = chars.tobytes()
-    return [blob[r * width:r * width + L].decode("ascii") for r, L in enumerate(lens.tolist())]
+    return chars
 
 
 COMPACT_ESCAPE = 255      # one-byte count meaning "look in the escape list"

@@ -53,11 +53,45 @@ def read_counts(names):
     return counts
 
 
-def write_clusters(path, sample, parts, names, cl, threads=None):
-    """mrg_write_clusters over the arrays of Engine.cluster_valid (parts: the FmIndex list; names: the reads')."""
+def _blob(strs):
+    """(blob, offsets uint64 [n + 1], n) of a list of strings, or of a ready (blob, offsets) pair (mrg_predict_read_names,
+    pack.unpack_blob), which is passed through."""
+    if isinstance(strs, tuple) and len(strs) == 2 and isinstance(strs[0], (bytes, bytearray, memoryview, np.ndarray)):
+        blob, off = strs
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        return (blob if isinstance(blob, bytes) else bytes(blob)), off, int(off.shape[0]) - 1
+    blob, off = bowtie._blob(strs)
+    return blob, off, len(strs)
+
+
+def read_names(numbers, counts):
+    """The names `mir<number>_<count>` of a list's rows as one blob plus offsets (mrg_predict_read_names): the pair
+    write_clusters and write_sorted_sam take in place of a list of names.  counts: uint32 or uint64."""
     from . import _native
     lib = _native.load()
-    nb, no = bowtie._blob(names)
+    numbers = np.ascontiguousarray(numbers, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts)
+    if counts.dtype != np.uint64:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    k = int(numbers.shape[0])
+    if counts.shape != (k,):
+        raise ValueError("read_names: one count per number")
+    off = np.zeros(k + 1, dtype=np.uint64)
+    need = C.c_uint64(0)
+    _native.check(lib.mrg_predict_read_names(_ptr(numbers), _ptr(counts), counts.dtype.itemsize, k, None, 0, off.ctypes.data,
+                                             C.byref(need)))
+    blob = np.zeros(max(int(need.value), 1), dtype=np.uint8)
+    _native.check(lib.mrg_predict_read_names(_ptr(numbers), _ptr(counts), counts.dtype.itemsize, k, blob.ctypes.data,
+                                             int(need.value), off.ctypes.data, C.byref(need)))
+    return blob[:int(need.value)].tobytes(), off
+
+
+def write_clusters(path, sample, parts, names, cl, threads=None):
+    """mrg_write_clusters over the arrays of Engine.cluster_valid (parts: the FmIndex list; names: the reads', a list or
+    the (blob, offsets) pair of read_names)."""
+    from . import _native
+    lib = _native.load()
+    nb, no, n_reads = _blob(names)
     hs = (C.c_void_p * max(len(parts), 1))(*[p._h.value for p in parts])
     arr = {k: np.ascontiguousarray(cl[k], dtype=dt) for k, dt in
            (("entry", np.uint32), ("strand", np.uint8), ("start", np.uint32), ("end", np.uint32), ("seq_off", np.uint64),
@@ -68,16 +102,19 @@ def write_clusters(path, sample, parts, names, cl, threads=None):
         _native.check(lib.mrg_write_clusters(
             os.fsencode(path), sample.encode(), hs, len(parts), len(arr["entry"]), _ptr(arr["entry"]), _ptr(arr["strand"]),
             _ptr(arr["start"]), _ptr(arr["end"]), arr["seq_off"].ctypes.data, _ptr(seq), _ptr(arr["count_sum"]),
-            arr["member_off"].ctypes.data, _ptr(arr["members"]), len(names), nb, no.ctypes.data, C.byref(rows)))
+            arr["member_off"].ctypes.data, _ptr(arr["members"]), n_reads, nb, no.ctypes.data, C.byref(rows)))
     return int(rows.value)
 
 
 def write_sorted_sam(path, parts, names, seqs, rows, suppressed, m, threads=None):
-    """mrg_write_sorted_sam: rows = (read, entry, offset, strand, mm) in the order to print."""
+    """mrg_write_sorted_sam: rows = (read, entry, offset, strand, mm) in the order to print.  names / seqs: lists, or
+    (blob, offsets) pairs (read_names, pack.unpack_blob)."""
     from . import _native
     lib = _native.load()
-    nb, no = bowtie._blob(names)
-    sb, so = bowtie._blob(seqs)
+    nb, no, n_reads = _blob(names)
+    sb, so, n_seqs = _blob(seqs)
+    if n_seqs != n_reads:
+        raise ValueError("write_sorted_sam: %d names and %d sequences" % (n_reads, n_seqs))
     hs = (C.c_void_p * max(len(parts), 1))(*[p._h.value for p in parts])
     read, entry, offset, strand, mm = (np.ascontiguousarray(a, dtype=dt) for a, dt in
                                        zip(rows, (np.uint32, np.int32, np.int32, np.uint8, np.uint8)))
@@ -85,7 +122,7 @@ def write_sorted_sam(path, parts, names, seqs, rows, suppressed, m, threads=None
     summary = np.zeros(4, dtype=np.uint64)
     with _writer_threads(threads):
         _native.check(lib.mrg_write_sorted_sam(
-            os.fsencode(path), hs, len(parts), len(names), nb, no.ctypes.data, sb, so.ctypes.data, len(read), _ptr(read),
+            os.fsencode(path), hs, len(parts), n_reads, nb, no.ctypes.data, sb, so.ctypes.data, len(read), _ptr(read),
             _ptr(entry), _ptr(offset), _ptr(strand), _ptr(mm), _ptr(supp), int(m), summary.ctypes.data))
     return dict(processed=int(summary[0]), aligned=int(summary[1]), suppressed=int(summary[2]), reported=int(summary[3]))
 
@@ -124,26 +161,20 @@ def genome_libraries(engine, genome_prefix):
     return cache[key]
 
 
-def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None):
-    """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
-    against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
-    `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
-    arrays of Engine.cluster_valid.  mapping_loc 0 = no -m.  Nothing is written when a limit is exceeded."""
-    from .engine import ReadSet, STRATUM_ALL
-    names, seqs = bowtie.read_fasta(reads_fa)
-    longest = max((len(s) for s in seqs), default=0)
-    if longest > bowtie.MAX_READ_LEN:
-        raise ValueError("reads longer than %d nt are not supported; got %d" % (bowtie.MAX_READ_LEN, longest))
+def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
     if int(mapping_loc) < 0 or int(seedLength) < 5 or int(overlapLenCutoff) < 1:
         raise ValueError("mapping_loc must be >= 0, seedLength >= 5 and overlapLenCutoff >= 1")
-    counts = read_counts(names)
+
+
+def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
+                       sam, timings):
+    """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
+    as write_clusters / write_sorted_sam take them."""
+    from .engine import STRATUM_ALL
     keys, parts = genome_libraries(engine, genome_prefix)
     sam_path = out_stem + "_vs_genome_sorted.sam"
     keep = np.array(["chr" in nm for ix in parts for nm in ix.names], dtype=bool)
-    if seqs:
-        words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
-        rs = ReadSet(words, lens, nmask, device=engine.device)
+    if rs is not None:
         cl = engine.cluster_valid(rs, keys, counts, entry_keep=keep, threshold=int(overlapLenCutoff), strands=2,
                                   stratum_mode=STRATUM_ALL, m=int(mapping_loc), seed_len=int(seedLength), max_mm_seed=0,
                                   max_mm_total=bowtie.N_MODE_MAX_TOTAL, sorted_rows=sam, timings=timings)
@@ -156,6 +187,157 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     if sam:
         write_sorted_sam(sam_path, parts, names, seqs, cl["rows"], cl["suppressed"], int(mapping_loc))
     return cl
+
+
+def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
+                    timings=None):
+    """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
+    against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
+    `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
+    arrays of Engine.cluster_valid.  mapping_loc 0 = no -m.  Nothing is written when a limit is exceeded."""
+    from .engine import ReadSet
+    names, seqs = bowtie.read_fasta(reads_fa)
+    longest = max((len(s) for s in seqs), default=0)
+    if longest > bowtie.MAX_READ_LEN:
+        raise ValueError("reads longer than %d nt are not supported; got %d" % (bowtie.MAX_READ_LEN, longest))
+    _check_policy(mapping_loc, seedLength, overlapLenCutoff)
+    counts = read_counts(names)
+    rs = None
+    if seqs:
+        words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
+        rs = ReadSet(words, lens, nmask, device=engine.device)
+    return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
+                              out_stem, sam, timings)
+
+
+def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
+                          sam=True, timings=None):
+    """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
+    tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
+    host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
+    names; no FASTA is parsed and no Python string is made per read."""
+    import torch
+    from .engine import ReadSet
+    _check_policy(mapping_loc, seedLength, overlapLenCutoff)
+
+    def host_u32(x):   # (a device tensor holds uint32 in int32 storage)
+        return np.ascontiguousarray(x.cpu().numpy()).view(np.uint32) if torch.is_tensor(x) else np.ascontiguousarray(x, dtype=np.uint32)
+    numbers, counts = host_u32(numbers), host_u32(counts)
+    words, lens, nmask = engine._dev_reads(*reads)
+    k = int(lens.shape[0])
+    if numbers.shape != (k,) or counts.shape != (k,) or int(words.shape[1]) != k:
+        raise ValueError("map_and_cluster_reads: words [W, k], lens, numbers and counts [k] must match")
+    names = read_names(numbers, counts)
+    rs, seqs = None, (b"", np.zeros(1, np.uint64))
+    if k:
+        lo, hi = int(lens.min()), int(lens.max())
+        if hi > 32 * int(words.shape[0]):
+            raise ValueError("a read of %d nt does not fit %d words" % (hi, int(words.shape[0])))
+        # the batch map_and_cluster packs from the FASTA: the words the longest read needs, a mask only when an N is there
+        W = pack.words_for(max(hi, 1))
+        if W < int(words.shape[0]):
+            words = words[:W].contiguous()
+            nmask = None if nmask is None else nmask[:W].contiguous()
+        if nmask is not None and not bool(nmask.any()):
+            nmask = None
+        rs = ReadSet.from_device(words, lens, nmask, None, lo, hi)
+        if sam:
+            seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
+                                    None if nmask is None else nmask.cpu().numpy().view(np.uint64))
+    return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
+                              out_stem, sam, timings)
+
+
+def sample_stem(sample):
+    """convert2Fasta.py:40: a sample column's name up to its first `.`."""
+    return sample.strip().split(".")[0]
+
+
+def _write_fasta(lib, path, words, lens, nmask, rows, extra=()):
+    """mrg_write_predict_fasta: rows = (index, number, count uint32 or uint64) host arrays; extra = (sequence, number, count)
+    of the reads beyond 255 nt, in file order."""
+    from . import _native
+    W, n = words.shape
+    idx, num = (np.ascontiguousarray(a, dtype=np.uint32) for a in rows[:2])
+    cnt = np.ascontiguousarray(rows[2])
+    if cnt.dtype != np.uint64:
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    seqs = (C.c_char_p * max(len(extra), 1))(*[e[0].encode("ascii") for e in extra])
+    e_num = np.array([e[1] for e in extra], dtype=np.uint64)
+    e_cnt = np.array([e[2] for e in extra], dtype=np.uint64)
+    got = lib.mrg_write_predict_fasta(os.fsencode(path), words.ctypes.data, W, n, lens.ctypes.data,
+                                      None if nmask is None else nmask.ctypes.data, n, _ptr(idx), _ptr(num), _ptr(cnt),
+                                      cnt.dtype.itemsize, idx.shape[0], seqs, _ptr(e_num), _ptr(e_cnt), len(extra))
+    if got < 0:
+        _native.check(int(got))
+    return int(got)
+
+
+def candidate_lists(engine, pass_id, lens, quant, min_len, max_len, count_cutoff, timings=None):
+    """The lists of convert2Fasta.py from the arrays (Engine.predict_select once, Engine.predict_sample_reads per sample and
+    list): a dict with n_raw, n_sel, the host rows (index, number, count) of `raw` and `sel` (counts uint64: the totals)
+    and per sample `sample_raw[s]` and `sample_sel[s]` (counts uint32).  timings: a dict that receives `select_ms` and
+    `samples_ms`, between device events (the downloads included)."""
+    import torch
+    ev = None
+    if timings is not None:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+    sel = engine.predict_select(pass_id, lens, quant, min_len, max_len, count_cutoff)
+    quant_d = engine._dev_u32(quant)
+    S = int(quant_d.shape[1]) if quant_d.dim() == 2 else 1
+    total = sel["total"].cpu().numpy().view(np.uint64)
+    out = dict(n_raw=sel["n_raw"], n_sel=sel["n_sel"], sample_raw=[], sample_sel=[])
+    for key in ("raw", "sel"):
+        no = sel[key + "_no"].cpu().numpy().view(np.uint32)
+        idx = np.nonzero(no)[0].astype(np.uint32)
+        out[key] = (idx, no[idx], total[idx])
+    if ev:
+        ev[1].record()
+    for s in range(S):
+        for key, thr in (("raw", 1), ("sel", int(count_cutoff))):
+            rows = engine.predict_sample_reads(quant_d, sel[key + "_no"], s, thr)
+            out["sample_" + key].append(tuple(t.cpu().numpy().view(np.uint32) for t in rows))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        timings.update(select_ms=ev[0].elapsed_time(ev[1]), samples_ms=ev[1].elapsed_time(ev[2]))
+    return out
+
+
+def write_candidate_reads(outdir, sample_list, words, lens, nmask, lists, min_len, max_len, count_cutoff, long_rows=()):
+    """convert2Fasta.py's files for unmapped.csv, from the arrays and the lists of candidate_lists, by the native writer
+    (mrg_write_predict_fasta): unmapped_mirna.fa, unmapped_mirna_raw.fa and per sample unmapped_mirna_<stem>.fa and
+    unmapped_mirna_<stem>_raw.fa in `outdir`, 2 + 2 S files (two samples with one stem share a name; the later one's file
+    stays).  long_rows: (sequence, counts per sample) of the unmapped reads beyond 255 nt in the order of their rows at
+    the end of unmapped.csv; their numbers continue after the packed reads'.  Returns {file name: rows}."""
+    from . import _native
+    lib = _native.load()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    raw_extra, sel_extra = [], []      # (sequence, number, total, counts)
+    j, i = lists["n_raw"], lists["n_sel"]
+    for seq, q in long_rows:
+        q = [int(x) for x in q]
+        total = sum(q)
+        if total >= 1:
+            j += 1
+            raw_extra.append((seq, j, total, q))
+        if int(min_len) <= len(seq) <= int(max_len) and total >= int(count_cutoff):
+            i += 1
+            sel_extra.append((seq, i, total, q))
+    rows = {}
+    rows["unmapped_mirna.fa"] = _write_fasta(lib, os.path.join(outdir, "unmapped_mirna.fa"), words, lens, nm, lists["sel"],
+                                             [e[:3] for e in sel_extra])
+    rows["unmapped_mirna_raw.fa"] = _write_fasta(lib, os.path.join(outdir, "unmapped_mirna_raw.fa"), words, lens, nm,
+                                                 lists["raw"], [e[:3] for e in raw_extra])
+    for key, suffix, extra, thr in (("sel", ".fa", sel_extra, int(count_cutoff)), ("raw", "_raw.fa", raw_extra, 1)):
+        for s, name in enumerate(sample_list):
+            fn = "unmapped_mirna_" + sample_stem(name) + suffix
+            rows[fn] = _write_fasta(lib, os.path.join(outdir, fn), words, lens, nm, lists["sample_" + key][s],
+                                    [(e[0], e[1], e[3][s]) for e in extra if e[3][s] >= thr])
+    return rows
 
 
 def clusters_main(argv):
