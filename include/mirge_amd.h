@@ -927,6 +927,52 @@ int mrg_read_counts_from_names(uint64_t n_reads, const char *names, const uint64
                                uint32_t *counts, int64_t *bad_read);
 
 /*
+ * Predict mode's preliminary trim of the location clusters (reference utils/preTrimClusteredSeq.py and generate_Seq.py,
+ * miRge2.0.py:557-562) over the device arrays of mrg_cluster_bounds / mrg_cluster_assemble (csrc/predict_trim.hip).
+ *
+ *   mrg_predict_trim_temp_bytes  HOST: the bytes of device scratch mrg_predict_trim needs for n_clusters clusters.
+ *   mrg_predict_trim  DEVICE.  d_entry / d_strand / d_start / d_end [n_clusters], d_seq_off [n_clusters + 1] ascending from
+ *       0 to total_len, d_seq [total_len] ASCII.  The repeat table: d_rep_off [n_entries + 1] ascending into d_rep_start /
+ *       d_rep_end [n_elements] (1-based inclusive), an entry's elements sorted stably by start; an entry without elements
+ *       has an empty range.  Per cluster c:
+ *         d_orig        its bytes of d_seq on `+`; on `-` their reverse complement (A<->T, C<->G, any other byte itself)
+ *                       inside the same range [d_seq_off[c], d_seq_off[c + 1]);
+ *         d_flag = 1    iff its length <= len_cutoff, d_orig does not end in six `A` nor begin with six `T`, and neither of
+ *                       the two elements of its entry whose start is nearest d_start[c] shares a coordinate with
+ *                       [d_start[c], d_end[c]] (an entry with one element: that one; with none: passes).  Nearest is by
+ *                       |element start - d_start[c]|; at equal distance the lower element start goes first, then the lower
+ *                       element index.  An element with end < start intersects nothing;
+ *         d_rep         the nearer of the two elements if it intersects, else the other if it does, else -1.  The repeat
+ *                       test is not reached (-1) when the length or the end test fails.
+ *       The retained clusters (flag 1) in cluster order: d_kept [*n_kept of n_clusters] their numbers, d_kept_seq_off
+ *       [*n_kept + 1 of n_clusters + 1] the offsets of their d_orig bytes in d_kept_orig [*kept_len of total_len].
+ *       MRG_ERR_ARG when d_seq_off, d_entry or d_rep_off contradict the sizes given (the outputs are then undefined).
+ *       Limits: n_clusters < 2^31, total_len < 2^38, n_elements < 2^32 - 1.  Synchronises the stream.
+ *   mrg_write_trimmed_clusters  HOST: the three files from host arrays -- the cluster arrays, member lists and read names as
+ *       mrg_write_clusters takes them, flag / rep / orig of mrg_predict_trim, and the repeat names (rep_name_id [n_elements]
+ *       into the n_rep_names strings of rep_names / rep_names_off).  tsv_path: the header `miRClusterID OriginalSeq Flag
+ *       repetitiveElementName` + columns 2.. of mrg_write_clusters' header, one line per cluster (the name is `*` for
+ *       rep -1); fa_path / orig_fa_path: for the clusters with flag 1 `>` id `:` entry `:` start `_` end strand, then the
+ *       sequence / its orig.  *rows = clusters, *kept = FASTA records.  Blocks are formatted in parallel, written in order.
+ */
+int mrg_predict_trim_temp_bytes(uint64_t n_clusters, uint64_t *bytes);
+int mrg_predict_trim(mrg_ctx *ctx, uint64_t n_clusters, const uint32_t *d_entry, const uint8_t *d_strand,
+                     const uint32_t *d_start, const uint32_t *d_end, const uint64_t *d_seq_off, const char *d_seq,
+                     uint64_t total_len, uint32_t n_entries, const uint32_t *d_rep_off, const uint32_t *d_rep_start,
+                     const uint32_t *d_rep_end, uint64_t n_elements, int32_t len_cutoff, uint8_t *d_flag,
+                     int32_t *d_rep, char *d_orig, uint32_t *d_kept, uint64_t *d_kept_seq_off, char *d_kept_orig,
+                     uint64_t *n_kept, uint64_t *kept_len, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_write_trimmed_clusters(const char *tsv_path, const char *fa_path, const char *orig_fa_path, const char *sample,
+                               const mrg_index *const *parts, uint32_t n_parts, uint64_t n_clusters,
+                               const uint32_t *entry, const uint8_t *strand, const uint32_t *start,
+                               const uint32_t *end, const uint64_t *seq_off, const char *seq,
+                               const uint64_t *count_sum, const uint32_t *member_off, const uint32_t *members,
+                               uint64_t n_reads, const char *names, const uint64_t *names_off, const uint8_t *flag,
+                               const int32_t *rep, const char *orig, uint64_t n_elements,
+                               const uint32_t *rep_name_id, uint64_t n_rep_names, const char *rep_names,
+                               const uint64_t *rep_names_off, uint64_t *rows, uint64_t *kept);
+
+/*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are
  * grouped by group_of_entry[ref_id] -- the caller's map from a miRNA library entry to its name with the ".SNP..." suffix

@@ -181,6 +181,16 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_char_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "mrg_read_counts_from_names": (C.c_int, [C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "mrg_predict_trim_temp_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mrg_predict_trim": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mrg_write_trimmed_clusters": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.c_uint32,
+                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mrg_annotate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.POINTER(PassCfg), C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PassStats),

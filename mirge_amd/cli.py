@@ -21,7 +21,10 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     files convert2Fasta makes of unmapped.csv, picked and numbered on the GPU from the arrays; `--novel-clusters` (with
     `-ml 3 -sl 25 -olc 14`; implies `--novel-reads`) moves each sample's two files to
     `unmapped_tmp/unmapped_mirna_<sample>_tmp/` and writes that sample's `..._vs_genome_sorted_clusters.tsv` and
-    `..._vs_genome_sorted.sam` next to them (the genome as for `-ai`; reads of at most 255 nt: `-maxl` above 255 exits 1).
+    `..._vs_genome_sorted.sam` next to them (the genome as for `-ai`; reads of at most 255 nt: `-maxl` above 255 exits 1);
+    `--novel-trim` (with `-clc 30`; implies `--novel-clusters`) adds the preliminary trim of those clusters on the GPU:
+    `..._clusters_trimmed.tsv`, `..._clusters_trimmed.fa` and `..._clusters_trimmed_orig.fa`, the repeat elements read from
+    `<lib>/<sp>/annotation.Libs/<sp>_genome_repeats.tsv` (chr, start, end, name; a missing file = no repeat table).
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -72,12 +75,16 @@ def build_parser():
     p.add_argument("--novel-clusters", dest="novel_clusters", action="store_true",
                    help="extension: --novel-reads, then per sample the genome mapping and the location clusters of its "
                         "candidate reads on the GPU (-ml / -sl / -olc), in unmapped_tmp/unmapped_mirna_<sample>_tmp/")
+    p.add_argument("--novel-trim", dest="novel_trim", action="store_true",
+                   help="extension: --novel-clusters, then the preliminary trim of the clusters on the GPU (-clc; the repeat "
+                        "elements of <lib>/<sp>/annotation.Libs/<sp>_genome_repeats.tsv) -- the three _clusters_trimmed files")
     p.add_argument("-minl", default="16", dest="minLength", metavar="<int>")
     p.add_argument("-maxl", default="25", dest="maxLength", metavar="<int>")
     p.add_argument("-cc", default="2", dest="countCutoff", metavar="<int>")
     p.add_argument("-ml", default="3", dest="mapping_loc", metavar="<int>")
     p.add_argument("-sl", default="25", dest="seedLength", metavar="<int>")
     p.add_argument("-olc", default="14", dest="overlapLenCutoff", metavar="<int>")
+    p.add_argument("-clc", default="30", dest="clusterSeqLenCutoff", metavar="<int>")
     p.add_argument("--gpu", type=int, default=0, help="device index (default 0)")
     p.add_argument("--device-ingest", action="store_true",
                    help="split, trim and pack the FASTQ records on the GPU (raw text blocks are uploaded; `-ad none` / `-ad +N` "
@@ -190,7 +197,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
     sp, lib = args.species, args.libraryPath
     if args.trf_output and sp != "human":  # MAIN:161-163
         _die("tRF detection is only supported for the species of human. Please check it.")
-    novel_clusters = bool(getattr(args, "novel_clusters", False))
+    novel_trim = bool(getattr(args, "novel_trim", False))
+    novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
     novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
     novel_genome = None
 
@@ -206,6 +214,13 @@ def annotate_main(args, engine_factory=None, materialize=False):
             novel_die("The values of -minl, -maxl, -cc, -ml, -sl and -olc must be integers. Please check them.")
         if novel_min < 0 or novel_min > novel_max or novel_cc < 1:
             novel_die("-minl must not exceed -maxl and -cc must be at least 1. Please check them.")
+    if novel_trim:
+        try:
+            cluster_len_cutoff = int(args.clusterSeqLenCutoff)
+        except ValueError:
+            novel_die("The value of -clc must be an integer. Please check it.")
+        if cluster_len_cutoff < 0:
+            novel_die("-clc must not be negative. Please check it.")
     if novel_clusters:
         if novel_max > 255:
             novel_die("-maxl %d: the genome stage of --novel-clusters takes reads of at most 255 nt. Please check it." % novel_max)
@@ -521,6 +536,10 @@ def annotate_main(args, engine_factory=None, materialize=False):
         if novel_clusters:
             a_reads = (shard.words, shard.lens, shard.nmask) if on_device else (h_words, h_lens, h_nmask)
             stems = [predict.sample_stem(name) for name in sample_list]
+            trim = None
+            if novel_trim:   # MAIN:557-562; a missing file is the reference's "no repeat table"
+                trim = (predict.load_repeats(predict.repeats_path(lib, sp), predict.genome_libraries(engine, novel_genome)[1]),
+                        cluster_len_cutoff)
             for s, stem in enumerate(stems):
                 if stem in stems[s + 1:]:   # (a later sample wrote this stem's files)
                     continue
@@ -531,7 +550,7 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 idx, num, _cnt = lists["sample_sel"][s]
                 g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
                 predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
-                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem))
+                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

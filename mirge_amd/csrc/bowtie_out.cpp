@@ -280,27 +280,27 @@ unsigned writer_threads(uint64_t n_blocks) {
   return (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
 }
 
-// format(b, text) for every block b < n_blocks on worker threads; the texts go out in block order.
-// turn = the block whose text goes out next: a worker formats its block, waits for its turn, writes, passes the turn on
-template <class Format>
-void write_blocks_in_order(OutFile& file, uint64_t n_blocks, Format format) {
+// format(b, texts) for every block b < n_blocks on worker threads; texts[f] goes to files[f], every file in block order.
+// turn = the block whose texts go out next: a worker formats its block, waits for its turn, writes, passes the turn on
+template <size_t N, class Format>
+void write_file_blocks_in_order(OutFile* const (&files)[N], uint64_t n_blocks, Format format) {
   const unsigned n_threads = writer_threads(n_blocks);
   std::atomic<uint64_t> next{0}, turn{0};
   std::atomic<bool> stop{false};
   std::vector<std::exception_ptr> failed(n_threads);
   auto worker = [&](unsigned t) {
-    std::string text;
+    std::string texts[N];
     try {
       for (;;) {
         const uint64_t b = next.fetch_add(1, std::memory_order_relaxed);
         if (b >= n_blocks || stop.load(std::memory_order_relaxed)) break;
-        text.clear();
-        format(b, text);
+        for (std::string& text : texts) text.clear();
+        format(b, texts);
         while (turn.load(std::memory_order_acquire) != b) {
           if (stop.load(std::memory_order_relaxed)) return;
           std::this_thread::yield();
         }
-        file.write_all(text.data(), text.size());
+        for (size_t f = 0; f < N; ++f) files[f]->write_all(texts[f].data(), texts[f].size());
         turn.store(b + 1, std::memory_order_release);
       }
     } catch (...) {
@@ -329,6 +329,13 @@ void write_blocks_in_order(OutFile& file, uint64_t n_blocks, Format format) {
   }
   for (unsigned t = 0; t < n_threads; ++t)
     if (failed[t]) std::rethrow_exception(failed[t]);
+}
+
+// one file: format(b, text)
+template <class Format>
+void write_blocks_in_order(OutFile& file, uint64_t n_blocks, Format format) {
+  OutFile* const files[1] = {&file};
+  write_file_blocks_in_order(files, n_blocks, [&](uint64_t b, std::string (&texts)[1]) { format(b, texts[0]); });
 }
 
 void sam_sq_lines(const std::vector<const FmIndex*>& parts, std::string& h) {
@@ -462,6 +469,93 @@ void write_clusters(const char* path, const char* sample, const std::vector<cons
   });
   file.close();
   *rows = n_clusters;
+}
+
+// preTrimClusteredSeq.py's table and generate_Seq.py's two FASTA files from the cluster arrays and the arrays of mrg_predict_trim
+void write_trimmed_clusters(const TrimmedClustersArgs& a, uint64_t* rows, uint64_t* kept) {
+  const Entries entries(*a.parts);
+  for (uint64_t c = 0; c < a.n_clusters; ++c) {
+    if (a.seq_off[c + 1] < a.seq_off[c]) throw std::invalid_argument("cluster sequence offsets out of order");
+    if (a.rep[c] >= 0 && (uint64_t)a.rep[c] >= a.n_elements) throw std::invalid_argument("repeat element out of range");
+    if (a.rep[c] >= 0 && a.rep_name_id[a.rep[c]] >= a.n_rep_names) throw std::invalid_argument("repeat name out of range");
+  }
+  OutFile tsv(a.tsv_path), fa(a.fa_path), orig_fa(a.orig_fa_path);
+  const std::string h =
+      "miRClusterID\tOriginalSeq\tFlag\trepetitiveElementName\tChr\tStrand\tStart\tEnd\tSequence\tSequenceLenght\tCoutOfReads\t"
+      "CountOfMembers\tMembers\n";
+  tsv.write_all(h.data(), h.size());
+  constexpr uint64_t kBlock = 1u << 13;
+  std::atomic<uint64_t> n_kept{0};
+  OutFile* const files[3] = {&tsv, &fa, &orig_fa};
+  write_file_blocks_in_order(files, (a.n_clusters + kBlock - 1) / kBlock, [&](uint64_t b, std::string (&texts)[3]) {
+    std::string id, where;
+    uint64_t k = 0;
+    for (uint64_t c = b * kBlock; c < std::min(a.n_clusters, (b + 1) * kBlock); ++c) {
+      const uint64_t len = a.seq_off[c + 1] - a.seq_off[c];
+      id = a.sample;
+      id += ":miRCluster_";
+      put_u64(id, c + 1);
+      id += '_';
+      put_u64(id, len);
+      const std::string& chr = entries.name(a.entry[c]);
+      std::string& text = texts[0];
+      text += id;
+      text += '\t';
+      text.append(a.orig + a.seq_off[c], (size_t)len);
+      text += a.flag[c] ? "\t1\t" : "\t0\t";
+      if (a.rep[c] < 0) {
+        text += '*';
+      } else {
+        const uint32_t nm = a.rep_name_id[a.rep[c]];
+        text.append(a.rep_names + a.rep_names_off[nm], (size_t)(a.rep_names_off[nm + 1] - a.rep_names_off[nm]));
+      }
+      text += '\t';
+      text += chr;
+      text += a.strand[c] ? "\t-\t" : "\t+\t";
+      put_u64(text, a.start[c]);
+      text += '\t';
+      put_u64(text, a.end[c]);
+      text += '\t';
+      text.append(a.seq + a.seq_off[c], (size_t)len);
+      text += '\t';
+      put_u64(text, len);
+      text += '\t';
+      put_u64(text, a.count_sum[c]);
+      text += '\t';
+      put_u64(text, a.member_off[c + 1] - a.member_off[c]);
+      text += '\t';
+      for (uint32_t m = a.member_off[c]; m < a.member_off[c + 1]; ++m) {
+        const uint32_t r = a.members[m];
+        if (r >= a.n_reads) throw std::runtime_error("cluster member of an unknown read");
+        if (m != a.member_off[c]) text += ',';
+        text.append(a.names + a.names_off[r], (size_t)(a.names_off[r + 1] - a.names_off[r]));
+      }
+      text += '\n';
+      if (!a.flag[c]) continue;
+      ++k;
+      where = ">";
+      where += id;
+      where += ':';
+      where += chr;
+      where += ':';
+      put_u64(where, a.start[c]);
+      where += '_';
+      put_u64(where, a.end[c]);
+      where += a.strand[c] ? "-\n" : "+\n";
+      texts[1] += where;
+      texts[1].append(a.seq + a.seq_off[c], (size_t)len);
+      texts[1] += '\n';
+      texts[2] += where;
+      texts[2].append(a.orig + a.seq_off[c], (size_t)len);
+      texts[2] += '\n';
+    }
+    n_kept.fetch_add(k, std::memory_order_relaxed);
+  });
+  tsv.close();
+  fa.close();
+  orig_fa.close();
+  *rows = a.n_clusters;
+  *kept = n_kept.load();
 }
 
 // the integer between the first and the second '_' of every read name (`mir<k>_<count>`, reference convert2Fasta.py:131)

@@ -24,6 +24,7 @@
 #include "fm_index.hpp"
 #include "a2i_align.hpp"
 #include "collapsed_order.hpp"
+#include "predict_trim.hpp"
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
@@ -3017,6 +3018,112 @@ int mrg_read_counts_from_names(uint64_t n_reads, const char* names, const uint64
   if (*bad_read >= 0)
     return fail(MRG_ERR_FORMAT, "mrg_read_counts_from_names: read %lld has no `_<count>` field below 2^32 in its name", (long long)*bad_read);
   return MRG_OK;
+}
+
+// ------------------------------------------------- predict mode: the preliminary trim (csrc/predict_trim.hip)
+namespace {
+// mrg_predict_trim's scratch: the stat words, three uint32 arrays and one uint64 array of n + 1, the scans' own scratch
+struct TrimScratch {
+  size_t flag32, rank, keep_len, keep_off, scan, total;
+  explicit TrimScratch(uint64_t n) {
+    const size_t words = (size_t)((n + 1 + 1) & ~1ull) * sizeof(uint32_t);  // (an even count: the uint64 array stays aligned)
+    flag32 = mrg::kTrimStatWords * sizeof(uint32_t);
+    rank = flag32 + words;
+    keep_len = rank + words;
+    keep_off = keep_len + words;
+    scan = keep_off + (size_t)(n + 1) * sizeof(uint64_t);
+    total = scan + ((mrg::prims::scan_temp_bytes(n + 1) + 7) & ~(size_t)7);
+  }
+};
+constexpr uint64_t kTrimMaxClusters = (1ull << 31) - 1, kTrimMaxBytes = (1ull << 38) - 1;
+}  // namespace
+
+int mrg_predict_trim_temp_bytes(uint64_t n_clusters, uint64_t* bytes) {
+  if (!bytes) return fail(MRG_ERR_ARG, "mrg_predict_trim_temp_bytes: null argument");
+  if (n_clusters > kTrimMaxClusters)
+    return fail(MRG_ERR_ARG, "mrg_predict_trim_temp_bytes: %llu clusters; the limit is 2^31 - 1", (unsigned long long)n_clusters);
+  *bytes = TrimScratch(n_clusters).total;
+  return MRG_OK;
+}
+
+int mrg_predict_trim(mrg_ctx* ctx, uint64_t n_clusters, const uint32_t* d_entry, const uint8_t* d_strand, const uint32_t* d_start,
+                     const uint32_t* d_end, const uint64_t* d_seq_off, const char* d_seq, uint64_t total_len, uint32_t n_entries,
+                     const uint32_t* d_rep_off, const uint32_t* d_rep_start, const uint32_t* d_rep_end, uint64_t n_elements,
+                     int32_t len_cutoff, uint8_t* d_flag, int32_t* d_rep, char* d_orig, uint32_t* d_kept, uint64_t* d_kept_seq_off,
+                     char* d_kept_orig, uint64_t* n_kept, uint64_t* kept_len, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_trim";
+  if (!ctx || !n_kept || !kept_len) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_kept = *kept_len = 0;
+  if (n_clusters > kTrimMaxClusters) return fail(MRG_ERR_ARG, "%s: %llu clusters; the limit is 2^31 - 1", fn, (unsigned long long)n_clusters);
+  if (total_len > kTrimMaxBytes) return fail(MRG_ERR_ARG, "%s: %llu sequence bytes; the limit is 2^38 - 1", fn, (unsigned long long)total_len);
+  if (n_elements >= 0xffffffffull) return fail(MRG_ERR_ARG, "%s: %llu repeat elements; the limit is 2^32 - 2", fn, (unsigned long long)n_elements);
+  if (len_cutoff < 0) return fail(MRG_ERR_ARG, "%s: the length cutoff must not be negative (got %d)", fn, len_cutoff);
+  if (!d_seq_off || !d_kept_seq_off || !d_tmp || !d_rep_off) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_clusters && (!d_entry || !d_strand || !d_start || !d_end || !d_flag || !d_rep || !d_kept))
+    return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (total_len && (!n_clusters || !d_seq || !d_orig || !d_kept_orig)) return fail(MRG_ERR_ARG, "%s: null sequence buffers", fn);
+  if (n_elements && (!d_rep_start || !d_rep_end)) return fail(MRG_ERR_ARG, "%s: null repeat table", fn);
+  const TrimScratch sc(n_clusters);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_trim_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
+  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  uint32_t* keep_len = reinterpret_cast<uint32_t*>(base + sc.keep_len);
+  uint64_t* keep_off = reinterpret_cast<uint64_t*>(base + sc.keep_off);
+  void* scan_tmp = base + sc.scan;
+  const mrg::TrimClusters c{(uint32_t)n_clusters, d_entry, d_strand, d_start, d_end, d_seq_off, d_seq, total_len};
+  const mrg::TrimRepeats r{n_entries, (uint32_t)n_elements, d_rep_off, d_rep_start, d_rep_end};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kTrimStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::trim_orig_launch(c, d_orig, stat, st));
+  HIP_TRY(mrg::trim_flags_launch(c, r, d_orig, (uint32_t)len_cutoff, d_flag, d_rep, flag32, keep_len, stat, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_clusters + 1, scan_tmp, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(keep_len, keep_off, n_clusters + 1, scan_tmp, st));
+  HIP_TRY(mrg::trim_compact_launch((uint32_t)n_clusters, rank, keep_off, d_kept, d_kept_seq_off, st));
+  HIP_TRY(mrg::trim_gather_launch(c, d_orig, rank, keep_off, d_kept_orig, st));
+  uint32_t h_stat[mrg::kTrimStatWords] = {0, 0, 0, 0}, h_kept = 0;
+  uint64_t h_len = 0;
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h_kept, rank + n_clusters, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h_len, keep_off + n_clusters, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_stat[mrg::kTrimStatBadSeqOff]) return fail(MRG_ERR_ARG, "%s: d_seq_off does not ascend from 0 to total_len", fn);
+  if (h_stat[mrg::kTrimStatBadEntry]) return fail(MRG_ERR_ARG, "%s: a cluster on an entry beyond the %u of the repeat table", fn, n_entries);
+  if (h_stat[mrg::kTrimStatBadTable]) return fail(MRG_ERR_ARG, "%s: d_rep_off does not ascend inside the %llu elements", fn, (unsigned long long)n_elements);
+  *n_kept = h_kept;
+  *kept_len = h_len;
+  return MRG_OK;
+}
+
+int mrg_write_trimmed_clusters(const char* tsv_path, const char* fa_path, const char* orig_fa_path, const char* sample,
+                               const mrg_index* const* parts, uint32_t n_parts, uint64_t n_clusters, const uint32_t* entry,
+                               const uint8_t* strand, const uint32_t* start, const uint32_t* end, const uint64_t* seq_off, const char* seq,
+                               const uint64_t* count_sum, const uint32_t* member_off, const uint32_t* members, uint64_t n_reads,
+                               const char* names, const uint64_t* names_off, const uint8_t* flag, const int32_t* rep, const char* orig,
+                               uint64_t n_elements, const uint32_t* rep_name_id, uint64_t n_rep_names, const char* rep_names,
+                               const uint64_t* rep_names_off, uint64_t* rows, uint64_t* kept) {
+  const char* fn = "mrg_write_trimmed_clusters";
+  if (!tsv_path || !fa_path || !orig_fa_path || !sample || !rows || !kept) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_clusters && (!entry || !strand || !start || !end || !seq_off || !seq || !count_sum || !member_off || !members || !names ||
+                     !names_off || !flag || !rep || !orig))
+    return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (n_elements && (!rep_name_id || !rep_names || !rep_names_off)) return fail(MRG_ERR_ARG, "%s: null repeat names", fn);
+  std::vector<const mrg::FmIndex*> ix;
+  int rc = index_list(fn, parts, n_parts, &ix);
+  if (rc != MRG_OK) return rc;
+  try {
+    const mrg::TrimmedClustersArgs a{tsv_path, fa_path,   orig_fa_path, sample,  &ix,   n_clusters, entry, strand,     start,
+                                     end,      seq_off,   seq,          count_sum, member_off, members, n_reads, names, names_off,
+                                     flag,     rep,       orig,         n_elements, rep_name_id, n_rep_names, rep_names, rep_names_off};
+    mrg::write_trimmed_clusters(a, rows, kept);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
 }
 
 // ----------------------------------------------------- host convenience

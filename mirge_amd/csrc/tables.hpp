@@ -36,6 +36,32 @@ void write_clusters(const char* path, const char* sample, const std::vector<cons
                     const uint32_t* entry, const uint8_t* strand, const uint32_t* start, const uint32_t* end, const uint64_t* seq_off,
                     const char* seq, const uint64_t* count_sum, const uint32_t* member_off, const uint32_t* members, uint64_t n_reads,
                     const char* names, const uint64_t* names_off, uint64_t* rows);
+// mrg_write_trimmed_clusters: the cluster arrays of write_clusters plus flag / rep / orig of mrg_predict_trim and the repeat
+// table's names.  Throws std::invalid_argument (arrays that contradict each other: nothing is written) or std::runtime_error.
+struct TrimmedClustersArgs {
+  const char *tsv_path, *fa_path, *orig_fa_path, *sample;
+  const std::vector<const FmIndex*>* parts;
+  uint64_t n_clusters;
+  const uint32_t* entry;
+  const uint8_t* strand;
+  const uint32_t *start, *end;
+  const uint64_t* seq_off;
+  const char* seq;
+  const uint64_t* count_sum;
+  const uint32_t *member_off, *members;
+  uint64_t n_reads;
+  const char* names;
+  const uint64_t* names_off;
+  const uint8_t* flag;
+  const int32_t* rep;  // element index or -1
+  const char* orig;
+  uint64_t n_elements;
+  const uint32_t* rep_name_id;  // [n_elements]
+  uint64_t n_rep_names;
+  const char* rep_names;
+  const uint64_t* rep_names_off;  // [n_rep_names + 1]
+};
+void write_trimmed_clusters(const TrimmedClustersArgs& a, uint64_t* rows, uint64_t* kept);
 int64_t read_counts_from_names(uint64_t n_reads, const char* names, const uint64_t* names_off, uint32_t* counts);
 
 }  // namespace mrg

@@ -1058,7 +1058,7 @@ class Engine:
                 suppressed)
 
     def cluster_valid(self, reads, libs, counts, entry_keep=None, threshold=14, strands=2, stratum_mode=STRATUM_ALL, m=0,
-                      seed_len=28, max_mm_seed=0, max_mm_total=2, sorted_rows=False, timings=None):
+                      seed_len=28, max_mm_seed=0, max_mm_total=2, sorted_rows=False, timings=None, keep_device=False):
         """Predict mode's location clusters of the listing of list_valid (same reads, libraries, entry numbering and
         policy; `-m` and the best stratum are decided over all parts from the per-read counts, as there), without the
         alignment rows leaving the device: mrg_list_valid_fill per part, then mrg_cluster_keys / _sort / _scan /
@@ -1070,7 +1070,9 @@ class Engine:
         [n] bool, n_rows, n_valid (rows on kept entries); clusters are ordered by (entry, strand, start).
         sorted_rows=True adds "rows" = (read, entry, offset, strand, mm) of every alignment ordered by (entry, offset,
         strand, read) -- a coordinate-sorted SAM file's order.  timings: a dict, or None; gets count_s / fill_s as
-        list_valid does and the device milliseconds sort_ms / scan_ms / assemble_ms."""
+        list_valid does and the device milliseconds sort_ms / scan_ms / assemble_ms.
+        keep_device=True adds "device": the cluster arrays as device tensors for predict_trim (entry, strand, start, end,
+        seq_off, seq, and the ints n_clusters, total_len), None when there is no alignment row."""
         import time
         torch = _torch()
         n = reads.n
@@ -1118,6 +1120,8 @@ class Engine:
         if sorted_rows:
             out["rows"] = (np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
                            np.zeros(0, np.uint8))
+        if keep_device:
+            out["device"] = None
         if T == 0:
             return out
 
@@ -1211,6 +1215,9 @@ class Engine:
                    seq_off=c_soff.cpu().numpy()[:K + 1].view(np.uint64), seq=seq.cpu().numpy()[:int(total.value)].tobytes(),
                    count_sum=c_sum.cpu().numpy()[:K].view(np.uint64), member_off=c_moff.cpu().numpy()[:K + 1].view(np.uint32),
                    members=member.cpu().numpy()[:V].view(np.uint32))
+        if keep_device:
+            out["device"] = dict(entry=c_entry, strand=c_strand, start=c_start, end=c_end, seq_off=c_soff, seq=seq, n_clusters=K,
+                                 total_len=int(total.value))
         if timings is not None:
             ev[-1].synchronize()
             for name, a, b in (("sort_ms", 0, 1), ("scan_ms", 1, 2), ("assemble_ms", 2, 3)):
@@ -1225,6 +1232,79 @@ class Engine:
                                                     r_strand.data_ptr(), r_mm.data_ptr(), st))
             out["rows"] = (r_read.cpu().numpy()[:T].view(np.uint32), r_entry.cpu().numpy()[:T], r_pos.cpu().numpy()[:T],
                            r_strand.cpu().numpy()[:T], r_mm.cpu().numpy()[:T])
+        return out
+
+    def predict_trim(self, clusters, repeats, cutoff=30, timings=None):
+        """Predict mode's preliminary trim of the location clusters (mrg_predict_trim; the rules of preTrimClusteredSeq.py
+        and generate_Seq.py).  clusters: the "device" dict of cluster_valid(keep_device=True), or a dict of host arrays
+        entry, strand, start, end, seq_off [K + 1], seq (bytes) as cluster_valid returns them (uploaded).  repeats: the
+        dict of predict.load_repeats (rep_off [entries + 1], start, end; uploaded once per device).
+        Returns a dict: the host arrays flag (uint8 [K]), rep (int32 [K]: the element's index in the table, -1 = `*`),
+        orig (bytes), kept (uint32: the retained clusters), kept_seq_off (uint64 [kept + 1]), kept_orig (bytes), and
+        "device" with the same as device tensors.  timings: a dict that receives trim_ms (device events) and
+        download_ms."""
+        torch = _torch()
+        dev = self.device
+        if "n_clusters" in clusters:
+            d = clusters
+            K, total = int(d["n_clusters"]), int(d["total_len"])
+            self._expect(d["entry"], torch.int32, "predict_trim: entry")
+            self._expect(d["strand"], torch.uint8, "predict_trim: strand")
+            self._expect(d["start"], torch.int32, "predict_trim: start")
+            self._expect(d["end"], torch.int32, "predict_trim: end")
+            self._expect(d["seq_off"], torch.int64, "predict_trim: seq_off")
+            self._expect(d["seq"], torch.uint8, "predict_trim: seq")
+        else:
+            K = int(len(clusters["entry"]))
+            seq = np.array(np.frombuffer(bytes(clusters["seq"]), dtype=np.uint8))   # (a copy: torch wants writable memory)
+            total = int(seq.shape[0])
+            soff = np.ascontiguousarray(clusters["seq_off"], dtype=np.uint64)
+            if soff.shape != (K + 1,) or any(len(clusters[k]) != K for k in ("strand", "start", "end")):
+                raise ValueError("predict_trim: entry, strand, start and end [K] and seq_off [K + 1] must match")
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            pad = lambda a: a if a.shape[0] else np.zeros(1, a.dtype)
+            d = dict(entry=self._dev_u32(pad(np.asarray(clusters["entry"], dtype=np.uint32))),
+                     strand=up(pad(np.asarray(clusters["strand"], dtype=np.uint8))),
+                     start=self._dev_u32(pad(np.asarray(clusters["start"], dtype=np.uint32))),
+                     end=self._dev_u32(pad(np.asarray(clusters["end"], dtype=np.uint32))),
+                     seq_off=up(soff.view(np.int64)), seq=up(pad(seq)))
+        if min(d[k].numel() for k in ("entry", "strand", "start", "end")) < K or d["seq_off"].numel() < K + 1 or d["seq"].numel() < total:
+            raise ValueError("predict_trim: a cluster array is shorter than the %d clusters or %d bytes given" % (K, total))
+        cache = repeats.setdefault("_device", {})
+        if str(dev) not in cache:
+            pad = lambda a: a if a.shape[0] else np.zeros(1, np.uint32)
+            cache[str(dev)] = tuple(self._dev_u32(pad(np.ascontiguousarray(repeats[k], dtype=np.uint32))) for k in ("rep_off", "start", "end"))
+        r_off, r_start, r_end = cache[str(dev)]
+        n_entries, n_elements = int(len(repeats["rep_off"])) - 1, int(len(repeats["start"]))
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_trim_temp_bytes(K, C.byref(need)))
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
+        tmp = e(need.value, torch.uint8)
+        flag, rep, orig = e(K, torch.uint8), e(K, torch.int32), e(total, torch.uint8)
+        kept, kept_off, kept_orig = e(K, torch.int32), e(K + 1, torch.int64), e(total, torch.uint8)
+        n_kept, kept_len = C.c_uint64(), C.c_uint64()
+        ev = None
+        if timings is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record(torch.cuda.current_stream(dev))
+        check(self._lib.mrg_predict_trim(self._h, K, d["entry"].data_ptr(), d["strand"].data_ptr(), d["start"].data_ptr(),
+                                         d["end"].data_ptr(), d["seq_off"].data_ptr(), d["seq"].data_ptr(), total, n_entries,
+                                         r_off.data_ptr(), r_start.data_ptr(), r_end.data_ptr(), n_elements, int(cutoff),
+                                         flag.data_ptr(), rep.data_ptr(), orig.data_ptr(), kept.data_ptr(), kept_off.data_ptr(),
+                                         kept_orig.data_ptr(), C.byref(n_kept), C.byref(kept_len), tmp.data_ptr(), need.value,
+                                         self._stream_ptr()))
+        nk, kl = int(n_kept.value), int(kept_len.value)
+        if ev:
+            ev[1].record(torch.cuda.current_stream(dev))
+        out = dict(flag=flag.cpu().numpy()[:K], rep=rep.cpu().numpy()[:K], orig=orig.cpu().numpy()[:total].tobytes(),
+                   kept=kept.cpu().numpy()[:nk].view(np.uint32), kept_seq_off=kept_off.cpu().numpy()[:nk + 1].view(np.uint64),
+                   kept_orig=kept_orig.cpu().numpy()[:kl].tobytes(),
+                   device=dict(flag=flag, rep=rep, orig=orig, kept=kept, kept_seq_off=kept_off, kept_orig=kept_orig, n_kept=nk,
+                               kept_len=kl))
+        if ev:
+            ev[2].record(torch.cuda.current_stream(dev))
+            ev[2].synchronize()
+            timings.update(trim_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
         return out
 
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):

@@ -12,6 +12,16 @@ so the samtools view / sort / index / view round trip of this stage is gone.  Ro
 alignments with equal (entry, strand, position) is read order: a choice, not pinned against a real `samtools sort`.
 
     python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> -m 3 -l 25 --overlap 14 -o <out_stem> [--no-sam]
+                                         [--trim [--repeats FILE] [-clc 30]]
+
+With `trim=(repeats, cutoff)` / `--trim` the next two calls of the reference (preTrimClusteredSeq, generate_Seq; miRge2.0.py:557-562)
+run over the same device arrays (Engine.predict_trim = mrg_predict_trim; mrg_write_trimmed_clusters) and add
+
+    <out_stem>_vs_genome_sorted_clusters_trimmed.tsv        OriginalSeq, Flag and repetitiveElementName in front of every row
+    <out_stem>_vs_genome_sorted_clusters_trimmed.fa         the retained clusters' sequences
+    <out_stem>_vs_genome_sorted_clusters_trimmed_orig.fa    ... and their OriginalSeq
+
+The repeat elements come from a four-column tab-separated file (load_repeats), not from the reference's pickle.
 
 The device is $MIRGE_AMD_GPU (default 0).  Limits: reads up to 255 nt, fewer than 2^32 - 1 alignment rows, positions
 below 2^31; beyond them the call fails naming the limit and writes nothing.
@@ -127,6 +137,113 @@ def write_sorted_sam(path, parts, names, seqs, rows, suppressed, m, threads=None
     return dict(processed=int(summary[0]), aligned=int(summary[1]), suppressed=int(summary[2]), reported=int(summary[3]))
 
 
+def repeats_path(lib, species):
+    """Where `annotate --novel-trim` looks for the repeat elements of a species."""
+    return os.path.join(lib, species, "annotation.Libs", "%s_genome_repeats.tsv" % species)
+
+
+def load_repeats(path, parts):
+    """The repeat elements of a genome as flat arrays.  path: a tab-separated file of `chr  start  end  name` lines (1-based
+    inclusive coordinates; lines starting with `#` and a first line `chr start end name` are skipped); None or a missing file
+    is an empty table, as the reference's IOError branch leaves every chromosome without one.  parts: the genome's FmIndex
+    list, whose entry names are the chromosomes; rows of a chromosome the genome lacks are dropped.
+    Returns a dict: rep_off (uint32 [entries + 1]: entry e owns elements rep_off[e] .. rep_off[e + 1]), start, end, name_id
+    (uint32 per element, sorted stably by start inside an entry), names (list), names_blob / names_off (uint64), parts."""
+    entries = [nm for ix in parts for nm in ix.names]
+    number = {}
+    for i, nm in enumerate(entries):
+        number.setdefault(nm, i)
+    ent, start, end, name_id, names, ids = [], [], [], [], [], {}
+    lines = []
+    if path is not None and os.path.isfile(path):
+        with open(path) as fh:
+            lines = fh.read().split("\n")
+    for ln, line in enumerate(lines, 1):
+        if not line or line.startswith("#"):
+            continue
+        f = line.rstrip("\r").split("\t")
+        if ln == 1 and f == ["chr", "start", "end", "name"]:
+            continue
+        try:
+            if len(f) != 4:
+                raise ValueError
+            s0, e0 = int(f[1]), int(f[2])
+            if not (0 <= s0 < 2 ** 32 and 0 <= e0 < 2 ** 32):
+                raise ValueError
+        except ValueError:
+            raise ValueError("%s line %d: expected `chr<TAB>start<TAB>end<TAB>name` with coordinates in [0, 2^32)" % (path, ln))
+        e = number.get(f[0])
+        if e is None:
+            continue
+        k = ids.get(f[3])
+        if k is None:
+            k = ids[f[3]] = len(names)
+            names.append(f[3])
+        ent.append(e)
+        start.append(s0)
+        end.append(e0)
+        name_id.append(k)
+    ent, start = np.array(ent, dtype=np.int64), np.array(start, dtype=np.uint32)
+    order = np.lexsort((start, ent))          # (stable: rows of one entry and start keep the file's order)
+    rep_off = np.zeros(len(entries) + 1, dtype=np.uint32)
+    np.cumsum(np.bincount(ent, minlength=len(entries)), out=rep_off[1:])
+    nb, no = bowtie._blob(names)
+    return dict(rep_off=rep_off, start=start[order], end=np.array(end, dtype=np.uint32)[order],
+                name_id=np.array(name_id, dtype=np.uint32)[order], names=names, names_blob=nb, names_off=no, parts=parts)
+
+
+def write_trimmed_clusters(stem, sample, names, cl, trimmed, repeats, threads=None):
+    """mrg_write_trimmed_clusters: `<stem>_trimmed.tsv`, `<stem>_trimmed.fa` and `<stem>_trimmed_orig.fa` from the arrays of
+    Engine.cluster_valid (cl), Engine.predict_trim (trimmed: flag, rep, orig) and load_repeats.  Returns (rows, retained)."""
+    from . import _native
+    lib = _native.load()
+    parts = repeats["parts"]
+    nb, no, n_reads = _blob(names)
+    hs = (C.c_void_p * max(len(parts), 1))(*[p._h.value for p in parts])
+    arr = {k: np.ascontiguousarray(cl[k], dtype=dt) for k, dt in
+           (("entry", np.uint32), ("strand", np.uint8), ("start", np.uint32), ("end", np.uint32), ("seq_off", np.uint64),
+            ("count_sum", np.uint64), ("member_off", np.uint32), ("members", np.uint32))}
+    K = len(arr["entry"])
+    seq = np.frombuffer(bytes(cl["seq"]), dtype=np.uint8)
+    orig = np.frombuffer(bytes(trimmed["orig"]), dtype=np.uint8)
+    flag = np.ascontiguousarray(trimmed["flag"], dtype=np.uint8)
+    rep = np.ascontiguousarray(trimmed["rep"], dtype=np.int32)
+    if flag.shape != (K,) or rep.shape != (K,) or orig.shape != seq.shape or arr["seq_off"].shape != (K + 1,) or \
+            int(arr["seq_off"][-1]) != seq.shape[0]:
+        raise ValueError("write_trimmed_clusters: flag and rep [K], orig and seq [seq_off[K]] must match the clusters")
+    name_id = np.ascontiguousarray(repeats["name_id"], dtype=np.uint32)
+    rn_off = np.ascontiguousarray(repeats["names_off"], dtype=np.uint64)
+    rows, kept = C.c_uint64(), C.c_uint64()
+    with _writer_threads(threads):
+        _native.check(lib.mrg_write_trimmed_clusters(
+            os.fsencode(stem + "_trimmed.tsv"), os.fsencode(stem + "_trimmed.fa"), os.fsencode(stem + "_trimmed_orig.fa"),
+            sample.encode(), hs, len(parts), K, _ptr(arr["entry"]), _ptr(arr["strand"]), _ptr(arr["start"]), _ptr(arr["end"]),
+            arr["seq_off"].ctypes.data, _ptr(seq), _ptr(arr["count_sum"]), arr["member_off"].ctypes.data, _ptr(arr["members"]),
+            n_reads, nb, no.ctypes.data, _ptr(flag), _ptr(rep), _ptr(orig), len(name_id), _ptr(name_id), len(rn_off) - 1,
+            repeats["names_blob"], rn_off.ctypes.data, C.byref(rows), C.byref(kept)))
+    return int(rows.value), int(kept.value)
+
+
+def trim_clusters(engine, cl, repeats, clusterSeqLenCutoff, out_stem, names, threads=None, timings=None):
+    """The reference's miRge2.0.py:557-562 over the clusters of Engine.cluster_valid (cl; with keep_device=True its arrays
+    are taken where they are, else uploaded): preTrimClusteredSeq(repeats, <out_stem>_vs_genome_sorted_clusters.tsv,
+    clusterSeqLenCutoff) and generate_Seq.  Writes `<out_stem>_vs_genome_sorted_clusters_trimmed.tsv`, `..._trimmed.fa` and
+    `..._trimmed_orig.fa`; returns Engine.predict_trim's dict (flag, rep, orig and the retained arrays) plus n_retained.
+    repeats: load_repeats' dict over the genome's parts; names: the reads' as write_clusters takes them.  timings gets
+    trim_ms / download_ms (device events) and write_s."""
+    import time
+    cutoff = int(clusterSeqLenCutoff)
+    if cutoff < 0:
+        raise ValueError("clusterSeqLenCutoff must not be negative")
+    t = engine.predict_trim(cl.get("device") or cl, repeats, cutoff, timings=timings)
+    sam_path = out_stem + "_vs_genome_sorted.sam"
+    t0 = time.perf_counter()
+    _, t["n_retained"] = write_trimmed_clusters(sam_path[:-4] + "_clusters", sample_name(sam_path), names, cl, t, repeats, threads)
+    if timings is not None:
+        timings["write_s"] = time.perf_counter() - t0
+    return t
+
+
 class _writer_threads:
     """MIRGE_AMD_TABLE_THREADS for the duration of one writer call (None = leave the environment alone)."""
 
@@ -167,17 +284,24 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings):
+                       sam, timings, trim=None):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
     as write_clusters / write_sorted_sam take them."""
     from .engine import STRATUM_ALL
     keys, parts = genome_libraries(engine, genome_prefix)
+    if trim is not None:
+        repeats, cutoff = trim
+        if repeats is None or isinstance(repeats, (str, bytes, os.PathLike)):
+            repeats = load_repeats(repeats, parts)
+        if int(cutoff) < 0 or len(repeats["rep_off"]) != 1 + sum(len(ix.names) for ix in parts):
+            raise ValueError("trim: the cutoff must not be negative and the repeat table must be load_repeats' over this genome")
     sam_path = out_stem + "_vs_genome_sorted.sam"
     keep = np.array(["chr" in nm for ix in parts for nm in ix.names], dtype=bool)
     if rs is not None:
         cl = engine.cluster_valid(rs, keys, counts, entry_keep=keep, threshold=int(overlapLenCutoff), strands=2,
                                   stratum_mode=STRATUM_ALL, m=int(mapping_loc), seed_len=int(seedLength), max_mm_seed=0,
-                                  max_mm_total=bowtie.N_MODE_MAX_TOTAL, sorted_rows=sam, timings=timings)
+                                  max_mm_total=bowtie.N_MODE_MAX_TOTAL, sorted_rows=sam, timings=timings,
+                                  **({} if trim is None else {"keep_device": True}))
     else:
         cl = dict(entry=np.zeros(0, np.uint32), strand=np.zeros(0, np.uint8), start=np.zeros(0, np.uint32),
                   end=np.zeros(0, np.uint32), seq_off=np.zeros(1, np.uint64), seq=b"", count_sum=np.zeros(0, np.uint64),
@@ -186,15 +310,21 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
     write_clusters(sam_path[:-4] + "_clusters.tsv", sample_name(sam_path), parts, names, cl)
     if sam:
         write_sorted_sam(sam_path, parts, names, seqs, cl["rows"], cl["suppressed"], int(mapping_loc))
+    if trim is not None:
+        cl["trim"] = trim_clusters(engine, cl, repeats, cutoff, out_stem, names)
+        cl.pop("device", None)
+        cl["trim"].pop("device", None)
     return cl
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None):
+                    timings=None, trim=None):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
-    arrays of Engine.cluster_valid.  mapping_loc 0 = no -m.  Nothing is written when a limit is exceeded."""
+    arrays of Engine.cluster_valid.  mapping_loc 0 = no -m.  Nothing is written when a limit is exceeded.
+    trim = (repeats, clusterSeqLenCutoff) adds :557-562 (trim_clusters: the three `_clusters_trimmed` files; the return value
+    gains "trim"); repeats = load_repeats' dict over this genome, or the path of the file (None: no table)."""
     from .engine import ReadSet
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
@@ -207,15 +337,15 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings)
+                              out_stem, sam, timings, trim)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None):
+                          sam=True, timings=None, trim=None):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
-    names; no FASTA is parsed and no Python string is made per read."""
+    names; no FASTA is parsed and no Python string is made per read.  trim: as map_and_cluster's."""
     import torch
     from .engine import ReadSet
     _check_policy(mapping_loc, seedLength, overlapLenCutoff)
@@ -245,7 +375,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
             seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings)
+                              out_stem, sam, timings, trim)
 
 
 def sample_stem(sample):
@@ -349,19 +479,24 @@ def clusters_main(argv):
     ap.add_argument("--overlap", type=int, default=14)
     ap.add_argument("-o", dest="out_stem", required=True)
     ap.add_argument("--no-sam", action="store_true")
+    ap.add_argument("--trim", action="store_true", help="also write the three _clusters_trimmed files")
+    ap.add_argument("--repeats", metavar="FILE", help="the repeat elements (chr, start, end, name; tab-separated) for --trim")
+    ap.add_argument("-clc", dest="cluster_len_cutoff", type=int, default=30)
     a = ap.parse_args(argv)
     from .engine import Engine
     try:
         eng = Engine(int(os.environ.get("MIRGE_AMD_GPU", "0")))
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
-                                 sam=not a.no_sam)
+                                 sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
         sys.stderr.write("predict clusters: %s\n" % e)
         return 1
     sys.stderr.write("# clusters: %d from %d alignments (%d on chr entries)\n" % (len(cl["entry"]), cl["n_rows"], cl["n_valid"]))
+    if a.trim:
+        sys.stderr.write("# trimmed: %d of them retained\n" % cl["trim"]["n_retained"])
     return 0
 
 
@@ -369,7 +504,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
-                         "-o <out_stem> [--no-sam]\n")
+                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30]]\n")
         return 1
     return clusters_main(argv[1:])
 
