@@ -973,6 +973,54 @@ int mrg_write_trimmed_clusters(const char *tsv_path, const char *fa_path, const 
                                const uint64_t *rep_names_off, uint64_t *rows, uint64_t *kept);
 
 /*
+ * Predict mode's second mapping (reference miRge2.0.py:566-601: two bowtie passes of the sample's filtered reads against the
+ * retained clusters, utils/processSam.py and `sort -k6,6 -k1,1`) around two listings of mrg_list_valid_count / _fill against
+ * the cluster library, whose entry j is record j of `*_clusters_trimmed_orig.fa` (csrc/predict_remap.hip).
+ *
+ *   mrg_predict_remap_temp_bytes  HOST: the bytes of device scratch the two calls below need for n_reads reads and n_rows
+ *       rows (pass 1 + pass 2).
+ *   mrg_predict_trim_reads  DEVICE.  d_counts [4][n]: the per-stratum counts of mrg_list_valid_count for pass 1.  The reads
+ *       with no alignment in any stratum, in read order: d_sel [*n_sel of n] their indices, and the reads themselves as a
+ *       packed set of their own -- d_out_reads [words_per_read][*n_sel] (the stride is *n_sel; the buffers hold
+ *       words_per_read * n words), d_out_lens [*n_sel of n], d_out_nmask like d_out_reads when d_nmask is given -- with
+ *       trim5 bases cut at the 5' end and trim3 at the 3' end (bowtie's -5 / -3): the length is max(0, len - trim5 - trim3),
+ *       the words and the N mask are shifted across the 64-bit word boundaries, every bit beyond the new length is zero.
+ *       Synchronises the stream.
+ *   mrg_predict_remap_rows  DEVICE.  Pass 1: d_off1 [n_reads + 1] ascending from 0 to rows1, d_ref1 / d_pos1 / d_mm1
+ *       [rows1]; pass 2 likewise over the n_sel reads d_sel [n_sel] (d_off2 [n_sel + 1], rows2); a listing without rows is
+ *       not read.  d_numbers [n_reads]: the n of `mir<n>_<count>`; d_kept [n_clusters]: entry j is cluster number
+ *       d_kept[j] + 1.  Output, [rows1 + rows2] each: d_read, d_cluster (the entry), d_offset, d_mm, d_pass (0 / 1), ordered
+ *       as `LC_ALL=C sort -k6,6 -k1,1` orders the lines: by the bytes of the cluster name, i.e. of the digits of its number
+ *       followed by `_` (a 40-bit key: the digits left-aligned at 4 bits each, padded with 15), then likewise by the read
+ *       name; rows equal in both keep the listing order (pass 1 before pass 2, rows of a listing in its order) and are put
+ *       into the order of their lines by the writer.  MRG_ERR_ARG when offsets, entries or d_sel contradict the sizes given
+ *       (the outputs are then undefined).  Limits: n_reads, n_clusters < 2^31, rows1 + rows2 < 2^32 - 1.  Synchronises.
+ *   mrg_write_remapped_rows  HOST: `<sample>_vs_representative_seq_modified_selected_sorted.tsv` from host arrays: the
+ *       packed reads, their numbers and counts, the cluster library (its entry names are printed), kept_seq_off /
+ *       kept_orig of mrg_predict_trim and the rows above.  One line per row, 17 tab-separated fields: name, count, the whole
+ *       read, the cluster's OriginalSeq, then FLAG (0) .. NM:i: exactly as mrg_write_bowtie's SAM lines have them; a pass-2
+ *       row's sequence is the read without its first trim5 and last trim3 bases.  Rows that name no read or cluster, align
+ *       an empty read or run past their cluster's end are MRG_ERR_ARG before the file is opened.  *rows = lines.
+ */
+int mrg_predict_remap_temp_bytes(uint64_t n_reads, uint64_t n_rows, uint64_t *bytes);
+int mrg_predict_trim_reads(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_per_read, uint64_t stride,
+                           const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n, const uint32_t *d_counts,
+                           uint32_t trim5, uint32_t trim3, uint32_t *d_sel, uint64_t *d_out_reads, uint8_t *d_out_lens,
+                           uint64_t *d_out_nmask, uint64_t *n_sel, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_remap_rows(mrg_ctx *ctx, uint64_t n_reads, const uint32_t *d_numbers, uint64_t n_clusters,
+                           const uint32_t *d_kept, const uint64_t *d_off1, uint64_t rows1, const int32_t *d_ref1,
+                           const int32_t *d_pos1, const uint8_t *d_mm1, uint64_t n_sel, const uint32_t *d_sel,
+                           const uint64_t *d_off2, uint64_t rows2, const int32_t *d_ref2, const int32_t *d_pos2,
+                           const uint8_t *d_mm2, uint32_t *d_read, uint32_t *d_cluster, uint32_t *d_offset, uint8_t *d_mm,
+                           uint8_t *d_pass, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_write_remapped_rows(const char *path, const uint64_t *reads, uint32_t words_per_read, uint64_t stride,
+                            const uint8_t *lens, const uint64_t *nmask, uint64_t n_reads, const uint32_t *numbers,
+                            const uint32_t *counts, const mrg_index *clusters, uint64_t n_clusters,
+                            const uint64_t *kept_seq_off, const char *kept_orig, uint64_t n_rows, const uint32_t *row_read,
+                            const uint32_t *row_cluster, const uint32_t *row_offset, const uint8_t *row_mm,
+                            const uint8_t *row_pass, uint32_t trim5, uint32_t trim3, uint64_t *rows);
+
+/*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are
  * grouped by group_of_entry[ref_id] -- the caller's map from a miRNA library entry to its name with the ".SNP..." suffix

@@ -24,7 +24,9 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     `..._vs_genome_sorted.sam` next to them (the genome as for `-ai`; reads of at most 255 nt: `-maxl` above 255 exits 1);
     `--novel-trim` (with `-clc 30`; implies `--novel-clusters`) adds the preliminary trim of those clusters on the GPU:
     `..._clusters_trimmed.tsv`, `..._clusters_trimmed.fa` and `..._clusters_trimmed_orig.fa`, the repeat elements read from
-    `<lib>/<sp>/annotation.Libs/<sp>_genome_repeats.tsv` (chr, start, end, name; a missing file = no repeat table).
+    `<lib>/<sp>/annotation.Libs/<sp>_genome_repeats.tsv` (chr, start, end, name; a missing file = no repeat table);
+    `--novel-map` (with `-sl`; implies `--novel-trim`) maps each sample's reads back to its retained clusters on the GPU
+    and adds `..._vs_representative_seq_modified_selected_sorted.tsv`, the table the feature stage reads.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -36,6 +38,16 @@ import numpy as np
 
 ANNOT_NAMES = ["exact miRNA", "hairpin miRNA", "mature tRNA", "primary tRNA", "snoRNA", "rRNA",
                "ncrna others", "mRNA", "isomiR miRNA"]  # MAIN:335
+
+
+def novel_stages(args):
+    """(reads, clusters, trim, map): which of predict mode's stages the `--novel-*` options ask for; each implies the ones
+    before it."""
+    novel_map = bool(getattr(args, "novel_map", False))
+    novel_trim = novel_map or bool(getattr(args, "novel_trim", False))
+    novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
+    novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
+    return novel_reads, novel_clusters, novel_trim, novel_map
 
 
 def build_parser():
@@ -78,6 +90,9 @@ def build_parser():
     p.add_argument("--novel-trim", dest="novel_trim", action="store_true",
                    help="extension: --novel-clusters, then the preliminary trim of the clusters on the GPU (-clc; the repeat "
                         "elements of <lib>/<sp>/annotation.Libs/<sp>_genome_repeats.tsv) -- the three _clusters_trimmed files")
+    p.add_argument("--novel-map", dest="novel_map", action="store_true",
+                   help="extension: --novel-trim, then the sample's reads mapped to the retained clusters on the GPU in the "
+                        "reference's two passes (-sl) -- unmapped_mirna_<sample>_vs_representative_seq_modified_selected_sorted.tsv")
     p.add_argument("-minl", default="16", dest="minLength", metavar="<int>")
     p.add_argument("-maxl", default="25", dest="maxLength", metavar="<int>")
     p.add_argument("-cc", default="2", dest="countCutoff", metavar="<int>")
@@ -197,9 +212,7 @@ def annotate_main(args, engine_factory=None, materialize=False):
     sp, lib = args.species, args.libraryPath
     if args.trf_output and sp != "human":  # MAIN:161-163
         _die("tRF detection is only supported for the species of human. Please check it.")
-    novel_trim = bool(getattr(args, "novel_trim", False))
-    novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
-    novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
+    novel_reads, novel_clusters, novel_trim, novel_map = novel_stages(args)
     novel_genome = None
 
     def novel_die(msg, out=sys.stderr):   # every rank of `--gpus N` leaves with status 1; rank 0 says why, as for -ai
@@ -550,7 +563,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 idx, num, _cnt = lists["sample_sel"][s]
                 g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
                 predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
-                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim)
+                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
+                                              remap=novel_map)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

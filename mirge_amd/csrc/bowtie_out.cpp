@@ -156,6 +156,39 @@ void format_unaligned(const BowtieArgs& a, uint64_t r, std::string& out, LineScr
   out += '\n';
 }
 
+// a SAM line's fields after the read name, from the tab before FLAG to the last of NM:i: (no line end): q = the sequence as
+// printed, ref = the reference bases under it
+void put_sam_fields(std::string& out, bool minus, const std::string& rname, uint32_t off, const std::string& q, const std::string& qual,
+                    const std::string& ref, uint32_t mm) {
+  const uint32_t L = (uint32_t)q.size();
+  out += minus ? "\t16\t" : "\t0\t";
+  out += rname;
+  out += '\t';
+  put_u64(out, (uint64_t)off + 1);
+  out += "\t255\t";
+  put_u64(out, L);
+  out += "M\t*\t0\t0\t";
+  out += q;
+  out += '\t';
+  out += qual;
+  out += "\tXA:i:";
+  put_u64(out, mm);
+  out += "\tMD:Z:";
+  uint32_t run = 0;
+  for (uint32_t i = 0; i < L; ++i) {
+    if (q[i] == ref[i]) {
+      ++run;
+      continue;
+    }
+    put_u64(out, run);
+    out += ref[i];
+    run = 0;
+  }
+  put_u64(out, run);
+  out += "\tNM:i:";
+  put_u64(out, mm);
+}
+
 // the line of alignment k (entry / offset / strand / mm [k]) of read r
 void format_aligned(const BowtieArgs& a, uint64_t r, uint64_t k, std::string& out, LineScratch& t) {
   const char* name = a.names + a.names_off[r];
@@ -177,32 +210,7 @@ void format_aligned(const BowtieArgs& a, uint64_t r, uint64_t k, std::string& ou
   const std::string& rname = a.entries->name(e);
   out.append(name, name_len);
   if (a.sam) {
-    out += minus ? "\t16\t" : "\t0\t";
-    out += rname;
-    out += '\t';
-    put_u64(out, (uint64_t)off + 1);
-    out += "\t255\t";
-    put_u64(out, L);
-    out += "M\t*\t0\t0\t";
-    out += q;
-    out += '\t';
-    out += t.qual;
-    out += "\tXA:i:";
-    put_u64(out, a.mm[k]);
-    out += "\tMD:Z:";
-    uint32_t run = 0;
-    for (uint32_t i = 0; i < L; ++i) {
-      if (q[i] == ref[i]) {
-        ++run;
-        continue;
-      }
-      put_u64(out, run);
-      out += ref[i];
-      run = 0;
-    }
-    put_u64(out, run);
-    out += "\tNM:i:";
-    put_u64(out, a.mm[k]);
+    put_sam_fields(out, minus, rname, off, q, t.qual, ref, a.mm[k]);
   } else {
     out += minus ? "\t-\t" : "\t+\t";
     out += rname;
@@ -556,6 +564,88 @@ void write_trimmed_clusters(const TrimmedClustersArgs& a, uint64_t* rows, uint64
   orig_fa.close();
   *rows = a.n_clusters;
   *kept = n_kept.load();
+}
+
+// `<sample>_vs_representative_seq_modified_selected_sorted.tsv` (decorateSam + parse_refine_sam + `sort -k6,6 -k1,1` of the
+// reference) from the rows of mrg_predict_remap_rows: per row the read's name, count and whole sequence, the cluster's
+// OriginalSeq and the SAM fields of the alignment (put_sam_fields: forward strand, the sequence a pass-2 row aligned with is
+// the read cut by trim5 / trim3).  The rows come ordered by (cluster name, read name); the rows of one read on one cluster are
+// put into the byte order of their lines here, which is `sort`'s last resort.
+uint64_t write_remapped_rows(const RemappedRowsArgs& a) {
+  static const char kBase[4] = {'A', 'C', 'G', 'T'};
+  if (a.n_clusters && (!a.clusters || a.clusters->names.size() != a.n_clusters))
+    throw std::invalid_argument("the cluster library does not hold the clusters given");
+  for (uint64_t c = 0; c < a.n_clusters; ++c)
+    if (a.kept_seq_off[c + 1] < a.kept_seq_off[c]) throw std::invalid_argument("cluster sequence offsets out of order");
+  for (uint64_t k = 0; k < a.n_rows; ++k) {
+    const uint64_t r = a.row_read[k], c = a.row_cluster[k];
+    if (r >= a.n_reads) throw std::invalid_argument("row " + std::to_string(k) + " of an unknown read");
+    if (c >= a.n_clusters) throw std::invalid_argument("row " + std::to_string(k) + " of an unknown cluster");
+    if (a.row_pass[k] > 1) throw std::invalid_argument("row " + std::to_string(k) + " of an unknown pass");
+    const uint32_t full = a.lens[r], cut = a.row_pass[k] ? a.trim5 + a.trim3 : 0u;
+    if (full > 32u * a.W) throw std::invalid_argument("read " + std::to_string(r) + " does not fit its words");
+    if (full <= cut) throw std::invalid_argument("row " + std::to_string(k) + " aligns an empty read");
+    if ((uint64_t)a.row_offset[k] + (full - cut) > a.kept_seq_off[c + 1] - a.kept_seq_off[c])
+      throw std::invalid_argument("row " + std::to_string(k) + " runs past the end of its cluster");
+  }
+  OutFile file(a.path);
+  uint64_t block = 1u << 12;
+  if (const char* e = std::getenv("MIRGE_AMD_PREDICT_BLOCK_ROWS")) block = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  // a block starts at the first row at or after its nominal start that continues no (cluster, read) run
+  auto run_start = [&](uint64_t k) {
+    k = std::min(k, a.n_rows);
+    while (k && k < a.n_rows && a.row_cluster[k] == a.row_cluster[k - 1] && a.row_read[k] == a.row_read[k - 1]) ++k;
+    return k;
+  };
+  auto format_row = [&](uint64_t k, std::string& out, LineScratch& t, std::string& whole) {
+    const uint64_t r = a.row_read[k], c = a.row_cluster[k];
+    const uint32_t full = a.lens[r];
+    whole.resize(full);
+    for (uint32_t i = 0; i < full; ++i) {
+      const uint64_t w = (uint64_t)(i >> 5) * a.stride + r;
+      const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
+      whole[i] = is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull];
+    }
+    const uint32_t t5 = a.row_pass[k] ? a.trim5 : 0u, t3 = a.row_pass[k] ? a.trim3 : 0u;
+    const uint32_t L = full - t5 - t3;
+    const char* orig = a.kept_orig + a.kept_seq_off[c];
+    t.q.assign(whole, t5, L);
+    t.qual.assign(L, 'I');
+    t.ref.assign(orig + a.row_offset[k], L);
+    out += "mir";
+    put_u64(out, a.numbers[r]);
+    out += '_';
+    put_u64(out, a.counts[r]);
+    out += '\t';
+    put_u64(out, a.counts[r]);
+    out += '\t';
+    out += whole;
+    out += '\t';
+    out.append(orig, (size_t)(a.kept_seq_off[c + 1] - a.kept_seq_off[c]));
+    put_sam_fields(out, false, a.clusters->names[c], a.row_offset[k], t.q, t.qual, t.ref, a.row_mm[k]);
+    out += '\n';
+  };
+  write_blocks_in_order(file, (a.n_rows + block - 1) / block, [&](uint64_t b, std::string& text) {
+    LineScratch t;
+    std::string whole;
+    std::vector<std::string> lines;
+    const uint64_t lo = run_start(b * block), hi = run_start((b + 1) * block);
+    for (uint64_t k = lo; k < hi;) {
+      uint64_t e = k + 1;
+      while (e < hi && a.row_cluster[e] == a.row_cluster[k] && a.row_read[e] == a.row_read[k]) ++e;
+      if (e - k == 1) {
+        format_row(k, text, t, whole);
+      } else {
+        lines.assign(e - k, std::string());
+        for (uint64_t j = k; j < e; ++j) format_row(j, lines[j - k], t, whole);
+        std::sort(lines.begin(), lines.end());
+        for (const std::string& s : lines) text += s;
+      }
+      k = e;
+    }
+  });
+  file.close();
+  return a.n_rows;
 }
 
 // the integer between the first and the second '_' of every read name (`mir<k>_<count>`, reference convert2Fasta.py:131)

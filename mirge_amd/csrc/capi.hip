@@ -24,6 +24,7 @@
 #include "fm_index.hpp"
 #include "a2i_align.hpp"
 #include "collapsed_order.hpp"
+#include "predict_remap.hpp"
 #include "predict_trim.hpp"
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
@@ -3118,6 +3119,167 @@ int mrg_write_trimmed_clusters(const char* tsv_path, const char* fa_path, const 
                                      end,      seq_off,   seq,          count_sum, member_off, members, n_reads, names, names_off,
                                      flag,     rep,       orig,         n_elements, rep_name_id, n_rep_names, rep_names, rep_names_off};
     mrg::write_trimmed_clusters(a, rows, kept);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+// ------------------------------------------------- predict mode: the second mapping (csrc/predict_remap.hip)
+namespace {
+constexpr uint64_t kRemapMaxReads = (1ull << 31) - 1, kRemapMaxRows = 0xfffffffeull;
+inline size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
+// mrg_predict_trim_reads' scratch: two uint32 arrays of n + 1 and the scan's own
+struct RemapTrimScratch {
+  size_t rank, scan, total;
+  explicit RemapTrimScratch(uint64_t n) {
+    rank = up8((size_t)(n + 1) * sizeof(uint32_t));
+    scan = 2 * rank;
+    total = scan + up8(mrg::prims::scan_temp_bytes(n + 1));
+  }
+};
+// mrg_predict_remap_rows' scratch: the stat words, three uint64 and five uint32 arrays and two byte arrays of T, the sort's own
+struct RemapRowsScratch {
+  size_t key0, key1, ckey, vals0, vals1, read, cluster, offset, mm, pass, sort, total;
+  explicit RemapRowsScratch(uint64_t rows) {
+    const size_t k8 = (size_t)rows * sizeof(uint64_t), k4 = up8((size_t)rows * sizeof(uint32_t)), k1 = up8((size_t)rows);
+    key0 = up8(mrg::kRemapStatWords * sizeof(uint32_t));
+    key1 = key0 + k8;
+    ckey = key1 + k8;
+    vals0 = ckey + k8;
+    vals1 = vals0 + k4;
+    read = vals1 + k4;
+    cluster = read + k4;
+    offset = cluster + k4;
+    mm = offset + k4;
+    pass = mm + k1;
+    sort = pass + k1;
+    total = sort + up8(mrg::prims::radix_temp_bytes(rows));
+  }
+};
+}  // namespace
+
+int mrg_predict_remap_temp_bytes(uint64_t n_reads, uint64_t n_rows, uint64_t* bytes) {
+  const char* fn = "mrg_predict_remap_temp_bytes";
+  if (!bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_reads > kRemapMaxReads) return fail(MRG_ERR_ARG, "%s: %llu reads; the limit is 2^31 - 1", fn, (unsigned long long)n_reads);
+  if (n_rows > kRemapMaxRows) return fail(MRG_ERR_ARG, "%s: %llu rows; the limit is 2^32 - 2", fn, (unsigned long long)n_rows);
+  *bytes = std::max(RemapTrimScratch(n_reads).total, RemapRowsScratch(n_rows).total);
+  return MRG_OK;
+}
+
+int mrg_predict_trim_reads(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read, uint64_t stride, const uint8_t* d_lens,
+                           const uint64_t* d_nmask, uint64_t n, const uint32_t* d_counts, uint32_t trim5, uint32_t trim3, uint32_t* d_sel,
+                           uint64_t* d_out_reads, uint8_t* d_out_lens, uint64_t* d_out_nmask, uint64_t* n_sel, void* d_tmp,
+                           uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_trim_reads";
+  if (!ctx || !n_sel) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_sel = 0;
+  if (n > kRemapMaxReads) return fail(MRG_ERR_ARG, "%s: %llu reads; the limit is 2^31 - 1", fn, (unsigned long long)n);
+  if (words_per_read < 1 || words_per_read > 8) return fail(MRG_ERR_ARG, "%s: words_per_read must be 1 .. 8", fn);
+  if (stride < n) return fail(MRG_ERR_ARG, "%s: a stride of %llu for %llu reads", fn, (unsigned long long)stride, (unsigned long long)n);
+  if (trim5 > 255 || trim3 > 255) return fail(MRG_ERR_ARG, "%s: trims beyond the longest read (255)", fn);
+  if (!d_tmp) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n && (!d_reads || !d_lens || !d_counts || !d_sel || !d_out_reads || !d_out_lens || (d_nmask && !d_out_nmask)))
+    return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  const RemapTrimScratch sc(n);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_remap_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base);
+  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  HIP_TRY(mrg::remap_mark_launch(d_counts, (uint32_t)n, flag32, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::remap_compact_launch((uint32_t)n, rank, d_sel, st));
+  uint32_t k = 0;
+  HIP_TRY(hipMemcpyAsync(&k, rank + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (k > n) return fail(MRG_ERR_HIP, "%s: %u reads picked of %llu", fn, k, (unsigned long long)n);
+  const mrg::RemapReads in{d_reads, words_per_read, stride, d_lens, d_nmask, (uint32_t)n};
+  HIP_TRY(mrg::remap_trim_launch(in, d_sel, k, trim5, trim3, d_out_reads, d_out_lens, d_out_nmask, st));
+  *n_sel = k;
+  return MRG_OK;
+}
+
+int mrg_predict_remap_rows(mrg_ctx* ctx, uint64_t n_reads, const uint32_t* d_numbers, uint64_t n_clusters, const uint32_t* d_kept,
+                           const uint64_t* d_off1, uint64_t rows1, const int32_t* d_ref1, const int32_t* d_pos1, const uint8_t* d_mm1,
+                           uint64_t n_sel, const uint32_t* d_sel, const uint64_t* d_off2, uint64_t rows2, const int32_t* d_ref2,
+                           const int32_t* d_pos2, const uint8_t* d_mm2, uint32_t* d_read, uint32_t* d_cluster, uint32_t* d_offset,
+                           uint8_t* d_mm, uint8_t* d_pass, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_remap_rows";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_reads > kRemapMaxReads || n_sel > n_reads)
+    return fail(MRG_ERR_ARG, "%s: %llu reads (the limit is 2^31 - 1), %llu of them in pass 2", fn, (unsigned long long)n_reads,
+                (unsigned long long)n_sel);
+  if (n_clusters > kRemapMaxReads) return fail(MRG_ERR_ARG, "%s: %llu clusters; the limit is 2^31 - 1", fn, (unsigned long long)n_clusters);
+  if (rows1 > kRemapMaxRows || rows2 > kRemapMaxRows || rows1 + rows2 > kRemapMaxRows)
+    return fail(MRG_ERR_ARG, "%s: %llu rows; the limit is 2^32 - 2", fn, (unsigned long long)(rows1 + rows2));
+  const uint64_t T = rows1 + rows2;
+  if (!d_tmp) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (rows1 && (!n_reads || !d_off1 || !d_ref1 || !d_pos1 || !d_mm1)) return fail(MRG_ERR_ARG, "%s: null pass-1 listing", fn);
+  if (rows2 && (!n_sel || !d_sel || !d_off2 || !d_ref2 || !d_pos2 || !d_mm2)) return fail(MRG_ERR_ARG, "%s: null pass-2 listing", fn);
+  if (T && (!n_clusters || !d_numbers || !d_kept || !d_read || !d_cluster || !d_offset || !d_mm || !d_pass))
+    return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
+  const RemapRowsScratch sc(T);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_remap_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint64_t* key0 = reinterpret_cast<uint64_t*>(base + sc.key0);
+  uint64_t* key1 = reinterpret_cast<uint64_t*>(base + sc.key1);
+  uint64_t* ckey = reinterpret_cast<uint64_t*>(base + sc.ckey);
+  uint32_t* vals0 = reinterpret_cast<uint32_t*>(base + sc.vals0);
+  uint32_t* vals1 = reinterpret_cast<uint32_t*>(base + sc.vals1);
+  const mrg::RemapRows listed{reinterpret_cast<uint32_t*>(base + sc.read), reinterpret_cast<uint32_t*>(base + sc.cluster),
+                              reinterpret_cast<uint32_t*>(base + sc.offset), reinterpret_cast<uint8_t*>(base + sc.mm),
+                              reinterpret_cast<uint8_t*>(base + sc.pass)};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kRemapStatWords * sizeof(uint32_t), st));
+  // a listing without rows has no say: its offsets are not read
+  const mrg::RemapListing p1{d_off1, rows1 ? (uint32_t)n_reads : 0u, d_ref1, d_pos1, d_mm1, (uint32_t)rows1};
+  const mrg::RemapListing p2{d_off2, rows2 ? (uint32_t)n_sel : 0u, d_ref2, d_pos2, d_mm2, (uint32_t)rows2};
+  const mrg::RemapMergeArgs a{p1, p2, d_sel, (uint32_t)n_reads, d_numbers, (uint32_t)n_clusters, d_kept, listed, key0, ckey, vals0, stat};
+  if (T) {
+    HIP_TRY(mrg::remap_merge_launch(a, st));
+    // by read name, then (stable) by cluster name: the order of `sort -k6,6 -k1,1` up to the rows equal in both
+    bool second = false;
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, vals0, vals1, (uint32_t)T, mrg::kRemapKeyBits, base + sc.sort, st, &second));
+    uint32_t* by_read = second ? vals1 : vals0;
+    uint32_t* spare = second ? vals0 : vals1;
+    HIP_TRY(mrg::remap_gather_keys_launch(ckey, by_read, (uint32_t)T, key0, st));
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, by_read, spare, (uint32_t)T, mrg::kRemapKeyBits, base + sc.sort, st, &second));
+    const mrg::RemapRows out{d_read, d_cluster, d_offset, d_mm, d_pass};
+    HIP_TRY(mrg::remap_gather_rows_launch(listed, second ? spare : by_read, (uint32_t)T, out, st));
+  }
+  uint32_t h_stat[mrg::kRemapStatWords] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h_stat[mrg::kRemapStatBadOffsets]) return fail(MRG_ERR_ARG, "%s: a listing's offsets do not ascend from 0 to its rows", fn);
+  if (h_stat[mrg::kRemapStatBadCluster]) return fail(MRG_ERR_ARG, "%s: a row on an entry beyond the %llu clusters, or at a negative offset", fn, (unsigned long long)n_clusters);
+  if (h_stat[mrg::kRemapStatBadRead]) return fail(MRG_ERR_ARG, "%s: a pass-2 read beyond the %llu reads", fn, (unsigned long long)n_reads);
+  return MRG_OK;
+}
+
+int mrg_write_remapped_rows(const char* path, const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens,
+                            const uint64_t* nmask, uint64_t n_reads, const uint32_t* numbers, const uint32_t* counts,
+                            const mrg_index* clusters, uint64_t n_clusters, const uint64_t* kept_seq_off, const char* kept_orig,
+                            uint64_t n_rows, const uint32_t* row_read, const uint32_t* row_cluster, const uint32_t* row_offset,
+                            const uint8_t* row_mm, const uint8_t* row_pass, uint32_t trim5, uint32_t trim3, uint64_t* rows) {
+  const char* fn = "mrg_write_remapped_rows";
+  if (!path || !rows) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *rows = 0;
+  if (n_reads && (!reads || !lens || !numbers || !counts)) return fail(MRG_ERR_ARG, "%s: null read arrays", fn);
+  if (n_clusters && (!clusters || !kept_seq_off || !kept_orig)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (n_rows && (!row_read || !row_cluster || !row_offset || !row_mm || !row_pass)) return fail(MRG_ERR_ARG, "%s: null row arrays", fn);
+  if (words_per_read < 1 || words_per_read > 8 || stride < n_reads) return fail(MRG_ERR_ARG, "%s: words_per_read must be 1 .. 8 and the stride cover the reads", fn);
+  try {
+    const mrg::RemappedRowsArgs a{path,       reads,        words_per_read, stride,   lens,     nmask,       n_reads,    numbers,
+                                  counts,     clusters ? &clusters->ix : nullptr,     n_clusters, kept_seq_off, kept_orig, n_rows,
+                                  row_read,   row_cluster,  row_offset,     row_mm,   row_pass, trim5,       trim3};
+    *rows = mrg::write_remapped_rows(a);
     return MRG_OK;
   } catch (const std::invalid_argument& e) {
     return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());

@@ -62,6 +62,28 @@ struct TrimmedClustersArgs {
   const uint64_t* rep_names_off;  // [n_rep_names + 1]
 };
 void write_trimmed_clusters(const TrimmedClustersArgs& a, uint64_t* rows, uint64_t* kept);
+// mrg_write_remapped_rows: the packed reads with their numbers and counts, the cluster library (its entry names are the
+// cluster names) with the retained clusters' OriginalSeq bytes, and the rows of mrg_predict_remap_rows.  Throws
+// std::invalid_argument (arrays that contradict each other: the file is not opened) or std::runtime_error.  Returns the lines.
+struct RemappedRowsArgs {
+  const char* path;
+  const uint64_t* reads;  // [W][stride]
+  uint32_t W;
+  uint64_t stride;
+  const uint8_t* lens;
+  const uint64_t* nmask;  // or null
+  uint64_t n_reads;
+  const uint32_t *numbers, *counts;  // `mir<number>_<count>`
+  const FmIndex* clusters;
+  uint64_t n_clusters;
+  const uint64_t* kept_seq_off;  // [n_clusters + 1]
+  const char* kept_orig;
+  uint64_t n_rows;
+  const uint32_t *row_read, *row_cluster, *row_offset;
+  const uint8_t *row_mm, *row_pass;
+  uint32_t trim5, trim3;  // what a pass-2 row's aligned sequence lost
+};
+uint64_t write_remapped_rows(const RemappedRowsArgs& a);
 int64_t read_counts_from_names(uint64_t n_reads, const char* names, const uint64_t* names_off, uint32_t* counts);
 
 }  // namespace mrg

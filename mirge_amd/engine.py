@@ -1057,42 +1057,31 @@ class Engine:
         return (offsets, entry[order].astype(np.int32), pos[order].astype(np.int32), strand[order], mm[order],
                 suppressed)
 
-    def cluster_valid(self, reads, libs, counts, entry_keep=None, threshold=14, strands=2, stratum_mode=STRATUM_ALL, m=0,
-                      seed_len=28, max_mm_seed=0, max_mm_total=2, sorted_rows=False, timings=None, keep_device=False):
-        """Predict mode's location clusters of the listing of list_valid (same reads, libraries, entry numbering and
-        policy; `-m` and the best stratum are decided over all parts from the per-read counts, as there), without the
-        alignment rows leaving the device: mrg_list_valid_fill per part, then mrg_cluster_keys / _sort / _scan /
-        _bounds / _assemble (the rule is documented there).  counts: uint32 [n], the copies each read stands for;
-        entry_keep: bool per entry over all parts (None = all), False drops the entry's alignments from the clusters
-        (the reference keeps names containing "chr").
-        Returns a dict of host arrays: entry, strand, start, end (1-based inclusive), seq_off [C + 1], seq (bytes),
-        count_sum (uint64), member_off [C + 1], members (read numbers, cluster after cluster in list order), suppressed
-        [n] bool, n_rows, n_valid (rows on kept entries); clusters are ordered by (entry, strand, start).
-        sorted_rows=True adds "rows" = (read, entry, offset, strand, mm) of every alignment ordered by (entry, offset,
-        strand, read) -- a coordinate-sorted SAM file's order.  timings: a dict, or None; gets count_s / fill_s as
-        list_valid does and the device milliseconds sort_ms / scan_ms / assemble_ms.
-        keep_device=True adds "device": the cluster arrays as device tensors for predict_trim (entry, strand, start, end,
-        seq_off, seq, and the ints n_clusters, total_len), None when there is no alignment row."""
+    def _list_valid_device(self, reads, libs, strands, stratum_mode, m, seed_len, max_mm_seed, max_mm_total, timings=None):
+        """list_valid's listing with the offsets and the rows left on the device (mrg_list_valid_count per part, the best
+        stratum and `-m` decided over all parts on the host from the counts, mrg_list_valid_fill per part).  Returns a dict:
+        bases (first entry number of every part, then the total), n_entries, suppressed [n] bool, n_rows, counts (per part
+        the device tensor [4, n] of mrg_list_valid_count), aligned [n] bool; and, unless n_rows is 0, the device tensors ref
+        (the part's own entry numbers) / pos / strand / mm [n_rows], part after part, and offsets = per part (int64 [n + 1]
+        inside the part's rows, first row, rows).  ValueError beyond 2^32 - 2 rows.  timings gets count_s / fill_s."""
         import time
         torch = _torch()
         n = reads.n
         dev = self.device
         st = self._stream_ptr()
-        if int(threshold) < 1:
-            raise ValueError("the overlap threshold must be at least 1 (got %d)" % int(threshold))
         lids = [self.libs[k] if isinstance(k, str) else int(k) for k in libs]
         keys = {v: k for k, v in self.libs.items()}
         bases = np.cumsum([0] + [self.indexes[keys[l]].n_ref for l in lids])
-        n_entries = int(bases[-1])
         nm = reads.nmask.data_ptr() if reads.nmask is not None else None
         args = (reads.W, reads.lens.data_ptr(), nm, n)
-        per_lib = []
+        per_lib, counts_d = [], []
         t0 = time.perf_counter()
         for lid in lids:
             cnt = torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev)
             check(self._lib.mrg_list_valid_count(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(seed_len),
                                                  int(max_mm_seed), int(max_mm_total), cnt.data_ptr(), st))
             per_lib.append(cnt.cpu().numpy()[:, :n].view(np.uint32).astype(np.int64))
+            counts_d.append(cnt)
         if timings is not None:
             timings["count_s"] = time.perf_counter() - t0
         tot = np.sum(per_lib, axis=0) if per_lib else np.zeros((4, n), dtype=np.int64)
@@ -1114,14 +1103,7 @@ class Engine:
         T = int(sum(int(o[-1]) for o in part_off))
         if T >= 2 ** 32 - 1:
             raise ValueError("%d alignment rows; the limit is 2^32 - 2" % T)
-        out = dict(suppressed=suppressed, n_rows=T, n_valid=0, entry=np.zeros(0, np.uint32), strand=np.zeros(0, np.uint8),
-                   start=np.zeros(0, np.uint32), end=np.zeros(0, np.uint32), seq_off=np.zeros(1, np.uint64), seq=b"",
-                   count_sum=np.zeros(0, np.uint64), member_off=np.zeros(1, np.uint32), members=np.zeros(0, np.uint32))
-        if sorted_rows:
-            out["rows"] = (np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
-                           np.zeros(0, np.uint8))
-        if keep_device:
-            out["device"] = None
+        out = dict(bases=bases, n_entries=int(bases[-1]), suppressed=suppressed, n_rows=T, counts=counts_d, aligned=aligned)
         if T == 0:
             return out
 
@@ -1146,6 +1128,48 @@ class Engine:
             row_base += t
         if timings is not None:
             timings["fill_s"] = t_fill
+        out.update(ref=ref, pos=pos, strand=strand, mm=mm, offsets=offs_d)
+        return out
+
+    def cluster_valid(self, reads, libs, counts, entry_keep=None, threshold=14, strands=2, stratum_mode=STRATUM_ALL, m=0,
+                      seed_len=28, max_mm_seed=0, max_mm_total=2, sorted_rows=False, timings=None, keep_device=False):
+        """Predict mode's location clusters of the listing of list_valid (same reads, libraries, entry numbering and
+        policy; `-m` and the best stratum are decided over all parts from the per-read counts, as there), without the
+        alignment rows leaving the device: mrg_list_valid_fill per part, then mrg_cluster_keys / _sort / _scan /
+        _bounds / _assemble (the rule is documented there).  counts: uint32 [n], the copies each read stands for;
+        entry_keep: bool per entry over all parts (None = all), False drops the entry's alignments from the clusters
+        (the reference keeps names containing "chr").
+        Returns a dict of host arrays: entry, strand, start, end (1-based inclusive), seq_off [C + 1], seq (bytes),
+        count_sum (uint64), member_off [C + 1], members (read numbers, cluster after cluster in list order), suppressed
+        [n] bool, n_rows, n_valid (rows on kept entries); clusters are ordered by (entry, strand, start).
+        sorted_rows=True adds "rows" = (read, entry, offset, strand, mm) of every alignment ordered by (entry, offset,
+        strand, read) -- a coordinate-sorted SAM file's order.  timings: a dict, or None; gets count_s / fill_s as
+        list_valid does and the device milliseconds sort_ms / scan_ms / assemble_ms.
+        keep_device=True adds "device": the cluster arrays as device tensors for predict_trim (entry, strand, start, end,
+        seq_off, seq, and the ints n_clusters, total_len), None when there is no alignment row."""
+        torch = _torch()
+        n = reads.n
+        dev = self.device
+        st = self._stream_ptr()
+        if int(threshold) < 1:
+            raise ValueError("the overlap threshold must be at least 1 (got %d)" % int(threshold))
+        nm = reads.nmask.data_ptr() if reads.nmask is not None else None
+        ls = self._list_valid_device(reads, libs, strands, stratum_mode, m, seed_len, max_mm_seed, max_mm_total, timings)
+        bases, n_entries, suppressed, T = ls["bases"], ls["n_entries"], ls["suppressed"], ls["n_rows"]
+        out = dict(suppressed=suppressed, n_rows=T, n_valid=0, entry=np.zeros(0, np.uint32), strand=np.zeros(0, np.uint8),
+                   start=np.zeros(0, np.uint32), end=np.zeros(0, np.uint32), seq_off=np.zeros(1, np.uint64), seq=b"",
+                   count_sum=np.zeros(0, np.uint64), member_off=np.zeros(1, np.uint32), members=np.zeros(0, np.uint32))
+        if sorted_rows:
+            out["rows"] = (np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
+                           np.zeros(0, np.uint8))
+        if keep_device:
+            out["device"] = None
+        if T == 0:
+            return out
+
+        def dev_empty(count, dtype):
+            return torch.empty(max(int(count), 1), dtype=dtype, device=dev)
+        ref, pos, strand, mm, offs_d = ls["ref"], ls["pos"], ls["strand"], ls["mm"], ls["offsets"]
         max_pos = int(pos[:T].max())
         if max_pos < 0 or max_pos >= 2 ** 31:
             raise ValueError("an alignment at offset %d; positions must be below 2^31" % max_pos)
@@ -1306,6 +1330,122 @@ class Engine:
             ev[2].synchronize()
             timings.update(trim_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
         return out
+
+    def _remap_tmp(self, n_reads, n_rows):
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_remap_temp_bytes(int(n_reads), int(n_rows), C.byref(need)))
+        return _torch().empty(max(int(need.value), 8), dtype=_torch().uint8, device=self.device)
+
+    def predict_trim_reads(self, reads, counts, trim5=1, trim3=3):
+        """The reads of a ReadSet that a listing left unaligned, cut for the next one (mrg_predict_trim_reads).  counts: the
+        device tensor [4, n] of mrg_list_valid_count (int32 storage).  Returns (sel, ReadSet): sel = the picked reads'
+        indices (device, uint32 in int32 storage, read order), the ReadSet = those reads without their first trim5 and last
+        trim3 bases (a read of trim5 + trim3 bases or fewer is empty), W as the input's; None in its place when no read is
+        picked."""
+        torch = _torch()
+        n, W, dev = reads.n, reads.W, self.device
+        self._expect(counts, torch.int32, "predict_trim_reads: counts")
+        if counts.dim() != 2 or int(counts.shape[0]) != 4 or int(counts.shape[1]) < n or (n and int(counts.shape[1]) != n) or \
+                not counts.is_contiguous():
+            raise ValueError("predict_trim_reads: counts must be a contiguous [4, n] tensor")
+        tmp = self._remap_tmp(n, 0)
+        sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        o_words = torch.empty(max(W * n, 1), dtype=torch.int64, device=dev)
+        o_nmask = None if reads.nmask is None else torch.empty(max(W * n, 1), dtype=torch.int64, device=dev)
+        o_lens = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        k = C.c_uint64(0)
+        check(self._lib.mrg_predict_trim_reads(
+            self._h, reads.words.data_ptr(), W, n, reads.lens.data_ptr(), None if reads.nmask is None else reads.nmask.data_ptr(), n,
+            counts.data_ptr(), int(trim5), int(trim3), sel.data_ptr(), o_words.data_ptr(), o_lens.data_ptr(),
+            None if o_nmask is None else o_nmask.data_ptr(), C.byref(k), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        k = int(k.value)
+        if k == 0:
+            return sel[:0], None
+        cut = int(trim5) + int(trim3)
+        rs = ReadSet.from_device(o_words[:W * k].view(W, k), o_lens[:k], None if o_nmask is None else o_nmask[:W * k].view(W, k),
+                                 None, max(0, reads.min_len - cut), max(0, reads.max_len - cut))
+        return sel[:k], rs
+
+    def predict_remap_rows(self, numbers, kept, listing1, listing2, sel):
+        """The rows of two listings against the cluster library in the order of the sorted table (mrg_predict_remap_rows).
+        numbers [n]: the reads' numbers; kept [K]: the retained clusters (entry j is cluster number kept[j] + 1); listing =
+        (offsets int64 [reads + 1], ref int32, pos int32, mm uint8), device tensors, or None for a listing without rows;
+        sel [k]: the read of every read of listing2.  Returns device tensors (read, cluster, offset: uint32 in int32 storage;
+        mm, pass: uint8), [rows of both]."""
+        torch = _torch()
+        dev = self.device
+        numbers, kept = self._dev_u32(numbers, "predict_remap_rows: numbers"), self._dev_u32(kept, "predict_remap_rows: kept")
+        n, K = int(numbers.shape[0]), int(kept.shape[0])
+
+        def listing(ls, reads, what):
+            if ls is None:
+                return (None, 0, None, None, None)
+            off, ref, pos, mm = ls
+            self._expect(off, torch.int64, what + " offsets")
+            self._expect(ref, torch.int32, what + " ref")
+            self._expect(pos, torch.int32, what + " pos")
+            self._expect(mm, torch.uint8, what + " mm")
+            rows = min(int(ref.shape[0]), int(pos.shape[0]), int(mm.shape[0]))
+            if int(off.shape[0]) != reads + 1 or max(int(ref.shape[0]), int(pos.shape[0]), int(mm.shape[0])) != rows:
+                raise ValueError("%s: offsets [reads + 1] and ref / pos / mm [rows] must match" % what)
+            if rows == 0:
+                return (None, 0, None, None, None)
+            return (off.contiguous().data_ptr(), rows, ref.contiguous().data_ptr(), pos.contiguous().data_ptr(), mm.contiguous().data_ptr())
+        k = 0 if sel is None else int(sel.shape[0])
+        if sel is not None:
+            sel = self._dev_u32(sel, "predict_remap_rows: sel")
+        l1, l2 = listing(listing1, n, "predict_remap_rows: pass 1"), listing(listing2, k, "predict_remap_rows: pass 2")
+        T = l1[1] + l2[1]
+        tmp = self._remap_tmp(n, T)
+        e = lambda dtype: torch.empty(max(T, 1), dtype=dtype, device=dev)
+        read, cluster, offset, mm, pass_ = e(torch.int32), e(torch.int32), e(torch.int32), e(torch.uint8), e(torch.uint8)
+        check(self._lib.mrg_predict_remap_rows(
+            self._h, n, numbers.data_ptr() if n else None, K, kept.data_ptr() if K else None, *l1, k,
+            sel.data_ptr() if k else None, *l2, read.data_ptr(), cluster.data_ptr(), offset.data_ptr(), mm.data_ptr(),
+            pass_.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return read[:T], cluster[:T], offset[:T], mm[:T], pass_[:T]
+
+    def predict_remap(self, reads, numbers, lib, kept, seed_len, trims=(1, 3), timings=None):
+        """Predict mode's second mapping of a ReadSet against the cluster library `lib` of this engine (reference
+        miRge2.0.py:566-601).  Pass 1 lists every read under bowtie's `-n 0 -l seed_len -a --best --norc`; the reads it left
+        unaligned are cut by `trims` (`-5 1 -3 3`) and listed under `-n 1 -l 15 -a --best --strata --norc`; the rows of both
+        are merged and ordered as `sort -k6,6 -k1,1` orders the table.  numbers [n]: the reads' numbers (device tensor or
+        host array); kept [K]: Engine.predict_trim's, host or device.
+        Returns a dict: rows = host arrays (read, cluster, offset uint32; mm, pass uint8), n_rows, aligned1 / aligned2 /
+        unaligned (reads), and "device" with the rows as device tensors.  timings gets list_ms, rows_ms, download_ms."""
+        from .bowtie import N_MODE_MAX_TOTAL
+        torch = _torch()
+        dev = self.device
+        n = reads.n
+        ev = []
+
+        def mark():
+            if timings is not None:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record(torch.cuda.current_stream(dev))
+                ev.append(e)
+        mark()
+        p1 = self._list_valid_device(reads, [lib], 1, STRATUM_ALL, 0, int(seed_len), 0, N_MODE_MAX_TOTAL)
+        sel, cut = self.predict_trim_reads(reads, p1["counts"][0], *trims)
+        p2 = None
+        if cut is not None:
+            p2 = self._list_valid_device(cut, [lib], 1, STRATUM_BEST, 0, 15, 1, N_MODE_MAX_TOTAL)
+
+        def listing(p):
+            if p is None or p["n_rows"] == 0:
+                return None
+            return (p["offsets"][0][0], p["ref"][:p["n_rows"]], p["pos"][:p["n_rows"]], p["mm"][:p["n_rows"]])
+        mark()
+        rows = self.predict_remap_rows(numbers, kept, listing(p1), listing(p2), sel)
+        mark()
+        host = tuple(t.cpu().numpy().view(np.uint32) if t.dtype == torch.int32 else t.cpu().numpy() for t in rows)
+        mark()
+        a1 = int(p1["aligned"].sum())
+        a2 = 0 if p2 is None else int(p2["aligned"].sum())
+        if timings is not None:
+            ev[-1].synchronize()
+            timings.update(list_ms=ev[0].elapsed_time(ev[1]), rows_ms=ev[1].elapsed_time(ev[2]), download_ms=ev[2].elapsed_time(ev[3]))
+        return dict(rows=host, n_rows=int(host[0].shape[0]), aligned1=a1, aligned2=a2, unaligned=n - a1 - a2, device=rows)
 
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through

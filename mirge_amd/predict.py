@@ -12,7 +12,7 @@ so the samtools view / sort / index / view round trip of this stage is gone.  Ro
 alignments with equal (entry, strand, position) is read order: a choice, not pinned against a real `samtools sort`.
 
     python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> -m 3 -l 25 --overlap 14 -o <out_stem> [--no-sam]
-                                         [--trim [--repeats FILE] [-clc 30]]
+                                         [--trim [--repeats FILE] [-clc 30] [--remap]]
 
 With `trim=(repeats, cutoff)` / `--trim` the next two calls of the reference (preTrimClusteredSeq, generate_Seq; miRge2.0.py:557-562)
 run over the same device arrays (Engine.predict_trim = mrg_predict_trim; mrg_write_trimmed_clusters) and add
@@ -22,6 +22,12 @@ run over the same device arrays (Engine.predict_trim = mrg_predict_trim; mrg_wri
     <out_stem>_vs_genome_sorted_clusters_trimmed_orig.fa    ... and their OriginalSeq
 
 The repeat elements come from a four-column tab-separated file (load_repeats), not from the reference's pickle.
+
+With `remap=True` / `--remap` (needs the trim) the block after that (miRge2.0.py:566-601: bowtie-build over the retained
+clusters, two bowtie passes of the same reads, utils/processSam.py, `sort -k6,6 -k1,1`) runs over the same arrays
+(map_reads_to_clusters: Engine.predict_remap = mrg_predict_trim_reads / mrg_predict_remap_rows; mrg_write_remapped_rows) and adds
+
+    <out_stem>_vs_representative_seq_modified_selected_sorted.tsv    the only file generate_featureFiles reads
 
 The device is $MIRGE_AMD_GPU (default 0).  Limits: reads up to 255 nt, fewer than 2^32 - 1 alignment rows, positions
 below 2^31; beyond them the call fails naming the limit and writes nothing.
@@ -244,6 +250,113 @@ def trim_clusters(engine, cl, repeats, clusterSeqLenCutoff, out_stem, names, thr
     return t
 
 
+REMAP_SUFFIX = "_vs_representative_seq_modified_selected_sorted.tsv"
+REMAP_TRIMS = (1, 3)      # the second pass's -5 1 -3 3
+
+
+def write_remapped_rows(path, words, lens, nmask, numbers, counts, index, kept_seq_off, kept_orig, rows, trims=REMAP_TRIMS,
+                        threads=None):
+    """mrg_write_remapped_rows: the sorted table of the second mapping from host arrays -- the packed reads (words uint64
+    [W, n], lens, nmask or None), their numbers and counts (uint32 [n]), the cluster library (an FmIndex whose entry j is
+    retained cluster j), kept_seq_off / kept_orig of Engine.predict_trim and rows = (read, cluster, offset, mm, pass) of
+    Engine.predict_remap.  Returns the lines written."""
+    from . import _native
+    lib = _native.load()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    if words.ndim != 2:
+        raise ValueError("write_remapped_rows: words must be [W, n]")
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    numbers, counts = np.ascontiguousarray(numbers, dtype=np.uint32), np.ascontiguousarray(counts, dtype=np.uint32)
+    soff = np.ascontiguousarray(kept_seq_off, dtype=np.uint64)
+    orig = np.frombuffer(bytes(kept_orig), dtype=np.uint8)
+    read, cluster, offset = (np.ascontiguousarray(a, dtype=np.uint32) for a in rows[:3])
+    mm, pass_ = (np.ascontiguousarray(a, dtype=np.uint8) for a in rows[3:5])
+    K = int(soff.shape[0]) - 1
+    if lens.shape != (n,) or numbers.shape != (n,) or counts.shape != (n,) or (nm is not None and nm.shape != words.shape):
+        raise ValueError("write_remapped_rows: words [W, n], nmask, lens, numbers and counts [n] must match")
+    if K < 0 or int(soff[-1]) != orig.shape[0] or (index.n_ref if index is not None else 0) != K:
+        raise ValueError("write_remapped_rows: kept_seq_off [K + 1] must close at the bytes of kept_orig and the library hold K entries")
+    if any(a.shape != read.shape for a in (cluster, offset, mm, pass_)):
+        raise ValueError("write_remapped_rows: the row arrays differ in length")
+    done = C.c_uint64()
+    with _writer_threads(threads):
+        _native.check(lib.mrg_write_remapped_rows(
+            os.fsencode(path), _ptr(words), W, n, _ptr(lens), None if nm is None else _ptr(nm), n, _ptr(numbers), _ptr(counts),
+            index._h if index is not None else None, K, soff.ctypes.data, _ptr(orig), len(read), _ptr(read), _ptr(cluster),
+            _ptr(offset), _ptr(mm), _ptr(pass_), int(trims[0]), int(trims[1]), C.byref(done)))
+    return int(done.value)
+
+
+def read_numbers(names):
+    """numbers[r] = the n of read r's name `mir<n>_<count>`; ValueError without one below 2^32."""
+    out = np.zeros(len(names), dtype=np.uint32)
+    for r, nm in enumerate(names):
+        head = nm[3:].split("_")[0] if nm.startswith("mir") else ""
+        if not head.isdigit() or int(head) >= 2 ** 32:
+            raise ValueError("read name %r is not `mir<n>_<count>` with n below 2^32" % nm)
+        out[r] = int(head)
+    return out
+
+
+def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, out_stem, names=None, threads=None, timings=None):
+    """The reference's miRge2.0.py:566-601 from the arrays: the sample's filtered reads (rs: the ReadSet the genome stage
+    listed; numbers / counts [n]: their `mir<number>_<count>`, host arrays or device tensors; numbers None = read from
+    `names`, a list) against the clusters trim_clusters retained (trim_result: its return value), in two passes -- bowtie's
+    `-n 0 -l seedLength -a --best --norc`, then `-n 1 -l 15 -5 1 -3 3 -a --best --strata --norc` for the reads the first left
+    unaligned -- decorated, selected and sorted as `LC_ALL=C sort -k6,6 -k1,1` does.  Writes
+    `<out_stem>_vs_representative_seq_modified_selected_sorted.tsv`; returns a dict: rows (read, cluster, offset, mm, pass:
+    host arrays in file order), n_rows, aligned1, aligned2, unaligned (reads).
+    The cluster library is built on the device from `<out_stem>_vs_genome_sorted_clusters_trimmed_orig.fa`, the file the
+    trim wrote, and is resident on an engine of its own for the duration of the call: engine.libs is untouched.  With no
+    retained cluster nothing is written and every count is 0 (the reference aborts there)."""
+    import time
+    import torch
+    from .engine import Engine
+    from .index import FmIndex
+    if int(seedLength) < 5:
+        raise ValueError("seedLength must be >= 5")
+    empty = dict(rows=(np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint8)),
+                 n_rows=0, aligned1=0, aligned2=0, unaligned=0)
+    K = int(trim_result["n_retained"]) if "n_retained" in trim_result else len(trim_result["kept"])
+    if K == 0:
+        return empty
+    if K != len(trim_result["kept"]) or len(trim_result["kept_seq_off"]) != K + 1:
+        raise ValueError("map_reads_to_clusters: the trim result's kept arrays contradict its retained count")
+
+    def host_u32(x):
+        return np.ascontiguousarray(x.cpu().numpy()).view(np.uint32) if torch.is_tensor(x) else np.ascontiguousarray(x, dtype=np.uint32)
+    if numbers is None:
+        numbers = read_numbers(names)
+    n = 0 if rs is None else rs.n
+    numbers, counts = host_u32(numbers), host_u32(counts)
+    if numbers.shape != (n,) or counts.shape != (n,):
+        raise ValueError("map_reads_to_clusters: numbers and counts must hold one value per read")
+    path = out_stem + REMAP_SUFFIX
+    index = FmIndex.from_fasta(out_stem + "_vs_genome_sorted_clusters_trimmed_orig.fa", device=engine.device_index)
+    if index.n_ref != K:
+        raise ValueError("map_reads_to_clusters: %d records in the clusters' FASTA, %d retained clusters" % (index.n_ref, K))
+    if n == 0:
+        write_remapped_rows(path, np.zeros((1, 0), np.uint64), np.zeros(0, np.uint8), None, numbers, counts, index,
+                            trim_result["kept_seq_off"], trim_result["kept_orig"], empty["rows"], threads=threads)
+        return empty
+    scratch = Engine(engine.device_index)
+    try:
+        scratch.add_library("clusters", index, exact_dict=False)
+        got = scratch.predict_remap(rs, numbers, "clusters", trim_result["kept"], int(seedLength), REMAP_TRIMS, timings=timings)
+    finally:
+        scratch.close()
+    got.pop("device", None)
+    t0 = time.perf_counter()
+    write_remapped_rows(path, rs.words.cpu().numpy().view(np.uint64), rs.lens.cpu().numpy(),
+                        None if rs.nmask is None else rs.nmask.cpu().numpy().view(np.uint64), numbers, counts, index,
+                        trim_result["kept_seq_off"], trim_result["kept_orig"], got["rows"], threads=threads)
+    if timings is not None:
+        timings["write_s"] = time.perf_counter() - t0
+    return got
+
+
 class _writer_threads:
     """MIRGE_AMD_TABLE_THREADS for the duration of one writer call (None = leave the environment alone)."""
 
@@ -284,10 +397,12 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None):
+                       sam, timings, trim=None, remap=False, numbers=None):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
-    as write_clusters / write_sorted_sam take them."""
+    as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`)."""
     from .engine import STRATUM_ALL
+    if remap and trim is None:
+        raise ValueError("remap needs trim: the reads are mapped to the clusters the trim retains")
     keys, parts = genome_libraries(engine, genome_prefix)
     if trim is not None:
         repeats, cutoff = trim
@@ -314,17 +429,21 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
         cl["trim"] = trim_clusters(engine, cl, repeats, cutoff, out_stem, names)
         cl.pop("device", None)
         cl["trim"].pop("device", None)
+        if remap:
+            cl["remap"] = map_reads_to_clusters(engine, rs, numbers, counts, cl["trim"], seedLength, out_stem, names)
     return cl
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None, trim=None):
+                    timings=None, trim=None, remap=False):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
     arrays of Engine.cluster_valid.  mapping_loc 0 = no -m.  Nothing is written when a limit is exceeded.
     trim = (repeats, clusterSeqLenCutoff) adds :557-562 (trim_clusters: the three `_clusters_trimmed` files; the return value
-    gains "trim"); repeats = load_repeats' dict over this genome, or the path of the file (None: no table)."""
+    gains "trim"); repeats = load_repeats' dict over this genome, or the path of the file (None: no table).
+    remap=True (needs trim) adds :566-601 (map_reads_to_clusters: `<out_stem>_vs_representative_seq_modified_selected_sorted.tsv`;
+    the return value gains "remap")."""
     from .engine import ReadSet
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
@@ -337,15 +456,15 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim)
+                              out_stem, sam, timings, trim, remap)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None, trim=None):
+                          sam=True, timings=None, trim=None, remap=False):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
-    names; no FASTA is parsed and no Python string is made per read.  trim: as map_and_cluster's."""
+    names; no FASTA is parsed and no Python string is made per read.  trim / remap: as map_and_cluster's."""
     import torch
     from .engine import ReadSet
     _check_policy(mapping_loc, seedLength, overlapLenCutoff)
@@ -375,7 +494,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
             seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim)
+                              out_stem, sam, timings, trim, remap, numbers)
 
 
 def sample_stem(sample):
@@ -482,13 +601,16 @@ def clusters_main(argv):
     ap.add_argument("--trim", action="store_true", help="also write the three _clusters_trimmed files")
     ap.add_argument("--repeats", metavar="FILE", help="the repeat elements (chr, start, end, name; tab-separated) for --trim")
     ap.add_argument("-clc", dest="cluster_len_cutoff", type=int, default=30)
+    ap.add_argument("--remap", action="store_true", help="with --trim: also map the reads to the retained clusters (the sorted table)")
     a = ap.parse_args(argv)
+    if a.remap and not a.trim:
+        ap.error("--remap needs --trim")
     from .engine import Engine
     try:
         eng = Engine(int(os.environ.get("MIRGE_AMD_GPU", "0")))
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
-                                 sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None)
+                                 sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -497,6 +619,9 @@ def clusters_main(argv):
     sys.stderr.write("# clusters: %d from %d alignments (%d on chr entries)\n" % (len(cl["entry"]), cl["n_rows"], cl["n_valid"]))
     if a.trim:
         sys.stderr.write("# trimmed: %d of them retained\n" % cl["trim"]["n_retained"])
+    if a.remap:
+        sys.stderr.write("# remapped: %d reads in pass 1, %d in pass 2, %d unaligned, %d rows\n" % tuple(
+            cl["remap"][k] for k in ("aligned1", "aligned2", "unaligned", "n_rows")))
     return 0
 
 
@@ -504,7 +629,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
-                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30]]\n")
+                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap]]\n")
         return 1
     return clusters_main(argv[1:])
 
