@@ -1020,6 +1020,78 @@ int mrg_write_remapped_rows(const char *path, const uint64_t *reads, uint32_t wo
                             const uint32_t *row_cluster, const uint32_t *row_offset, const uint8_t *row_mm,
                             const uint8_t *row_pass, uint32_t trim5, uint32_t trim3, uint64_t *rows);
 
+/* Predict mode's cluster feature table (reference miRge2.0.py:604: utils/generate_featureFiles.py, classes/readCluster.py)
+ * from the rows of mrg_predict_remap_rows (csrc/predict_features.hip; the rule: tests/predict_features_model.py).  The
+ * retained clusters come as per-cluster arrays: d_cl_entry / _strand / _start / _end [n_clusters] (the location cluster's,
+ * gathered by d_kept), d_kept, d_kept_seq_off / d_kept_orig of mrg_predict_trim.  Every call returns MRG_ERR_ARG when the
+ * arrays contradict each other or the sizes given (the outputs are then undefined); no lane reads or writes beyond those
+ * sizes.  Limits: rows < 2^32 - 1, reads, clusters, entries < 2^31.  All but _tally synchronise.
+ *
+ *   mrg_predict_feature_temp_bytes  HOST: the bytes of device scratch the calls below need for n_rows rows.
+ *   mrg_predict_feature_groups  DEVICE.  The groups: consecutive rows of one cluster, in row order.  d_row_group [n_rows];
+ *       d_group_off [n_rows + 1], d_group_cluster / d_group_sum / d_group_pass [n_rows], of which *n_groups (+ 1) are set.
+ *       d_group_sum = the members' counts summed in 64 bits (a read listed twice counts twice); d_group_pass = 1 iff
+ *       sum >= 10, members >= 3, start > 20 and end < d_entry_len[entry] - 20.  Nothing is compacted.
+ *   mrg_predict_feature_align  DEVICE.  d_cl_word / d_cl_len [n_clusters]: the clusters packed two bits a base, length 255
+ *       for one longer than 32 nt or with a letter other than A/C/G/T.  Per row of a passing group the first alignment
+ *       pairwise2.align.localms(cluster, read, 2, -1, -20, -20) lists: d_row_status (0 = one ungapped diagonal, 1 = a tie
+ *       settled on the device, 2 = row of a failing group, not aligned; 3 = not packable, 4 = N in the read, 5 = gapped,
+ *       6 = tie left open, 7 = no score: left to the host), d_row_diag (read base 0 under cluster position d) and
+ *       d_row_ident (equal columns over the whole overlap).  d_group_host [n_groups] = 1 for a group with a row >= 3.
+ *   mrg_predict_feature_tally  DEVICE, asynchronous.  One wave per passing group that is not host-marked: d_frame
+ *       [n_groups][4] = H, T (dashes before / behind the cluster), head, tail (first / last column whose majority base
+ *       holds 5 c >= 4 sum; tail negative); d_valid = 1 iff such a column exists; d_exact = the summed counts of the
+ *       members whose identity is their length; d_nine [n_groups][45] = the count-weighted A, T, C, G and dash of the nine
+ *       feature columns of the re-padded frame.  Other groups get valid 0 and zeros.
+ *   mrg_predict_feature_neighbors  DEVICE.  The groups with d_valid ordered by (d_entry_rank[entry], start, end, cluster
+ *       number as text): d_order [n_groups], of which the first *n_sorted are those groups; per GROUP d_nb_t (its index on
+ *       its chromosome), d_nb_up / d_nb_down (distance s2 - e1 - 1 between the intervals (start + head - H,
+ *       end + 1 + tail + T)), d_nb_flags (bit 0: no upstream neighbour, bit 1: no downstream one, bits 2-3: 0 Null, 1 Good,
+ *       2 Bad).  Groups the host worked out take part with their d_frame / d_valid patched in by the caller.
+ *   mrg_write_predict_features  HOST: `_features.tsv` and `_cluster.txt` from host copies of the arrays above, for the
+ *       groups order [n_order] in that order.  group_text: null, or per group null / its frame as text (the cluster's padded
+ *       row and every member's, '\n' between) for a group whose rows have no diagonal.  mapped != 0: `-1\tNull` in front of
+ *       every line, else `Null\tNull`.  The genome parts supply the chromosome names, lengths and template bases, the
+ *       cluster library the cluster names.  Arrays that contradict each other, or a template range that leaves its
+ *       chromosome, are MRG_ERR_ARG before a file is opened.  written[0] = blocks of `_cluster.txt`, written[1] = lines of
+ *       `_features.tsv` below the header.  Worker threads: MIRGE_AMD_TABLE_THREADS.
+ */
+int mrg_predict_feature_temp_bytes(uint64_t n_rows, uint64_t *bytes);
+int mrg_predict_feature_groups(mrg_ctx *ctx, uint64_t n_rows, const uint32_t *d_row_read, const uint32_t *d_row_cluster,
+                               uint64_t n_reads, const uint32_t *d_counts, uint64_t n_clusters, const uint32_t *d_cl_entry,
+                               const uint32_t *d_cl_start, const uint32_t *d_cl_end, const uint64_t *d_kept_seq_off,
+                               uint64_t orig_len, uint64_t n_entries, const uint32_t *d_entry_len, uint32_t *d_row_group,
+                               uint32_t *d_group_off, uint32_t *d_group_cluster, uint64_t *d_group_sum, uint8_t *d_group_pass,
+                               uint64_t *n_groups, uint64_t *n_passed, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_feature_align(mrg_ctx *ctx, uint64_t n_rows, const uint32_t *d_row_read, const uint32_t *d_row_cluster,
+                              const uint32_t *d_row_group, uint64_t n_groups, const uint8_t *d_group_pass,
+                              const uint64_t *d_reads, const uint8_t *d_lens, const uint64_t *d_nmask, uint64_t n_reads,
+                              uint64_t n_clusters, const uint64_t *d_kept_seq_off, const char *d_kept_orig, uint64_t orig_len,
+                              uint64_t *d_cl_word, uint8_t *d_cl_len, uint8_t *d_row_status, int32_t *d_row_diag,
+                              uint8_t *d_row_ident, uint8_t *d_group_host, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_feature_tally(mrg_ctx *ctx, uint64_t n_groups, const uint32_t *d_group_off, const uint32_t *d_group_cluster,
+                              const uint8_t *d_group_pass, const uint8_t *d_group_host, uint64_t n_rows,
+                              const uint32_t *d_row_read, const int32_t *d_row_diag, const uint8_t *d_row_ident,
+                              const uint64_t *d_reads, const uint8_t *d_lens, uint64_t n_reads, const uint32_t *d_counts,
+                              uint64_t n_clusters, const uint8_t *d_cl_len, uint8_t *d_valid, int32_t *d_frame,
+                              uint64_t *d_exact, uint64_t *d_nine, void *stream);
+int mrg_predict_feature_neighbors(mrg_ctx *ctx, uint64_t n_groups, const uint32_t *d_group_cluster, const uint8_t *d_valid,
+                                  const int32_t *d_frame, uint64_t n_clusters, const uint32_t *d_cl_entry,
+                                  const uint8_t *d_cl_strand, const uint32_t *d_cl_start, const uint32_t *d_cl_end,
+                                  const uint32_t *d_kept, uint64_t n_entries, const uint32_t *d_entry_rank, uint32_t *d_order,
+                                  uint32_t *d_nb_t, int64_t *d_nb_up, int64_t *d_nb_down, uint8_t *d_nb_flags,
+                                  uint64_t *n_sorted, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_write_predict_features(const char *features_path, const char *cluster_path, int mapped, const mrg_index *const *parts,
+                               uint32_t n_parts, const mrg_index *clusters, uint64_t n_clusters, const uint32_t *cl_entry,
+                               const uint8_t *cl_strand, const uint32_t *cl_start, const uint32_t *cl_end,
+                               const uint64_t *kept_seq_off, const char *kept_orig, const uint64_t *reads,
+                               uint32_t words_per_read, uint64_t stride, const uint8_t *lens, const uint64_t *nmask,
+                               const uint32_t *counts, uint64_t n_reads, uint64_t n_rows, const uint32_t *row_read,
+                               const int32_t *row_diag, uint64_t n_groups, const uint32_t *group_off,
+                               const uint32_t *group_cluster, const int32_t *frame, const uint64_t *exact, const uint64_t *nine,
+                               const uint32_t *nb_t, const int64_t *nb_up, const int64_t *nb_down, const uint8_t *nb_flags,
+                               const char *const *group_text, uint64_t n_order, const uint32_t *order, uint64_t *written);
+
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are

@@ -29,6 +29,7 @@
 #include "isomir_gff.hpp"
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
+#include "predict_features.hpp"
 #include "predict_reads.hpp"
 #include "prims.hpp"
 #include "sa_build.hpp"
@@ -3280,6 +3281,309 @@ int mrg_write_remapped_rows(const char* path, const uint64_t* reads, uint32_t wo
                                   counts,     clusters ? &clusters->ix : nullptr,     n_clusters, kept_seq_off, kept_orig, n_rows,
                                   row_read,   row_cluster,  row_offset,     row_mm,   row_pass, trim5,       trim3};
     *rows = mrg::write_remapped_rows(a);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+// ------------------------------------------------- predict mode: the cluster feature table (csrc/predict_features.hip)
+namespace {
+constexpr uint64_t kFeatMaxRows = 0xfffffffeull, kFeatMaxItems = (1ull << 31) - 1;
+// mrg_predict_feature_groups' scratch: the stat words, two uint32 arrays of n_rows + 1 and the scan's own
+struct FeatGroupScratch {
+  size_t flag32, rank, scan, total;
+  explicit FeatGroupScratch(uint64_t rows) {
+    const size_t k4 = up8((size_t)(rows + 1) * sizeof(uint32_t));
+    flag32 = up8(mrg::kFeatStatWords * sizeof(uint32_t));
+    rank = flag32 + k4;
+    scan = rank + k4;
+    total = scan + up8(mrg::prims::scan_temp_bytes(rows + 1));
+  }
+};
+// mrg_predict_feature_neighbors' scratch: the stat words, five uint64 and two uint32 arrays of G, the sort's own
+struct FeatNeighborScratch {
+  size_t key_c, key_se, key_r, keys0, keys1, vals0, vals1, sort, total;
+  explicit FeatNeighborScratch(uint64_t G) {
+    const size_t k8 = (size_t)G * sizeof(uint64_t), k4 = up8((size_t)G * sizeof(uint32_t));
+    key_c = up8(mrg::kFeatStatWords * sizeof(uint32_t));
+    key_se = key_c + k8;
+    key_r = key_se + k8;
+    keys0 = key_r + k8;
+    keys1 = keys0 + k8;
+    vals0 = keys1 + k8;
+    vals1 = vals0 + k4;
+    sort = vals1 + k4;
+    total = sort + up8(mrg::prims::radix_temp_bytes(G));
+  }
+};
+int feat_stat_error(const char* fn, const uint32_t* h_stat) {
+  if (h_stat[mrg::kFeatStatBadRow]) return fail(MRG_ERR_ARG, "%s: a row names no read or no retained cluster", fn);
+  if (h_stat[mrg::kFeatStatBadCluster])
+    return fail(MRG_ERR_ARG, "%s: a cluster on no entry, or whose end - start + 1 is not its sequence length, or sequence offsets that do not ascend", fn);
+  if (h_stat[mrg::kFeatStatBadGroups]) return fail(MRG_ERR_ARG, "%s: group offsets that do not ascend inside the rows, or a group of no cluster", fn);
+  return MRG_OK;
+}
+}  // namespace
+
+int mrg_predict_feature_temp_bytes(uint64_t n_rows, uint64_t* bytes) {
+  const char* fn = "mrg_predict_feature_temp_bytes";
+  if (!bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_rows > kFeatMaxRows) return fail(MRG_ERR_ARG, "%s: %llu rows; the limit is 2^32 - 2", fn, (unsigned long long)n_rows);
+  *bytes = std::max(FeatGroupScratch(n_rows).total, FeatNeighborScratch(n_rows).total);
+  return MRG_OK;
+}
+
+int mrg_predict_feature_groups(mrg_ctx* ctx, uint64_t n_rows, const uint32_t* d_row_read, const uint32_t* d_row_cluster, uint64_t n_reads,
+                               const uint32_t* d_counts, uint64_t n_clusters, const uint32_t* d_cl_entry, const uint32_t* d_cl_start,
+                               const uint32_t* d_cl_end, const uint64_t* d_kept_seq_off, uint64_t orig_len, uint64_t n_entries,
+                               const uint32_t* d_entry_len, uint32_t* d_row_group, uint32_t* d_group_off, uint32_t* d_group_cluster,
+                               uint64_t* d_group_sum, uint8_t* d_group_pass, uint64_t* n_groups, uint64_t* n_passed, void* d_tmp,
+                               uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_feature_groups";
+  if (!ctx || !n_groups || !n_passed) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_groups = *n_passed = 0;
+  if (n_rows > kFeatMaxRows) return fail(MRG_ERR_ARG, "%s: %llu rows; the limit is 2^32 - 2", fn, (unsigned long long)n_rows);
+  if (n_reads > kFeatMaxItems || n_clusters > kFeatMaxItems || n_entries > kFeatMaxItems)
+    return fail(MRG_ERR_ARG, "%s: reads, clusters and entries are limited to 2^31 - 1 each", fn);
+  if (!d_tmp) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_rows && (!d_row_read || !d_row_cluster || !d_counts || !d_cl_entry || !d_cl_start || !d_cl_end || !d_kept_seq_off || !d_entry_len ||
+                 !d_row_group || !d_group_off || !d_group_cluster || !d_group_sum || !d_group_pass))
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  if (n_rows && (!n_reads || !n_clusters || !n_entries)) return fail(MRG_ERR_ARG, "%s: rows without reads, clusters or entries", fn);
+  const FeatGroupScratch sc(n_rows);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
+  if (n_rows == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
+  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  const mrg::FeatRows rows{(uint32_t)n_rows, d_row_read, d_row_cluster};
+  const mrg::FeatReads reads{nullptr, nullptr, nullptr, d_counts, (uint32_t)n_reads};
+  const mrg::FeatClusters cl{(uint32_t)n_clusters, d_cl_entry, nullptr, d_cl_start, d_cl_end, nullptr, d_kept_seq_off, nullptr, orig_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kFeatStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::feat_mark_launch(rows, (uint32_t)n_reads, (uint32_t)n_clusters, flag32, stat, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_rows + 1, base + sc.scan, st));
+  uint32_t h_stat[mrg::kFeatStatWords] = {0}, G = 0;
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&G, rank + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = feat_stat_error(fn, h_stat)) return rc;   // (rows of no cluster: the groups would mean nothing)
+  if (G == 0 || G > n_rows) return fail(MRG_ERR_HIP, "%s: %u groups of %llu rows", fn, G, (unsigned long long)n_rows);
+  HIP_TRY(mrg::feat_starts_launch(rows, rank, d_row_group, d_group_off, d_group_cluster, st));
+  HIP_TRY(mrg::feat_filter_launch(G, d_group_off, d_group_cluster, rows, reads, cl, (uint32_t)n_entries, d_entry_len, d_group_sum, d_group_pass,
+                                  stat, st));
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = feat_stat_error(fn, h_stat)) return rc;
+  *n_groups = G;
+  *n_passed = h_stat[mrg::kFeatStatPassed];
+  return MRG_OK;
+}
+
+int mrg_predict_feature_align(mrg_ctx* ctx, uint64_t n_rows, const uint32_t* d_row_read, const uint32_t* d_row_cluster,
+                              const uint32_t* d_row_group, uint64_t n_groups, const uint8_t* d_group_pass, const uint64_t* d_reads,
+                              const uint8_t* d_lens, const uint64_t* d_nmask, uint64_t n_reads, uint64_t n_clusters,
+                              const uint64_t* d_kept_seq_off, const char* d_kept_orig, uint64_t orig_len, uint64_t* d_cl_word,
+                              uint8_t* d_cl_len, uint8_t* d_row_status, int32_t* d_row_diag, uint8_t* d_row_ident, uint8_t* d_group_host,
+                              void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_feature_align";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_rows > kFeatMaxRows || n_groups > n_rows) return fail(MRG_ERR_ARG, "%s: %llu groups of %llu rows (the limit is 2^32 - 2 rows)", fn,
+                                                              (unsigned long long)n_groups, (unsigned long long)n_rows);
+  if (n_reads > kFeatMaxItems || n_clusters > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: reads and clusters are limited to 2^31 - 1 each", fn);
+  if (!d_tmp || tmp_bytes < up8(mrg::kFeatStatWords * sizeof(uint32_t)) || ((uintptr_t)d_tmp & 7))
+    return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
+  if (n_clusters && (!d_kept_seq_off || (orig_len && !d_kept_orig) || !d_cl_word || !d_cl_len)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (n_rows && (!n_groups || !n_reads || !n_clusters || !d_row_read || !d_row_cluster || !d_row_group || !d_group_pass || !d_reads || !d_lens ||
+                 !d_row_status || !d_row_diag || !d_row_ident || !d_group_host))
+    return fail(MRG_ERR_ARG, "%s: null row arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = reinterpret_cast<uint32_t*>(d_tmp);
+  const mrg::FeatClusters cl{(uint32_t)n_clusters, nullptr, nullptr, nullptr, nullptr, nullptr, d_kept_seq_off, d_kept_orig, orig_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kFeatStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::feat_pack_launch(cl, d_cl_word, d_cl_len, stat, st));
+  if (n_rows) {
+    HIP_TRY(hipMemsetAsync(d_group_host, 0, n_groups, st));
+    mrg::FeatAlignArgs a;
+    a.rows = mrg::FeatRows{(uint32_t)n_rows, d_row_read, d_row_cluster};
+    a.row_group = d_row_group;
+    a.n_groups = (uint32_t)n_groups;
+    a.group_pass = d_group_pass;
+    a.reads = mrg::FeatReads{d_reads, d_lens, d_nmask, nullptr, (uint32_t)n_reads};
+    a.n_clusters = (uint32_t)n_clusters;
+    a.cl_word = d_cl_word;
+    a.cl_len = d_cl_len;
+    a.row_status = d_row_status;
+    a.row_diag = d_row_diag;
+    a.row_ident = d_row_ident;
+    a.group_host = d_group_host;
+    HIP_TRY(mrg::feat_align_launch(a, st));
+  }
+  uint32_t h_stat[mrg::kFeatStatWords] = {0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return feat_stat_error(fn, h_stat);
+}
+
+int mrg_predict_feature_tally(mrg_ctx* ctx, uint64_t n_groups, const uint32_t* d_group_off, const uint32_t* d_group_cluster,
+                              const uint8_t* d_group_pass, const uint8_t* d_group_host, uint64_t n_rows, const uint32_t* d_row_read,
+                              const int32_t* d_row_diag, const uint8_t* d_row_ident, const uint64_t* d_reads, const uint8_t* d_lens,
+                              uint64_t n_reads, const uint32_t* d_counts, uint64_t n_clusters, const uint8_t* d_cl_len, uint8_t* d_valid,
+                              int32_t* d_frame, uint64_t* d_exact, uint64_t* d_nine, void* stream) {
+  const char* fn = "mrg_predict_feature_tally";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_rows > kFeatMaxRows || n_groups > n_rows) return fail(MRG_ERR_ARG, "%s: %llu groups of %llu rows (the limit is 2^32 - 2 rows)", fn,
+                                                              (unsigned long long)n_groups, (unsigned long long)n_rows);
+  if (n_reads > kFeatMaxItems || n_clusters > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: reads and clusters are limited to 2^31 - 1 each", fn);
+  if (n_groups && (!d_group_off || !d_group_cluster || !d_group_pass || !d_group_host || !d_row_read || !d_row_diag || !d_row_ident || !d_reads ||
+                   !d_lens || !d_counts || !d_cl_len || !d_valid || !d_frame || !d_exact || !d_nine))
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  if (n_groups == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  mrg::FeatTallyArgs a;
+  a.n_groups = (uint32_t)n_groups;
+  a.group_off = d_group_off;
+  a.group_cluster = d_group_cluster;
+  a.group_pass = d_group_pass;
+  a.group_host = d_group_host;
+  a.rows = mrg::FeatRows{(uint32_t)n_rows, d_row_read, nullptr};
+  a.row_diag = d_row_diag;
+  a.row_ident = d_row_ident;
+  a.reads = mrg::FeatReads{d_reads, d_lens, nullptr, d_counts, (uint32_t)n_reads};
+  a.n_clusters = (uint32_t)n_clusters;
+  a.cl_len = d_cl_len;
+  a.valid = d_valid;
+  a.frame = d_frame;
+  a.exact = d_exact;
+  a.nine = d_nine;
+  HIP_TRY(mrg::feat_tally_launch(a, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_predict_feature_neighbors(mrg_ctx* ctx, uint64_t n_groups, const uint32_t* d_group_cluster, const uint8_t* d_valid,
+                                  const int32_t* d_frame, uint64_t n_clusters, const uint32_t* d_cl_entry, const uint8_t* d_cl_strand,
+                                  const uint32_t* d_cl_start, const uint32_t* d_cl_end, const uint32_t* d_kept, uint64_t n_entries,
+                                  const uint32_t* d_entry_rank, uint32_t* d_order, uint32_t* d_nb_t, int64_t* d_nb_up, int64_t* d_nb_down,
+                                  uint8_t* d_nb_flags, uint64_t* n_sorted, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_feature_neighbors";
+  if (!ctx || !n_sorted) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_sorted = 0;
+  if (n_groups > kFeatMaxRows) return fail(MRG_ERR_ARG, "%s: %llu groups; the limit is 2^32 - 2", fn, (unsigned long long)n_groups);
+  if (n_clusters > kFeatMaxItems || n_entries > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: clusters and entries are limited to 2^31 - 1 each", fn);
+  if (!d_tmp) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_groups && (!n_clusters || !n_entries || !d_group_cluster || !d_valid || !d_frame || !d_cl_entry || !d_cl_strand || !d_cl_start ||
+                   !d_cl_end || !d_kept || !d_entry_rank || !d_order || !d_nb_t || !d_nb_up || !d_nb_down || !d_nb_flags))
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  const FeatNeighborScratch sc(n_groups);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
+  if (n_groups == 0) return MRG_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint64_t* key_c = reinterpret_cast<uint64_t*>(base + sc.key_c);
+  uint64_t* key_se = reinterpret_cast<uint64_t*>(base + sc.key_se);
+  uint64_t* key_r = reinterpret_cast<uint64_t*>(base + sc.key_r);
+  uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base + sc.keys0), reinterpret_cast<uint64_t*>(base + sc.keys1)};
+  uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + sc.vals0), reinterpret_cast<uint32_t*>(base + sc.vals1)};
+  const uint32_t G = (uint32_t)n_groups;
+  mrg::FeatNeighborArgs a;
+  a.n_groups = G;
+  a.group_cluster = d_group_cluster;
+  a.valid = d_valid;
+  a.frame = d_frame;
+  a.cl = mrg::FeatClusters{(uint32_t)n_clusters, d_cl_entry, d_cl_strand, d_cl_start, d_cl_end, d_kept, nullptr, nullptr, 0};
+  a.n_entries = (uint32_t)n_entries;
+  a.entry_rank = d_entry_rank;
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kFeatStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::feat_keys_launch(a, key_c, key_se, key_r, vals[0], stat, st));
+  // stable passes from the last key to the first: cluster number, (start, end), chromosome rank
+  HIP_TRY(hipMemcpyAsync(keys[0], key_c, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  uint32_t at = 0;  // which vals buffer holds the order so far
+  const uint64_t* later[2] = {key_se, key_r};
+  const uint32_t bits[3] = {mrg::kRemapKeyBits, 64u, 32u};
+  for (uint32_t pass = 0; pass < 3; ++pass) {
+    if (pass) HIP_TRY(mrg::feat_gather_keys_launch(later[pass - 1], vals[at], G, keys[0], st));
+    bool second = false;
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[0], keys[1], vals[at], vals[at ^ 1u], G, bits[pass], base + sc.sort, st, &second));
+    if (second) at ^= 1u;
+    if (pass == 2 && second) std::swap(keys[0], keys[1]);
+  }
+  HIP_TRY(hipMemcpyAsync(d_order, vals[at], (size_t)G * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(mrg::feat_neighbors_launch(a, keys[0], d_order, d_nb_t, d_nb_up, d_nb_down, d_nb_flags, stat, st));
+  uint32_t h_stat[mrg::kFeatStatWords] = {0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = feat_stat_error(fn, h_stat)) return rc;
+  *n_sorted = h_stat[mrg::kFeatStatSorted];
+  return MRG_OK;
+}
+
+int mrg_write_predict_features(const char* features_path, const char* cluster_path, int mapped, const mrg_index* const* parts,
+                               uint32_t n_parts, const mrg_index* clusters, uint64_t n_clusters, const uint32_t* cl_entry,
+                               const uint8_t* cl_strand, const uint32_t* cl_start, const uint32_t* cl_end, const uint64_t* kept_seq_off,
+                               const char* kept_orig, const uint64_t* reads, uint32_t words_per_read, uint64_t stride, const uint8_t* lens,
+                               const uint64_t* nmask, const uint32_t* counts, uint64_t n_reads, uint64_t n_rows, const uint32_t* row_read,
+                               const int32_t* row_diag, uint64_t n_groups, const uint32_t* group_off, const uint32_t* group_cluster,
+                               const int32_t* frame, const uint64_t* exact, const uint64_t* nine, const uint32_t* nb_t, const int64_t* nb_up,
+                               const int64_t* nb_down, const uint8_t* nb_flags, const char* const* group_text, uint64_t n_order,
+                               const uint32_t* order, uint64_t* written) {
+  const char* fn = "mrg_write_predict_features";
+  if (!features_path || !cluster_path || !written || !kept_seq_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  written[0] = written[1] = 0;
+  if (n_clusters && (!clusters || !cl_entry || !cl_strand || !cl_start || !cl_end || !kept_orig)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (n_reads && (!reads || !lens || !counts)) return fail(MRG_ERR_ARG, "%s: null read arrays", fn);
+  if (n_rows && (!row_read || !row_diag)) return fail(MRG_ERR_ARG, "%s: null row arrays", fn);
+  if (n_groups && (!group_off || !group_cluster || !frame || !exact || !nine || !nb_t || !nb_up || !nb_down || !nb_flags))
+    return fail(MRG_ERR_ARG, "%s: null group arrays", fn);
+  if (n_order && (!order || !n_groups)) return fail(MRG_ERR_ARG, "%s: an order without groups", fn);
+  std::vector<const mrg::FmIndex*> ix;
+  int rc = index_list(fn, parts, n_parts, &ix);
+  if (rc != MRG_OK) return rc;
+  try {
+    mrg::FeatWriteArgs a;
+    a.features_path = features_path;
+    a.cluster_path = cluster_path;
+    a.mapped = mapped != 0;
+    a.parts = &ix;
+    a.clusters = clusters ? &clusters->ix : nullptr;
+    a.n_clusters = n_clusters;
+    a.cl_entry = cl_entry;
+    a.cl_strand = cl_strand;
+    a.cl_start = cl_start;
+    a.cl_end = cl_end;
+    a.kept_seq_off = kept_seq_off;
+    a.kept_orig = kept_orig;
+    a.reads = reads;
+    a.W = words_per_read;
+    a.stride = stride;
+    a.lens = lens;
+    a.nmask = nmask;
+    a.counts = counts;
+    a.n_reads = n_reads;
+    a.n_rows = n_rows;
+    a.row_read = row_read;
+    a.row_diag = row_diag;
+    a.n_groups = n_groups;
+    a.group_off = group_off;
+    a.group_cluster = group_cluster;
+    a.frame = frame;
+    a.exact = exact;
+    a.nine = nine;
+    a.nb_t = nb_t;
+    a.nb_up = nb_up;
+    a.nb_down = nb_down;
+    a.nb_flags = nb_flags;
+    a.group_text = group_text;
+    a.n_order = n_order;
+    a.order = order;
+    mrg::write_predict_features(a, written);
     return MRG_OK;
   } catch (const std::invalid_argument& e) {
     return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());

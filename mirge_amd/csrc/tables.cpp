@@ -198,8 +198,6 @@ uint64_t write_read_table(const char* path, bool mapped, const char* header, boo
 // Python dict records in between (1.5 s of the command line's 3 s on a 32 M-read sample).  The reference's arithmetic in
 // the reference's order, so that the text comes out byte for byte: str(float) of Python 2 is "%.12g" (+ ".0" for a whole
 // number), math.log(x, 2) is log(x) / log(2), calcEntropy adds -1 * f * log2(f) over the entries > 1 in list order.
-namespace {
-
 void py2_float(double x, std::string& out) {
   char buf[40];
   if (x != x) {
@@ -214,6 +212,8 @@ void py2_float(double x, std::string& out) {
   out.append(buf, (size_t)len);
   if (!std::memchr(buf, '.', (size_t)len) && !std::memchr(buf, 'e', (size_t)len) && !std::memchr(buf, 'n', (size_t)len)) out += ".0";
 }
+
+namespace {
 
 double calc_entropy(const uint64_t* v, size_t n) {
   uint64_t total = 0;

@@ -1,9 +1,13 @@
 // Streaming writers of mapped.csv / unmapped.csv from columnar arrays (internal header).
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace mrg {
+
+// str(float) as Python 2.7 prints it (%.12g, `.0` appended when neither `.` nor `e` shows), appended to out; tables.cpp.
+void py2_float(double x, std::string& out);
 
 // Returns the number of rows written; throws std::runtime_error on I/O errors.
 uint64_t write_read_table(const char* path, bool mapped, const char* header, bool append, const uint64_t* reads,

@@ -1447,6 +1447,124 @@ class Engine:
             timings.update(list_ms=ev[0].elapsed_time(ev[1]), rows_ms=ev[1].elapsed_time(ev[2]), download_ms=ev[2].elapsed_time(ev[3]))
         return dict(rows=host, n_rows=int(host[0].shape[0]), aligned1=a1, aligned2=a2, unaligned=n - a1 - a2, device=rows)
 
+    def predict_features(self, reads, counts, rows, clusters, entry_len, entry_rank, host_groups=None, timings=None):
+        """Predict mode's cluster feature table from the rows of predict_remap (mrg_predict_feature_groups / _align /
+        _tally / _neighbors; the rule of the reference's generate_featureFiles.py and readCluster.py).  reads: the ReadSet
+        the rows index; counts [n]: the reads' counts; rows = (read, cluster) device tensors or host arrays in file order;
+        clusters: the retained clusters as a dict of entry, strand, start, end, kept [K] (host arrays or device tensors),
+        kept_seq_off [K + 1] and kept_orig (bytes); entry_len / entry_rank [entries]: every genome entry's length and the
+        position of its name among the sorted names.
+        A group with a row the device leaves to the host (a read or cluster beyond 32 nt, an N, a gapped or unsettled
+        alignment) is handed to host_groups(g, row_lo, row_hi, cluster) -> None (no stable column) or a dict of H, T, head,
+        tail, exact, nine [45]; its numbers join the others before the neighbour step.  Without host_groups such a group
+        is an error.
+        Returns a dict of host arrays: row_group, row_status, row_diag, row_ident [rows]; group_off [G + 1], group_cluster,
+        group_sum, group_pass, group_host, valid, frame [G, 4] (H, T, head, tail), exact, nine [G, 45], nb_t, nb_up, nb_down,
+        nb_flags [G]; order [n_sorted] = the groups with a stable column in file order; n_groups, n_passed, n_sorted,
+        host_results {g: what host_groups returned}.  timings gets device_ms (events around the four calls, the host groups'
+        time included when there are any) and download_ms."""
+        torch = _torch()
+        dev = self.device
+        n = reads.n
+        counts = self._dev_u32(counts, "predict_features: counts")
+        row_read, row_cluster = (self._dev_u32(t, "predict_features: rows") for t in rows[:2])
+        T = int(row_read.shape[0])
+        if int(row_cluster.shape[0]) != T or int(counts.shape[0]) != n:
+            raise ValueError("predict_features: rows (read, cluster) must match each other and counts the reads")
+        cl = {k: self._dev_u32(clusters[k], "predict_features: " + k) for k in ("entry", "start", "end", "kept")}
+        K = int(cl["entry"].shape[0])
+        strand = clusters["strand"]
+        if not torch.is_tensor(strand):
+            strand = torch.from_numpy(np.ascontiguousarray(strand, dtype=np.uint8)).to(dev)
+        strand = self._expect(strand, torch.uint8, "predict_features: strand").contiguous()
+        soff = np.ascontiguousarray(clusters["kept_seq_off"], dtype=np.uint64)
+        orig = np.frombuffer(bytes(clusters["kept_orig"]), dtype=np.uint8)
+        if any(int(t.shape[0]) != K for t in (cl["start"], cl["end"], cl["kept"], strand)) or soff.shape != (K + 1,) or \
+                int(soff[-1]) != orig.shape[0]:
+            raise ValueError("predict_features: entry, strand, start, end, kept [K] and kept_seq_off [K + 1] closing at kept_orig must match")
+        entry_len, entry_rank = self._dev_u32(entry_len, "predict_features: entry_len"), self._dev_u32(entry_rank, "predict_features: entry_rank")
+        E = int(entry_len.shape[0])
+        if int(entry_rank.shape[0]) != E:
+            raise ValueError("predict_features: one length and one rank per entry")
+        if T and (n == 0 or K == 0 or E == 0):
+            raise ValueError("predict_features: rows without reads, clusters or entries")
+        d_soff = torch.from_numpy(soff.view(np.int64)).to(dev)
+        d_orig = torch.from_numpy(np.array(orig if orig.shape[0] else np.zeros(1, np.uint8))).to(dev)
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_feature_temp_bytes(T, C.byref(need)))
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
+        tmp = e(max(int(need.value), 64), torch.uint8)
+        row_group, group_off, group_cluster = e(T, torch.int32), e(T + 1, torch.int32), e(T, torch.int32)
+        group_sum, group_pass = e(T, torch.int64), e(T, torch.uint8)
+        ev = []
+
+        def mark():
+            if timings is not None:
+                x = torch.cuda.Event(enable_timing=True)
+                x.record(torch.cuda.current_stream(dev))
+                ev.append(x)
+        ptr = lambda t: t.data_ptr()
+        G, P, S = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        mark()
+        check(self._lib.mrg_predict_feature_groups(
+            self._h, T, ptr(row_read), ptr(row_cluster), n, ptr(counts), K, ptr(cl["entry"]), ptr(cl["start"]), ptr(cl["end"]),
+            ptr(d_soff), int(orig.shape[0]), E, ptr(entry_len), ptr(row_group), ptr(group_off), ptr(group_cluster), ptr(group_sum),
+            ptr(group_pass), C.byref(G), C.byref(P), ptr(tmp), tmp.numel(), self._stream_ptr()))
+        G = int(G.value)
+        cl_word, cl_len = e(K, torch.int64), e(K, torch.uint8)
+        row_status, row_diag, row_ident, group_host = e(T, torch.uint8), e(T, torch.int32), e(T, torch.uint8), e(G, torch.uint8)
+        check(self._lib.mrg_predict_feature_align(
+            self._h, T, ptr(row_read), ptr(row_cluster), ptr(row_group), G, ptr(group_pass), ptr(reads.words) if n else None,
+            ptr(reads.lens) if n else None, None if reads.nmask is None else ptr(reads.nmask), n, K, ptr(d_soff), ptr(d_orig),
+            int(orig.shape[0]), ptr(cl_word), ptr(cl_len), ptr(row_status), ptr(row_diag), ptr(row_ident), ptr(group_host), ptr(tmp),
+            tmp.numel(), self._stream_ptr()))
+        valid, frame, exact, nine = e(G, torch.uint8), e(4 * G, torch.int32), e(G, torch.int64), e(45 * G, torch.int64)
+        check(self._lib.mrg_predict_feature_tally(
+            self._h, G, ptr(group_off), ptr(group_cluster), ptr(group_pass), ptr(group_host), T, ptr(row_read), ptr(row_diag),
+            ptr(row_ident), ptr(reads.words) if n else None, ptr(reads.lens) if n else None, n, ptr(counts), K, ptr(cl_len), ptr(valid),
+            ptr(frame), ptr(exact), ptr(nine), self._stream_ptr()))
+        h_pass, h_host = group_pass.cpu().numpy()[:G], group_host.cpu().numpy()[:G]
+        h_off, h_gc = group_off.cpu().numpy()[:G + 1].view(np.uint32), group_cluster.cpu().numpy()[:G].view(np.uint32)
+        todo = np.flatnonzero((h_pass != 0) & (h_host != 0))
+        host_results = {}
+        if todo.size:
+            if host_groups is None:
+                raise ValueError("predict_features: %d groups hold a row the device leaves to the host and no host_groups was given" % todo.size)
+            h_valid, h_frame = valid.cpu().numpy(), frame.cpu().numpy().reshape(-1, 4)
+            h_exact, h_nine = exact.cpu().numpy(), nine.cpu().numpy().reshape(-1, 45)
+            for g in todo:
+                got = host_groups(int(g), int(h_off[g]), int(h_off[g + 1]), int(h_gc[g]))
+                host_results[int(g)] = got
+                if got is None:
+                    continue
+                h_valid[g] = 1
+                h_frame[g] = (got["H"], got["T"], got["head"], got["tail"])
+                h_exact[g] = got["exact"]
+                h_nine[g] = got["nine"]
+            valid, frame = torch.from_numpy(h_valid).to(dev), torch.from_numpy(h_frame.reshape(-1)).to(dev)
+            exact, nine = torch.from_numpy(h_exact).to(dev), torch.from_numpy(h_nine.reshape(-1)).to(dev)
+        order, nb_t, nb_flags = e(G, torch.int32), e(G, torch.int32), e(G, torch.uint8)
+        nb_up, nb_down = e(G, torch.int64), e(G, torch.int64)
+        check(self._lib.mrg_predict_feature_neighbors(
+            self._h, G, ptr(group_cluster), ptr(valid), ptr(frame), K, ptr(cl["entry"]), ptr(strand), ptr(cl["start"]), ptr(cl["end"]),
+            ptr(cl["kept"]), E, ptr(entry_rank), ptr(order), ptr(nb_t), ptr(nb_up), ptr(nb_down), ptr(nb_flags), C.byref(S), ptr(tmp),
+            tmp.numel(), self._stream_ptr()))
+        S = int(S.value)
+        mark()
+        u32 = lambda t, k: t.cpu().numpy()[:k].view(np.uint32)
+        out = dict(row_group=u32(row_group, T), row_status=row_status.cpu().numpy()[:T], row_diag=row_diag.cpu().numpy()[:T],
+                   row_ident=row_ident.cpu().numpy()[:T], group_off=h_off, group_cluster=h_gc,
+                   group_sum=group_sum.cpu().numpy()[:G].view(np.uint64), group_pass=h_pass, group_host=h_host,
+                   valid=valid.cpu().numpy()[:G], frame=frame.cpu().numpy()[:4 * G].reshape(G, 4),
+                   exact=exact.cpu().numpy()[:G].view(np.uint64), nine=nine.cpu().numpy()[:45 * G].view(np.uint64).reshape(G, 45),
+                   nb_t=u32(nb_t, G), nb_up=nb_up.cpu().numpy()[:G], nb_down=nb_down.cpu().numpy()[:G], nb_flags=nb_flags.cpu().numpy()[:G],
+                   order=u32(order, G)[:S], n_groups=G, n_passed=int(P.value), n_sorted=S, host_results=host_results)
+        mark()
+        if timings is not None:
+            ev[-1].synchronize()
+            timings.update(device_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+        return out
+
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
         mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask

@@ -12,7 +12,7 @@ so the samtools view / sort / index / view round trip of this stage is gone.  Ro
 alignments with equal (entry, strand, position) is read order: a choice, not pinned against a real `samtools sort`.
 
     python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> -m 3 -l 25 --overlap 14 -o <out_stem> [--no-sam]
-                                         [--trim [--repeats FILE] [-clc 30] [--remap]]
+                                         [--trim [--repeats FILE] [-clc 30] [--remap [--features]]]
 
 With `trim=(repeats, cutoff)` / `--trim` the next two calls of the reference (preTrimClusteredSeq, generate_Seq; miRge2.0.py:557-562)
 run over the same device arrays (Engine.predict_trim = mrg_predict_trim; mrg_write_trimmed_clusters) and add
@@ -28,6 +28,13 @@ clusters, two bowtie passes of the same reads, utils/processSam.py, `sort -k6,6 
 (map_reads_to_clusters: Engine.predict_remap = mrg_predict_trim_reads / mrg_predict_remap_rows; mrg_write_remapped_rows) and adds
 
     <out_stem>_vs_representative_seq_modified_selected_sorted.tsv    the only file generate_featureFiles reads
+
+With `features=True` / `--features` (needs the remap) the call after that (miRge2.0.py:604, generate_featureFiles) runs over the
+rows the remap left on the device (cluster_features: Engine.predict_features = mrg_predict_feature_groups / _align / _tally /
+_neighbors; mrg_write_predict_features) and adds
+
+    <out_stem>_vs_representative_seq_modified_selected_sorted_features.tsv    one line per cluster with a stable stretch
+    <out_stem>_vs_representative_seq_modified_selected_sorted_cluster.txt     the aligned members of every cluster that got that far
 
 The device is $MIRGE_AMD_GPU (default 0).  Limits: reads up to 255 nt, fewer than 2^32 - 1 alignment rows, positions
 below 2^31; beyond them the call fails naming the limit and writes nothing.
@@ -300,7 +307,8 @@ def read_numbers(names):
     return out
 
 
-def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, out_stem, names=None, threads=None, timings=None):
+def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, out_stem, names=None, threads=None, timings=None,
+                          keep_device=False):
     """The reference's miRge2.0.py:566-601 from the arrays: the sample's filtered reads (rs: the ReadSet the genome stage
     listed; numbers / counts [n]: their `mir<number>_<count>`, host arrays or device tensors; numbers None = read from
     `names`, a list) against the clusters trim_clusters retained (trim_result: its return value), in two passes -- bowtie's
@@ -310,7 +318,9 @@ def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, 
     host arrays in file order), n_rows, aligned1, aligned2, unaligned (reads).
     The cluster library is built on the device from `<out_stem>_vs_genome_sorted_clusters_trimmed_orig.fa`, the file the
     trim wrote, and is resident on an engine of its own for the duration of the call: engine.libs is untouched.  With no
-    retained cluster nothing is written and every count is 0 (the reference aborts there)."""
+    retained cluster nothing is written and every count is 0 (the reference aborts there).
+    keep_device=True leaves the rows on the device too ("device": the tensors of Engine.predict_remap) and adds "index", the
+    cluster library, for cluster_features."""
     import time
     import torch
     from .engine import Engine
@@ -347,7 +357,10 @@ def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, 
         got = scratch.predict_remap(rs, numbers, "clusters", trim_result["kept"], int(seedLength), REMAP_TRIMS, timings=timings)
     finally:
         scratch.close()
-    got.pop("device", None)
+    if keep_device:
+        got["index"] = index
+    else:
+        got.pop("device", None)
     t0 = time.perf_counter()
     write_remapped_rows(path, rs.words.cpu().numpy().view(np.uint64), rs.lens.cpu().numpy(),
                         None if rs.nmask is None else rs.nmask.cpu().numpy().view(np.uint64), numbers, counts, index,
@@ -355,6 +368,203 @@ def map_reads_to_clusters(engine, rs, numbers, counts, trim_result, seedLength, 
     if timings is not None:
         timings["write_s"] = time.perf_counter() - t0
     return got
+
+
+FEATURES_SUFFIX, CLUSTER_SUFFIX = "_features.tsv", "_cluster.txt"
+
+
+def retained_clusters(cl, trim_result):
+    """entry, strand, start, end of the clusters the trim retained (host arrays [K]), from Engine.cluster_valid's arrays."""
+    kept = np.ascontiguousarray(trim_result["kept"], dtype=np.uint32).astype(np.int64)
+    return {k: np.ascontiguousarray(np.asarray(cl[k])[kept], dtype=dt)
+            for k, dt in (("entry", np.uint32), ("strand", np.uint8), ("start", np.uint32), ("end", np.uint32))}
+
+
+def ratio_reached(c, total):
+    """float(c) / total >= 0.8 as the reference asks it, decided in integers."""
+    return 5 * int(c) >= 4 * int(total)
+
+
+def host_group(cseq, seqs, counts):
+    """One group of the feature table worked out on the host, for the groups the device leaves (a read or cluster beyond
+    32 nt, an N, a gapped or unsettled alignment): a2i.local_pair per member, the frame, the column tallies and the nine
+    feature columns' counts.  Returns (rows, numbers): rows = the cluster's padded row and every member's; numbers = None
+    without a stable column, else a dict of H, T, head, tail, exact and nine [45] as mrg_predict_feature_tally leaves them."""
+    from .a2i import local_pair
+    rows, exact = [], 0
+    for seq, count in zip(seqs, counts):
+        cpad, spad = local_pair(cseq, seq)
+        if sum(1 for x, y in zip(cpad, spad) if x == y and x != "-") == len(seq):
+            exact += int(count)
+        if not rows:
+            rows = [cpad, spad]
+        elif cpad == rows[0]:
+            rows.append(spad)
+        else:
+            h1, h2 = cpad.index(cseq), rows[0].index(cseq)
+            dh, dt = h1 - h2, (len(cpad) - h1) - (len(rows[0]) - h2)
+            if dh > 0 or dt > 0:
+                rows = ["-" * max(dh, 0) + r + "-" * max(dt, 0) for r in rows]
+            rows.append("-" * max(-dh, 0) + spad + "-" * max(-dt, 0))
+    width, total = len(rows[0]), sum(int(c) for c in counts)
+
+    def tally(x):   # A, T, C, G, dash of column x; a column outside the frame is padding
+        t = [0, 0, 0, 0, 0]
+        for row, count in zip(rows[1:], counts):
+            t["ATCG".find(row[x]) if 0 <= x < width else 4] += int(count)
+        return t
+    stable = [ratio_reached(max(tally(x)[:4]), total) for x in range(width)]
+    if not any(stable):
+        return rows, None
+    head = stable.index(True)
+    tail = (width - 1 - stable[::-1].index(True)) - width
+    pad_t = max(0, 6 + tail + 1)
+    tp = tail if pad_t == 0 else -6
+    cols = [head - 3 + k for k in range(3)] + [width + pad_t + tp + k for k in range(6)]
+    nine = [v for x in cols for v in tally(x)]
+    H, T = len(rows[0]) - len(rows[0].lstrip("-")), len(rows[0]) - len(rows[0].rstrip("-"))
+    return rows, dict(H=H, T=T, head=head, tail=tail, exact=exact, nine=nine)
+
+
+def write_predict_features(table_path, parts, index, clusters, kept_seq_off, kept_orig, words, lens, nmask, counts, res, group_text=None,
+                           threads=None):
+    """mrg_write_predict_features: `<table>_features.tsv` and `<table>_cluster.txt` next to the table `table_path` names,
+    from host arrays -- the genome's parts, the cluster library, the retained clusters (entry, strand, start, end;
+    kept_seq_off, kept_orig), the packed reads with their counts, and res = the dict of Engine.predict_features with
+    row_read added.  group_text: {group: text} for the groups the host worked out.  Returns (cluster blocks, feature lines)."""
+    from . import _native
+    lib = _native.load()
+    base = os.path.basename(table_path).split("_")
+    if base[0] == "mapped" and len(base) > 1 and base[1] == "mirna":
+        raise ValueError("a table named mapped_mirna_* is compared with the known miRNA coordinates and gets four more files: not built")
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    if words.ndim != 2:
+        raise ValueError("write_predict_features: words must be [W, n]")
+    W, n = words.shape
+    lens = np.ascontiguousarray(lens, dtype=np.uint8)
+    nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    soff = np.ascontiguousarray(kept_seq_off, dtype=np.uint64)
+    orig = np.frombuffer(bytes(kept_orig), dtype=np.uint8)
+    cl = {k: np.ascontiguousarray(clusters[k], dtype=dt) for k, dt in
+          (("entry", np.uint32), ("strand", np.uint8), ("start", np.uint32), ("end", np.uint32))}
+    K = int(soff.shape[0]) - 1
+    if lens.shape != (n,) or counts.shape != (n,) or (nm is not None and nm.shape != words.shape):
+        raise ValueError("write_predict_features: words [W, n], nmask, lens and counts [n] must match")
+    if K < 0 or int(soff[-1]) != orig.shape[0] or (index.n_ref if index is not None else 0) != K or any(a.shape != (K,) for a in cl.values()):
+        raise ValueError("write_predict_features: entry, strand, start, end [K], kept_seq_off [K + 1] closing at kept_orig and "
+                         "the library's K entries must match")
+    G = int(res["n_groups"])
+    row_read = np.ascontiguousarray(res["row_read"], dtype=np.uint32)
+    row_diag = np.ascontiguousarray(res["row_diag"], dtype=np.int32)
+    goff = np.ascontiguousarray(res["group_off"], dtype=np.uint32)
+    arr = {k: np.ascontiguousarray(res[k], dtype=dt) for k, dt in
+           (("group_cluster", np.uint32), ("frame", np.int32), ("exact", np.uint64), ("nine", np.uint64), ("nb_t", np.uint32),
+            ("nb_up", np.int64), ("nb_down", np.int64), ("nb_flags", np.uint8))}
+    order = np.ascontiguousarray(res["order"], dtype=np.uint32)
+    if row_diag.shape != row_read.shape or (G and goff.shape != (G + 1,)) or arr["frame"].size != 4 * G or arr["nine"].size != 45 * G or \
+            any(arr[k].shape[0] != G for k in ("group_cluster", "exact", "nb_t", "nb_up", "nb_down", "nb_flags")):
+        raise ValueError("write_predict_features: the row arrays [rows] and the group arrays [G] do not fit each other")
+    texts = None
+    if group_text:
+        texts = (C.c_char_p * max(G, 1))()
+        for g, text in group_text.items():
+            if not 0 <= int(g) < G:
+                raise ValueError("write_predict_features: text for group %d of %d" % (g, G))
+            texts[int(g)] = text.encode("ascii")
+    hs = (C.c_void_p * max(len(parts), 1))(*[p._h.value for p in parts])
+    written = (C.c_uint64 * 2)()
+    with _writer_threads(threads):
+        rc = lib.mrg_write_predict_features(
+            os.fsencode(table_path[:-4] + FEATURES_SUFFIX), os.fsencode(table_path[:-4] + CLUSTER_SUFFIX), int(base[0] == "mapped"), hs,
+            len(parts), index._h if index is not None else None, K, _ptr(cl["entry"]), _ptr(cl["strand"]), _ptr(cl["start"]), _ptr(cl["end"]),
+            soff.ctypes.data, _ptr(orig), _ptr(words), W, n, _ptr(lens), None if nm is None else _ptr(nm), _ptr(counts), n,
+            len(row_read), _ptr(row_read), _ptr(row_diag), G, _ptr(goff), _ptr(arr["group_cluster"]), _ptr(arr["frame"]), _ptr(arr["exact"]),
+            _ptr(arr["nine"]), _ptr(arr["nb_t"]), _ptr(arr["nb_up"]), _ptr(arr["nb_down"]), _ptr(arr["nb_flags"]), texts, len(order),
+            _ptr(order), written)
+    if rc != 0:
+        msg = (lib.mrg_last_error() or b"").decode("utf-8", "replace")
+        if "leaves its chromosome" in msg:   # (the reference slices a shorter template there and prints garbage)
+            raise ValueError(msg)
+        _native.check(rc)
+    return int(written[0]), int(written[1])
+
+
+def entry_tables(parts):
+    """(entry_len, entry_rank) uint32 over the genome's entries: every entry's length, and the position of its name among
+    the names in Python's string order (the order the reference walks the chromosomes in)."""
+    from . import _native
+    names, lens = [], []
+    for ix in parts:
+        ln = C.c_uint32()
+        for i, nm in enumerate(ix.names):
+            _native.check(ix._lib.mrg_index_seq(ix._h, i, None, 0, C.byref(ln)))   # (no buffer: the length alone)
+            names.append(nm)
+            lens.append(int(ln.value))
+    rank = np.zeros(len(names), dtype=np.uint32)
+    rank[np.array(sorted(range(len(names)), key=lambda i: names[i]), dtype=np.int64)] = np.arange(len(names), dtype=np.uint32)
+    return np.array(lens, dtype=np.uint32), rank
+
+
+def cluster_features(engine, rs, counts, trim_result, remap_result, parts, out_stem, threads=None, timings=None):
+    """The reference's miRge2.0.py:604 (generate_featureFiles) from the arrays: the rows map_reads_to_clusters left
+    (remap_result: its return value with keep_device=True; rs / counts: the reads it mapped) against the clusters the trim
+    retained (trim_result: trim_clusters' return value plus "clusters" = retained_clusters(...)) on the genome `parts`.
+    Writes `<out_stem>_vs_representative_seq_modified_selected_sorted_features.tsv` and `..._cluster.txt`; returns the dict
+    of Engine.predict_features plus seen / passed / written (groups), lines (of `_features.tsv`), host_groups and
+    row_status_counts [8].  With no retained cluster or no row the partial header and an empty `_cluster.txt` are written.
+    timings gets device_ms, download_ms, host_s and write_s."""
+    import time
+    import torch
+    table_path = out_stem + REMAP_SUFFIX
+    clusters = trim_result.get("clusters")
+    K = len(trim_result["kept"])
+    if clusters is None or any(len(clusters[k]) != K for k in ("entry", "strand", "start", "end")):
+        raise ValueError("cluster_features: the trim result needs \"clusters\" = retained_clusters(...) over its kept clusters")
+    n_rows = int(remap_result["n_rows"])
+    empty = dict(n_groups=0, n_passed=0, n_sorted=0, seen=0, passed=0, written=0, lines=0, host_groups=0,
+                 row_status_counts=np.zeros(8, np.int64))
+    if K == 0 or n_rows == 0 or rs is None:
+        for suffix, text in ((FEATURES_SUFFIX, _FEATURES_HEADER_HEAD), (CLUSTER_SUFFIX, "")):
+            with open(table_path[:-4] + suffix, "w") as fh:
+                fh.write(text)
+        return empty
+    if "device" not in remap_result or "index" not in remap_result:
+        raise ValueError("cluster_features: the remap result must come from map_reads_to_clusters(..., keep_device=True)")
+    index = remap_result["index"]
+    entry_len, entry_rank = entry_tables(parts)
+    counts = np.ascontiguousarray(counts.cpu().numpy()).view(np.uint32) if torch.is_tensor(counts) else np.ascontiguousarray(counts, dtype=np.uint32)
+    words = rs.words.cpu().numpy().view(np.uint64)
+    lens = rs.lens.cpu().numpy()
+    nmask = None if rs.nmask is None else rs.nmask.cpu().numpy().view(np.uint64)
+    row_read = remap_result["rows"][0]
+    soff = np.ascontiguousarray(trim_result["kept_seq_off"], dtype=np.uint64)
+    orig = bytes(trim_result["kept_orig"])
+    texts, host_s = {}, [0.0]
+
+    def host_groups(g, lo, hi, c):
+        t0 = time.perf_counter()
+        members = [int(r) for r in row_read[lo:hi]]
+        seqs = pack.unpack_reads(words[:, members], lens[members], None if nmask is None else nmask[:, members])
+        rows, numbers = host_group(orig[int(soff[c]):int(soff[c + 1])].decode("ascii"), seqs, counts[members])
+        texts[g] = "\n".join(rows)
+        host_s[0] += time.perf_counter() - t0
+        return numbers
+    cl = dict(clusters, kept=trim_result["kept"], kept_seq_off=soff, kept_orig=orig)
+    res = engine.predict_features(rs, counts, remap_result["device"][:2], cl, entry_len, entry_rank, host_groups, timings)
+    res["row_read"] = row_read
+    t0 = time.perf_counter()
+    blocks, lines = write_predict_features(table_path, parts, index, clusters, soff, orig, words, lens, nmask, counts, res, texts, threads)
+    if timings is not None:
+        timings.update(host_s=host_s[0], write_s=time.perf_counter() - t0)
+    res.update(seen=res["n_groups"], passed=res["n_passed"], written=blocks, lines=lines, host_groups=len(texts),
+               row_status_counts=np.bincount(res["row_status"], minlength=8))
+    return res
+
+
+_FEATURES_HEADER_HEAD = ("realMicRNA\trealMicRNAName\tchr\tstartPos\tendPos\tclusterName\tclusterSeq\tmajoritySeq\tstableClusterSeq\t"
+                         "alignedClusterSeq\tadjustedClusterSeq\tclusterSecondSeq\ttemplateSeq\tseqCount\treadCountSum\texactMatchRatio\t"
+                         "headUnstableLength\ttailUnstableLength\t")
 
 
 class _writer_threads:
@@ -397,12 +607,14 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None, remap=False, numbers=None):
+                       sam, timings, trim=None, remap=False, numbers=None, features=False):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
     as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`)."""
     from .engine import STRATUM_ALL
     if remap and trim is None:
         raise ValueError("remap needs trim: the reads are mapped to the clusters the trim retains")
+    if features and not remap:
+        raise ValueError("features needs remap: the feature table is built from the rows of the second mapping")
     keys, parts = genome_libraries(engine, genome_prefix)
     if trim is not None:
         repeats, cutoff = trim
@@ -430,12 +642,18 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
         cl.pop("device", None)
         cl["trim"].pop("device", None)
         if remap:
-            cl["remap"] = map_reads_to_clusters(engine, rs, numbers, counts, cl["trim"], seedLength, out_stem, names)
+            cl["remap"] = map_reads_to_clusters(engine, rs, numbers, counts, cl["trim"], seedLength, out_stem, names,
+                                                keep_device=bool(features))
+        if features:
+            cl["features"] = cluster_features(engine, rs, counts, dict(cl["trim"], clusters=retained_clusters(cl, cl["trim"])),
+                                              cl["remap"], parts, out_stem)
+            cl["remap"].pop("device", None)
+            cl["remap"].pop("index", None)
     return cl
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None, trim=None, remap=False):
+                    timings=None, trim=None, remap=False, features=False):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
@@ -443,7 +661,8 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     trim = (repeats, clusterSeqLenCutoff) adds :557-562 (trim_clusters: the three `_clusters_trimmed` files; the return value
     gains "trim"); repeats = load_repeats' dict over this genome, or the path of the file (None: no table).
     remap=True (needs trim) adds :566-601 (map_reads_to_clusters: `<out_stem>_vs_representative_seq_modified_selected_sorted.tsv`;
-    the return value gains "remap")."""
+    the return value gains "remap").  features=True (needs remap) adds :604 (cluster_features: the table's `_features.tsv` and
+    `_cluster.txt`; the return value gains "features")."""
     from .engine import ReadSet
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
@@ -456,15 +675,15 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap)
+                              out_stem, sam, timings, trim, remap, features=features)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None, trim=None, remap=False):
+                          sam=True, timings=None, trim=None, remap=False, features=False):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
-    names; no FASTA is parsed and no Python string is made per read.  trim / remap: as map_and_cluster's."""
+    names; no FASTA is parsed and no Python string is made per read.  trim / remap / features: as map_and_cluster's."""
     import torch
     from .engine import ReadSet
     _check_policy(mapping_loc, seedLength, overlapLenCutoff)
@@ -494,7 +713,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
             seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, numbers)
+                              out_stem, sam, timings, trim, remap, numbers, features=features)
 
 
 def sample_stem(sample):
@@ -602,15 +821,19 @@ def clusters_main(argv):
     ap.add_argument("--repeats", metavar="FILE", help="the repeat elements (chr, start, end, name; tab-separated) for --trim")
     ap.add_argument("-clc", dest="cluster_len_cutoff", type=int, default=30)
     ap.add_argument("--remap", action="store_true", help="with --trim: also map the reads to the retained clusters (the sorted table)")
+    ap.add_argument("--features", action="store_true", help="with --remap: also build the cluster feature table (_features.tsv, _cluster.txt)")
     a = ap.parse_args(argv)
     if a.remap and not a.trim:
         ap.error("--remap needs --trim")
+    if a.features and not a.remap:
+        ap.error("--features needs --remap")
     from .engine import Engine
     try:
         eng = Engine(int(os.environ.get("MIRGE_AMD_GPU", "0")))
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
-                                 sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap)
+                                 sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap,
+                                 features=a.features)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -622,6 +845,9 @@ def clusters_main(argv):
     if a.remap:
         sys.stderr.write("# remapped: %d reads in pass 1, %d in pass 2, %d unaligned, %d rows\n" % tuple(
             cl["remap"][k] for k in ("aligned1", "aligned2", "unaligned", "n_rows")))
+    if a.features:
+        sys.stderr.write("# features: %d groups, %d pass the filter, %d written (%d feature lines), %d worked out on the host\n" % tuple(
+            cl["features"][k] for k in ("seen", "passed", "written", "lines", "host_groups")))
     return 0
 
 
@@ -629,7 +855,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
-                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap]]\n")
+                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features]]]\n")
         return 1
     return clusters_main(argv[1:])
 
