@@ -1092,6 +1092,51 @@ int mrg_write_predict_features(const char *features_path, const char *cluster_pa
                                const uint32_t *nb_t, const int64_t *nb_up, const int64_t *nb_down, const uint8_t *nb_flags,
                                const char *const *group_text, uint64_t n_order, const uint32_t *order, uint64_t *written);
 
+/* Predict mode's precursor candidates (reference miRge2.0.py:608: utils/get_precursors.py) from the groups of the feature
+ * table and the resident genome libraries (csrc/predict_precursors.hip; the rule: tests/predict_precursors_model.py).  For
+ * every group of d_order whose line `_features.tsv` holds -- (H + L + T) + max(0, 3 - head) + max(0, 6 - tailAdd) - head -
+ * tailAdd >= 7, L = end - start + 1, tailAdd = -tail - 1 -- the stable part is s = start - H + head, e = end + T - tailAdd
+ * on `+` and s = start - T + tailAdd, e = end + H - head on `-`; record 2 w is the bases [max(0, s - 71), e + 20) of the
+ * cluster's entry (0-based, clipped at the entry's length), record 2 w + 1 is [max(0, s - 21), e + 70); on `-` the
+ * reverse complement; as RNA (A C G U, N where the index holds no base).
+ *
+ *   mrg_predict_precursor_temp_bytes  HOST: the bytes of device scratch the two calls below need for n_order positions.
+ *   mrg_predict_precursors  DEVICE, synchronises.  d_order [n_order]: the groups in file order (mrg_predict_feature_neighbors'
+ *       first n_sorted), d_group_cluster / d_frame / d_valid [n_groups] as the feature calls left them; the retained clusters
+ *       [n_clusters]; d_entry_len [n_entries].  d_written [n_order] = 1 for a group with a line; d_rec_group / d_rec_lo /
+ *       d_rec_hi [2 n_order] and d_rec_off [2 n_order + 1], of which 2 *n_written (+ 1) are set: the record's group, its
+ *       window [lo, hi) and the offset of its bytes; *seq_len = d_rec_off[2 *n_written].  MRG_ERR_ARG when d_order names
+ *       no group or one with d_valid 0, a group names a cluster >= n_clusters, a cluster an entry >= n_entries, or a window
+ *       ends at or before base 0 (the outputs are then undefined).  Limits: groups < 2^30, bytes < 2^38.
+ *   mrg_predict_precursor_bases  DEVICE, synchronises.  d_seq [seq_len]: the bytes of the n_rec records.  libs [n_parts]: the
+ *       genome's parts as libraries of ctx (mrg_ctx_add_library), entry_base [n_parts]: the global number of every part's
+ *       first entry (host arrays; at most 32 parts; together they hold n_entries entries).  The records are checked first:
+ *       offsets that do not ascend from 0 to seq_len by hi - lo, lo > hi, hi beyond the entry, a group, cluster or entry out
+ *       of range are MRG_ERR_ARG and nothing is written.  A library's per-entry segment table is built at its first use.
+ *   mrg_write_precursors  HOST: `<table>_features_precusor.fa` from host copies: `>` + the cluster library's name of the
+ *       record's cluster + `:precusor_1` (even records) or `:precusor_2` (odd), the record's bytes.  Arrays that contradict
+ *       each other (an odd record count, a pair of two groups, a group listed twice, offsets that do not close at seq_len or
+ *       do not match hi - lo, a window beyond its entry) are MRG_ERR_ARG before the file is opened.  written[0] = records,
+ *       written[1] = bytes.  Worker threads: MIRGE_AMD_TABLE_THREADS.
+ */
+int mrg_predict_precursor_temp_bytes(uint64_t n_order, uint64_t *bytes);
+int mrg_predict_precursors(mrg_ctx *ctx, uint64_t n_order, const uint32_t *d_order, uint64_t n_groups,
+                           const uint32_t *d_group_cluster, const int32_t *d_frame, const uint8_t *d_valid, uint64_t n_clusters,
+                           const uint32_t *d_cl_entry, const uint8_t *d_cl_strand, const uint32_t *d_cl_start,
+                           const uint32_t *d_cl_end, uint64_t n_entries, const uint32_t *d_entry_len, uint8_t *d_written,
+                           uint32_t *d_rec_group, uint32_t *d_rec_lo, uint32_t *d_rec_hi, uint64_t *d_rec_off,
+                           uint64_t *n_written, uint64_t *seq_len, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_precursor_bases(mrg_ctx *ctx, uint64_t n_rec, const uint32_t *d_rec_group, const uint32_t *d_rec_lo,
+                                const uint32_t *d_rec_hi, const uint64_t *d_rec_off, uint64_t n_groups,
+                                const uint32_t *d_group_cluster, uint64_t n_clusters, const uint32_t *d_cl_entry,
+                                const uint8_t *d_cl_strand, uint64_t n_entries, const uint32_t *d_entry_len, uint32_t n_parts,
+                                const int32_t *libs, const uint32_t *entry_base, char *d_seq, uint64_t seq_len, void *d_tmp,
+                                uint64_t tmp_bytes, void *stream);
+int mrg_write_precursors(const char *path, const mrg_index *const *parts, uint32_t n_parts, const mrg_index *clusters,
+                         uint64_t n_clusters, const uint32_t *cl_entry, uint64_t n_groups, const uint32_t *group_cluster,
+                         uint64_t n_rec, const uint32_t *rec_group, const uint32_t *rec_lo, const uint32_t *rec_hi,
+                         const uint64_t *rec_off, const char *seq, uint64_t seq_len, uint64_t *written);
+
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are

@@ -28,7 +28,9 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     `--novel-map` (with `-sl`; implies `--novel-trim`) maps each sample's reads back to its retained clusters on the GPU
     and adds `..._vs_representative_seq_modified_selected_sorted.tsv`, the table the feature stage reads;
     `--novel-features` (implies `--novel-map`) builds that stage's two files on the GPU from the same arrays:
-    `..._sorted_features.tsv` and `..._sorted_cluster.txt`, as the reference's generate_featureFiles writes them.
+    `..._sorted_features.tsv` and `..._sorted_cluster.txt`, as the reference's generate_featureFiles writes them;
+    `--novel-precursors` (implies `--novel-features`) cuts the two precursor windows of every line of that table out of the
+    resident genome on the GPU: `..._sorted_features_precusor.fa`, the file the reference feeds to RNAfold.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -45,7 +47,8 @@ ANNOT_NAMES = ["exact miRNA", "hairpin miRNA", "mature tRNA", "primary tRNA", "s
 def novel_stages(args):
     """(reads, clusters, trim, map): which of predict mode's stages the `--novel-*` options ask for; each implies the ones
     before it."""
-    novel_map = bool(getattr(args, "novel_map", False)) or bool(getattr(args, "novel_features", False))
+    novel_map = bool(getattr(args, "novel_map", False)) or bool(getattr(args, "novel_features", False)) or \
+        bool(getattr(args, "novel_precursors", False))
     novel_trim = novel_map or bool(getattr(args, "novel_trim", False))
     novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
     novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
@@ -98,6 +101,9 @@ def build_parser():
     p.add_argument("--novel-features", dest="novel_features", action="store_true",
                    help="extension: --novel-map, then the cluster feature table of the sorted table on the GPU "
                         "(<table>_features.tsv and <table>_cluster.txt, as the reference's generate_featureFiles writes them)")
+    p.add_argument("--novel-precursors", dest="novel_precursors", action="store_true",
+                   help="extension: --novel-features, then the precursor candidates of every feature line cut out of the genome "
+                        "on the GPU (<table>_features_precusor.fa, as the reference's get_precursors writes it)")
     p.add_argument("-minl", default="16", dest="minLength", metavar="<int>")
     p.add_argument("-maxl", default="25", dest="maxLength", metavar="<int>")
     p.add_argument("-cc", default="2", dest="countCutoff", metavar="<int>")
@@ -558,6 +564,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
             if novel_trim:   # MAIN:557-562; a missing file is the reference's "no repeat table"
                 trim = (predict.load_repeats(predict.repeats_path(lib, sp), predict.genome_libraries(engine, novel_genome)[1]),
                         cluster_len_cutoff)
+            novel_precursors = bool(getattr(args, "novel_precursors", False))
+            novel_features = novel_precursors or bool(getattr(args, "novel_features", False))
             for s, stem in enumerate(stems):
                 if stem in stems[s + 1:]:   # (a later sample wrote this stem's files)
                     continue
@@ -569,7 +577,7 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
                 predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
                                               seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
-                                              remap=novel_map, features=bool(getattr(args, "novel_features", False)))
+                                              remap=novel_map, features=novel_features, precursors=novel_precursors)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

@@ -30,6 +30,7 @@
 #include "kernels.hpp"
 #include "predict_cluster.hpp"
 #include "predict_features.hpp"
+#include "predict_precursors.hpp"
 #include "predict_reads.hpp"
 #include "prims.hpp"
 #include "sa_build.hpp"
@@ -135,6 +136,7 @@ struct DevLib {
   uint32_t n = 0, nblk = 0, nsup = 0, primary = 0, text_words = 0, n_seg = 0, n_ref = 0;
   uint32_t max_ref_len = 0;
   bool simple = false;  // every entry is exactly one N-free segment: segment id == entry id, offset 0
+  uint32_t* first_seg = nullptr;  // [n_ref + 1] the segments of entry e are [first_seg[e], first_seg[e + 1]) (mrg_predict_precursor_bases, on first use)
 };
 
 template <class T>
@@ -556,7 +558,7 @@ void mrg_ctx_destroy(mrg_ctx* ctx) {
 namespace {
 void free_dev_lib(DevLib& l) {
   void* ptrs[] = {l.blocks, l.super, l.text, l.sa, l.ftab, l.ctx, l.sa16, l.buckets, l.pos_rows, l.kbits, l.pair_jump, l.pair_jump_s, l.pair_rows, l.dict_slots,
-                  l.bpair_jump, l.bpair_rows, l.seg_start, l.seg_ref, l.seg_off, l.chunk_seg};
+                  l.bpair_jump, l.bpair_rows, l.seg_start, l.seg_ref, l.seg_off, l.chunk_seg, l.first_seg};
   for (void* p : ptrs) (void)hipFree(p);
 }
 
@@ -3584,6 +3586,183 @@ int mrg_write_predict_features(const char* features_path, const char* cluster_pa
     a.n_order = n_order;
     a.order = order;
     mrg::write_predict_features(a, written);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+// ------------------------------------------------- predict mode: the precursor candidates (csrc/predict_precursors.hip)
+namespace {
+constexpr uint64_t kPrecMaxGroups = (1ull << 30) - 1, kPrecMaxBytes = (1ull << 38) - 1;
+// mrg_predict_precursors' scratch: the stat words, two uint32 arrays of S + 1, the windows [4 S], the lengths [2 S + 1] and
+// the scan's own; mrg_predict_precursor_bases reads the stat words alone
+struct PrecScratch {
+  size_t flag32, rank, win, len32, scan, total;
+  explicit PrecScratch(uint64_t S) {
+    const size_t k4 = up8((size_t)(S + 1) * sizeof(uint32_t));
+    flag32 = up8(mrg::kPrecStatWords * sizeof(uint32_t));
+    rank = flag32 + k4;
+    win = rank + k4;
+    len32 = win + up8((size_t)(4 * S) * sizeof(uint32_t));
+    scan = len32 + up8((size_t)(2 * S + 1) * sizeof(uint32_t));
+    total = scan + up8(mrg::prims::scan_temp_bytes(2 * S + 1));
+  }
+};
+int prec_stat_error(const char* fn, const uint32_t* h_stat) {
+  if (h_stat[mrg::kPrecStatBadGroup]) return fail(MRG_ERR_ARG, "%s: the order or a record names no group, or a group without a stable column", fn);
+  if (h_stat[mrg::kPrecStatBadCluster]) return fail(MRG_ERR_ARG, "%s: a group of no retained cluster", fn);
+  if (h_stat[mrg::kPrecStatBadEntry]) return fail(MRG_ERR_ARG, "%s: a cluster on no entry", fn);
+  if (h_stat[mrg::kPrecStatBadWindow]) return fail(MRG_ERR_ARG, "%s: a window that ends at or before its chromosome's first base", fn);
+  if (h_stat[mrg::kPrecStatBadRecord])
+    return fail(MRG_ERR_ARG, "%s: record offsets that do not ascend from 0 to seq_len by hi - lo, or a record outside its entry", fn);
+  return MRG_OK;
+}
+// first_seg of a resident library, built the first time a precursor call names it: the segment table is ordered by
+// (entry, offset), so entry e's segments are the run of seg_ref == e
+int ensure_first_seg(const char* fn, DevLib& l) {
+  if (l.first_seg) return MRG_OK;
+  std::vector<uint32_t> ref(l.n_seg), off(l.n_seg), first((size_t)l.n_ref + 1, 0u);
+  if (l.n_seg) {
+    HIP_TRY(hipMemcpy(ref.data(), l.seg_ref, (size_t)l.n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off.data(), l.seg_off, (size_t)l.n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  for (uint32_t s = 0; s < l.n_seg; ++s) {
+    if (ref[s] >= l.n_ref || (s && (ref[s] < ref[s - 1] || (ref[s] == ref[s - 1] && off[s] <= off[s - 1]))))
+      return fail(MRG_ERR_ARG, "%s: the library's segments are not ordered by (entry, offset)", fn);
+    ++first[ref[s] + 1];
+  }
+  for (uint32_t e = 0; e < l.n_ref; ++e) first[e + 1] += first[e];
+  return upload(&l.first_seg, first);
+}
+}  // namespace
+
+int mrg_predict_precursor_temp_bytes(uint64_t n_order, uint64_t* bytes) {
+  const char* fn = "mrg_predict_precursor_temp_bytes";
+  if (!bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_order > kPrecMaxGroups) return fail(MRG_ERR_ARG, "%s: %llu groups; the limit is 2^30 - 1", fn, (unsigned long long)n_order);
+  *bytes = PrecScratch(n_order).total;
+  return MRG_OK;
+}
+
+int mrg_predict_precursors(mrg_ctx* ctx, uint64_t n_order, const uint32_t* d_order, uint64_t n_groups, const uint32_t* d_group_cluster,
+                           const int32_t* d_frame, const uint8_t* d_valid, uint64_t n_clusters, const uint32_t* d_cl_entry,
+                           const uint8_t* d_cl_strand, const uint32_t* d_cl_start, const uint32_t* d_cl_end, uint64_t n_entries,
+                           const uint32_t* d_entry_len, uint8_t* d_written, uint32_t* d_rec_group, uint32_t* d_rec_lo, uint32_t* d_rec_hi,
+                           uint64_t* d_rec_off, uint64_t* n_written, uint64_t* seq_len, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_precursors";
+  if (!ctx || !n_written || !seq_len) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *n_written = *seq_len = 0;
+  if (n_order > kPrecMaxGroups || n_groups > kPrecMaxGroups || n_order > n_groups)
+    return fail(MRG_ERR_ARG, "%s: %llu positions of %llu groups (the limit is 2^30 - 1)", fn, (unsigned long long)n_order, (unsigned long long)n_groups);
+  if (n_clusters > kFeatMaxItems || n_entries > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: clusters and entries are limited to 2^31 - 1 each", fn);
+  if (!d_tmp || !d_rec_off) return fail(MRG_ERR_ARG, "%s: null buffers", fn);
+  if (n_order && (!d_order || !d_group_cluster || !d_frame || !d_valid || !d_cl_entry || !d_cl_strand || !d_cl_start || !d_cl_end || !d_entry_len ||
+                  !d_written || !d_rec_group || !d_rec_lo || !d_rec_hi))
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  const PrecScratch sc(n_order);
+  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_precursor_temp_bytes, or unaligned", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_order == 0) {
+    HIP_TRY(hipMemsetAsync(d_rec_off, 0, sizeof(uint64_t), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MRG_OK;
+  }
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
+  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  uint32_t* win = reinterpret_cast<uint32_t*>(base + sc.win);
+  uint32_t* len32 = reinterpret_cast<uint32_t*>(base + sc.len32);
+  const mrg::PrecGroups g{(uint32_t)n_order, d_order, (uint32_t)n_groups, d_group_cluster, d_frame, d_valid};
+  const mrg::PrecClusters cl{(uint32_t)n_clusters, d_cl_entry, d_cl_strand, d_cl_start, d_cl_end, (uint32_t)n_entries, d_entry_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPrecStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::prec_windows_launch(g, cl, d_written, flag32, win, stat, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_order + 1, base + sc.scan, st));
+  uint32_t h_stat[mrg::kPrecStatWords] = {0}, W = 0;
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&W, rank + n_order, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = prec_stat_error(fn, h_stat)) return rc;
+  if (W > n_order) return fail(MRG_ERR_HIP, "%s: %u groups written of %llu", fn, W, (unsigned long long)n_order);
+  HIP_TRY(mrg::prec_compact_launch(g, rank, win, d_rec_group, d_rec_lo, d_rec_hi, len32, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_rec_off, 2ull * W + 1, base + sc.scan, st));
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_rec_off + 2ull * W, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (total > kPrecMaxBytes) return fail(MRG_ERR_ARG, "%s: %llu sequence bytes; the limit is 2^38 - 1", fn, (unsigned long long)total);
+  *n_written = W;
+  *seq_len = total;
+  return MRG_OK;
+}
+
+int mrg_predict_precursor_bases(mrg_ctx* ctx, uint64_t n_rec, const uint32_t* d_rec_group, const uint32_t* d_rec_lo, const uint32_t* d_rec_hi,
+                                const uint64_t* d_rec_off, uint64_t n_groups, const uint32_t* d_group_cluster, uint64_t n_clusters,
+                                const uint32_t* d_cl_entry, const uint8_t* d_cl_strand, uint64_t n_entries, const uint32_t* d_entry_len,
+                                uint32_t n_parts, const int32_t* libs, const uint32_t* entry_base, char* d_seq, uint64_t seq_len, void* d_tmp,
+                                uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_precursor_bases";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_rec > 2 * kPrecMaxGroups || n_groups > kPrecMaxGroups) return fail(MRG_ERR_ARG, "%s: records and groups are limited to 2^31 - 2 and 2^30 - 1", fn);
+  if (n_clusters > kFeatMaxItems || n_entries > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: clusters and entries are limited to 2^31 - 1 each", fn);
+  if (seq_len > kPrecMaxBytes) return fail(MRG_ERR_ARG, "%s: %llu sequence bytes; the limit is 2^38 - 1", fn, (unsigned long long)seq_len);
+  if (!d_tmp || !d_rec_off || tmp_bytes < up8(mrg::kPrecStatWords * sizeof(uint32_t)) || ((uintptr_t)d_tmp & 7))
+    return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_precursor_temp_bytes, unaligned, or null offsets", fn);
+  if (n_rec && (!d_rec_group || !d_rec_lo || !d_rec_hi || !d_group_cluster || !d_cl_entry || !d_cl_strand || !d_entry_len)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  if (seq_len && (!n_rec || !d_seq)) return fail(MRG_ERR_ARG, "%s: sequence bytes without records or buffer", fn);
+  if (n_parts > mrg::kPrecMaxParts || (n_parts && (!libs || !entry_base)))
+    return fail(MRG_ERR_ARG, "%s: %u genome parts (the limit is %u), or null part tables", fn, n_parts, mrg::kPrecMaxParts);
+  HIP_TRY(hipSetDevice(ctx->device));
+  mrg::PrecGenome genome;
+  std::memset(&genome, 0, sizeof genome);
+  genome.n_parts = n_parts;
+  uint64_t next = 0;
+  for (uint32_t k = 0; k < n_parts; ++k) {
+    if (libs[k] < 0 || (size_t)libs[k] >= ctx->libs.size()) return fail(MRG_ERR_ARG, "%s: unknown library %d", fn, libs[k]);
+    DevLib& l = ctx->libs[libs[k]];
+    if (entry_base[k] != next) return fail(MRG_ERR_ARG, "%s: part %u starts at entry %u, the parts before it hold %llu", fn, k, entry_base[k], (unsigned long long)next);
+    next += l.n_ref;
+    if (int rc = ensure_first_seg(fn, l)) return rc;
+    genome.part[k] = mrg::PrecPart{l.text, l.seg_start, l.seg_off, l.first_seg, entry_base[k], l.n_ref};
+  }
+  if (n_rec && next != n_entries) return fail(MRG_ERR_ARG, "%s: the parts hold %llu entries, not the %llu given", fn, (unsigned long long)next, (unsigned long long)n_entries);
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = reinterpret_cast<uint32_t*>(d_tmp);
+  const mrg::PrecRecords r{(uint32_t)n_rec, d_rec_group, d_rec_lo, d_rec_hi, d_rec_off};
+  const mrg::PrecGroups g{0u, nullptr, (uint32_t)n_groups, d_group_cluster, nullptr, nullptr};
+  const mrg::PrecClusters cl{(uint32_t)n_clusters, d_cl_entry, d_cl_strand, nullptr, nullptr, (uint32_t)n_entries, d_entry_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPrecStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::prec_check_launch(r, g, cl, seq_len, stat, st));
+  uint32_t h_stat[mrg::kPrecStatWords] = {0};
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = prec_stat_error(fn, h_stat)) return rc;  // (before a byte is written: the bases kernel trusts the records)
+  HIP_TRY(mrg::prec_bases_launch(r, g, cl, genome, seq_len, d_seq, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+int mrg_write_precursors(const char* path, const mrg_index* const* parts, uint32_t n_parts, const mrg_index* clusters, uint64_t n_clusters,
+                         const uint32_t* cl_entry, uint64_t n_groups, const uint32_t* group_cluster, uint64_t n_rec, const uint32_t* rec_group,
+                         const uint32_t* rec_lo, const uint32_t* rec_hi, const uint64_t* rec_off, const char* seq, uint64_t seq_len,
+                         uint64_t* written) {
+  const char* fn = "mrg_write_precursors";
+  if (!path || !written || !rec_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  written[0] = written[1] = 0;
+  if (n_clusters && (!clusters || !cl_entry)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
+  if (n_groups && !group_cluster) return fail(MRG_ERR_ARG, "%s: null group arrays", fn);
+  if (n_rec && (!rec_group || !rec_lo || !rec_hi)) return fail(MRG_ERR_ARG, "%s: null record arrays", fn);
+  if (seq_len && !seq) return fail(MRG_ERR_ARG, "%s: null sequence bytes", fn);
+  std::vector<const mrg::FmIndex*> ix;
+  int rc = index_list(fn, parts, n_parts, &ix);
+  if (rc != MRG_OK) return rc;
+  try {
+    const mrg::PrecWriteArgs a{path, &ix, clusters ? &clusters->ix : nullptr, n_clusters, cl_entry, n_groups, group_cluster, n_rec, rec_group,
+                               rec_lo, rec_hi, rec_off, seq, seq_len};
+    mrg::write_precursors(a, written);
     return MRG_OK;
   } catch (const std::invalid_argument& e) {
     return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());

@@ -1447,7 +1447,8 @@ class Engine:
             timings.update(list_ms=ev[0].elapsed_time(ev[1]), rows_ms=ev[1].elapsed_time(ev[2]), download_ms=ev[2].elapsed_time(ev[3]))
         return dict(rows=host, n_rows=int(host[0].shape[0]), aligned1=a1, aligned2=a2, unaligned=n - a1 - a2, device=rows)
 
-    def predict_features(self, reads, counts, rows, clusters, entry_len, entry_rank, host_groups=None, timings=None):
+    def predict_features(self, reads, counts, rows, clusters, entry_len, entry_rank, host_groups=None, timings=None,
+                         keep_device=False):
         """Predict mode's cluster feature table from the rows of predict_remap (mrg_predict_feature_groups / _align /
         _tally / _neighbors; the rule of the reference's generate_featureFiles.py and readCluster.py).  reads: the ReadSet
         the rows index; counts [n]: the reads' counts; rows = (read, cluster) device tensors or host arrays in file order;
@@ -1462,7 +1463,9 @@ class Engine:
         group_sum, group_pass, group_host, valid, frame [G, 4] (H, T, head, tail), exact, nine [G, 45], nb_t, nb_up, nb_down,
         nb_flags [G]; order [n_sorted] = the groups with a stable column in file order; n_groups, n_passed, n_sorted,
         host_results {g: what host_groups returned}.  timings gets device_ms (events around the four calls, the host groups'
-        time included when there are any) and download_ms."""
+        time included when there are any) and download_ms.
+        keep_device=True adds "device" for predict_precursors: the device tensors order, group_cluster, frame, valid, cl_len,
+        the clusters' entry, strand, start, end, entry_len, and the ints n_sorted, n_groups, n_clusters."""
         torch = _torch()
         dev = self.device
         n = reads.n
@@ -1560,9 +1563,83 @@ class Engine:
                    nb_t=u32(nb_t, G), nb_up=nb_up.cpu().numpy()[:G], nb_down=nb_down.cpu().numpy()[:G], nb_flags=nb_flags.cpu().numpy()[:G],
                    order=u32(order, G)[:S], n_groups=G, n_passed=int(P.value), n_sorted=S, host_results=host_results)
         mark()
+        if keep_device:
+            out["device"] = dict(order=order, group_cluster=group_cluster, frame=frame, valid=valid, cl_len=cl_len, entry=cl["entry"],
+                                 strand=strand, start=cl["start"], end=cl["end"], entry_len=entry_len, n_sorted=S, n_groups=G,
+                                 n_clusters=K)
         if timings is not None:
             ev[-1].synchronize()
             timings.update(device_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+        return out
+
+    def predict_precursors(self, features_device, clusters=None, entry_len=None, parts_libs=(), timings=None):
+        """Predict mode's precursor candidates (mrg_predict_precursors / mrg_predict_precursor_bases; the rule of the
+        reference's get_precursors.py): for every group whose line the feature file holds, the two genome windows around the
+        stable part of its cluster, as RNA, cut out of the resident genome libraries.  features_device: the "device" dict of
+        predict_features(keep_device=True); clusters: a dict of entry, strand, start, end [K] (host arrays or device
+        tensors; None: the tensors features_device carries); entry_len [entries] (None: likewise); parts_libs: the keys of
+        the genome's parts on this engine, in entry order.
+        Returns a dict of host arrays: written (uint8 [n_sorted]), rec_group, rec_lo, rec_hi (uint32 [2 W]), rec_off (uint64
+        [2 W + 1]), seq (bytes), n_written = W, and device_ms / download_ms (None without timings, which gets them too)."""
+        torch = _torch()
+        dev = self.device
+        d = features_device
+        S, G = int(d["n_sorted"]), int(d["n_groups"])
+        order = self._expect(d["order"], torch.int32, "predict_precursors: order")
+        group_cluster = self._expect(d["group_cluster"], torch.int32, "predict_precursors: group_cluster")
+        frame = self._expect(d["frame"], torch.int32, "predict_precursors: frame")
+        valid = self._expect(d["valid"], torch.uint8, "predict_precursors: valid")
+        if S > G or order.numel() < S or group_cluster.numel() < G or frame.numel() < 4 * G or valid.numel() < G:
+            raise ValueError("predict_precursors: order [n_sorted] and group_cluster, frame [G, 4], valid [G] must hold what the counts say")
+        src = d if clusters is None else clusters
+        cl = {k: self._dev_u32(src[k], "predict_precursors: " + k) for k in ("entry", "start", "end")}
+        strand = src["strand"]
+        if not torch.is_tensor(strand):
+            strand = torch.from_numpy(np.ascontiguousarray(strand, dtype=np.uint8)).to(dev)
+        strand = self._expect(strand, torch.uint8, "predict_precursors: strand").contiguous()
+        K = int(d["n_clusters"]) if clusters is None else int(cl["entry"].shape[0])
+        if any(int(t.numel()) < K for t in (cl["entry"], cl["start"], cl["end"], strand)):
+            raise ValueError("predict_precursors: entry, strand, start and end must hold the K clusters")
+        entry_len = self._dev_u32(d["entry_len"] if entry_len is None else entry_len, "predict_precursors: entry_len")
+        E = int(entry_len.shape[0])
+        lids = np.array([self.libs[k] for k in parts_libs], dtype=np.int32)
+        ebase = np.cumsum([0] + [self.indexes[k].n_ref for k in parts_libs]).astype(np.uint32)
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_precursor_temp_bytes(S, C.byref(need)))
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
+        tmp = e(max(int(need.value), 64), torch.uint8)
+        written, rec_group, rec_lo, rec_hi = e(S, torch.uint8), e(2 * S, torch.int32), e(2 * S, torch.int32), e(2 * S, torch.int32)
+        rec_off = e(2 * S + 1, torch.int64)
+        ev = []
+
+        def mark():
+            if timings is not None:
+                x = torch.cuda.Event(enable_timing=True)
+                x.record(torch.cuda.current_stream(dev))
+                ev.append(x)
+        ptr = lambda t: t.data_ptr()
+        W, total = C.c_uint64(0), C.c_uint64(0)
+        mark()
+        check(self._lib.mrg_predict_precursors(
+            self._h, S, ptr(order), G, ptr(group_cluster), ptr(frame), ptr(valid), K, ptr(cl["entry"]), ptr(strand), ptr(cl["start"]),
+            ptr(cl["end"]), E, ptr(entry_len), ptr(written), ptr(rec_group), ptr(rec_lo), ptr(rec_hi), ptr(rec_off), C.byref(W),
+            C.byref(total), ptr(tmp), tmp.numel(), self._stream_ptr()))
+        W, total = int(W.value), int(total.value)
+        seq = e(total, torch.uint8)
+        check(self._lib.mrg_predict_precursor_bases(
+            self._h, 2 * W, ptr(rec_group), ptr(rec_lo), ptr(rec_hi), ptr(rec_off), G, ptr(group_cluster), K, ptr(cl["entry"]), ptr(strand),
+            E, ptr(entry_len), len(lids), lids.ctypes.data if len(lids) else None, ebase.ctypes.data, ptr(seq), total, ptr(tmp),
+            tmp.numel(), self._stream_ptr()))
+        mark()
+        u32 = lambda t, k: t.cpu().numpy()[:k].view(np.uint32)
+        out = dict(written=written.cpu().numpy()[:S], rec_group=u32(rec_group, 2 * W), rec_lo=u32(rec_lo, 2 * W), rec_hi=u32(rec_hi, 2 * W),
+                   rec_off=rec_off.cpu().numpy()[:2 * W + 1].view(np.uint64), seq=seq.cpu().numpy()[:total].tobytes(), n_written=W,
+                   device_ms=None, download_ms=None)
+        mark()
+        if timings is not None:
+            ev[-1].synchronize()
+            out.update(device_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+            timings.update(device_ms=out["device_ms"], download_ms=out["download_ms"])
         return out
 
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):

@@ -506,14 +506,15 @@ def entry_tables(parts):
     return np.array(lens, dtype=np.uint32), rank
 
 
-def cluster_features(engine, rs, counts, trim_result, remap_result, parts, out_stem, threads=None, timings=None):
+def cluster_features(engine, rs, counts, trim_result, remap_result, parts, out_stem, threads=None, timings=None, keep_device=False):
     """The reference's miRge2.0.py:604 (generate_featureFiles) from the arrays: the rows map_reads_to_clusters left
     (remap_result: its return value with keep_device=True; rs / counts: the reads it mapped) against the clusters the trim
     retained (trim_result: trim_clusters' return value plus "clusters" = retained_clusters(...)) on the genome `parts`.
     Writes `<out_stem>_vs_representative_seq_modified_selected_sorted_features.tsv` and `..._cluster.txt`; returns the dict
     of Engine.predict_features plus seen / passed / written (groups), lines (of `_features.tsv`), host_groups and
     row_status_counts [8].  With no retained cluster or no row the partial header and an empty `_cluster.txt` are written.
-    timings gets device_ms, download_ms, host_s and write_s."""
+    timings gets device_ms, download_ms, host_s and write_s.  keep_device=True adds "device" (Engine.predict_features') and
+    "index" (the cluster library) for cluster_precursors; neither is there when nothing was built."""
     import time
     import torch
     table_path = out_stem + REMAP_SUFFIX
@@ -551,8 +552,11 @@ def cluster_features(engine, rs, counts, trim_result, remap_result, parts, out_s
         host_s[0] += time.perf_counter() - t0
         return numbers
     cl = dict(clusters, kept=trim_result["kept"], kept_seq_off=soff, kept_orig=orig)
-    res = engine.predict_features(rs, counts, remap_result["device"][:2], cl, entry_len, entry_rank, host_groups, timings)
+    res = engine.predict_features(rs, counts, remap_result["device"][:2], cl, entry_len, entry_rank, host_groups, timings,
+                                  **({"keep_device": True} if keep_device else {}))
     res["row_read"] = row_read
+    if keep_device:
+        res["index"] = index
     t0 = time.perf_counter()
     blocks, lines = write_predict_features(table_path, parts, index, clusters, soff, orig, words, lens, nmask, counts, res, texts, threads)
     if timings is not None:
@@ -560,6 +564,90 @@ def cluster_features(engine, rs, counts, trim_result, remap_result, parts, out_s
     res.update(seen=res["n_groups"], passed=res["n_passed"], written=blocks, lines=lines, host_groups=len(texts),
                row_status_counts=np.bincount(res["row_status"], minlength=8))
     return res
+
+
+PRECURSOR_SUFFIX = "_features_precusor.fa"
+
+
+def write_precursors(path, parts, index, cl_entry, group_cluster, rec, threads=None):
+    """mrg_write_precursors: the file `path` from host arrays -- the genome's parts, the cluster library (entry j's name is
+    retained cluster j's), every retained cluster's entry, every group's cluster and rec = a dict of rec_group, rec_lo,
+    rec_hi [2 W], rec_off [2 W + 1] and seq (bytes) as Engine.predict_precursors returns them.  Returns (records, bytes)."""
+    from . import _native
+    lib = _native.load()
+    cl_entry = np.ascontiguousarray(cl_entry, dtype=np.uint32)
+    group_cluster = np.ascontiguousarray(group_cluster, dtype=np.uint32)
+    rg, lo, hi = (np.ascontiguousarray(rec[k], dtype=np.uint32) for k in ("rec_group", "rec_lo", "rec_hi"))
+    off = np.ascontiguousarray(rec["rec_off"], dtype=np.uint64)
+    seq = np.frombuffer(bytes(rec["seq"]), dtype=np.uint8)
+    n_rec = int(rg.shape[0])
+    if lo.shape != (n_rec,) or hi.shape != (n_rec,) or off.shape != (n_rec + 1,):
+        raise ValueError("write_precursors: rec_group, rec_lo, rec_hi [records] and rec_off [records + 1] must match")
+    if int(off[-1]) != seq.shape[0]:
+        raise ValueError("write_precursors: rec_off must close at the %d sequence bytes (it ends at %d)" % (seq.shape[0], int(off[-1])))
+    K = int(cl_entry.shape[0])
+    if (index.n_ref if index is not None else 0) != K:
+        raise ValueError("write_precursors: the cluster library's entries must be the %d retained clusters" % K)
+    hs = (C.c_void_p * max(len(parts), 1))(*[p._h.value for p in parts])
+    written = (C.c_uint64 * 2)()
+    with _writer_threads(threads):
+        _native.check(lib.mrg_write_precursors(
+            os.fsencode(path), hs, len(parts), index._h if index is not None else None, K, _ptr(cl_entry), int(group_cluster.shape[0]),
+            _ptr(group_cluster), n_rec, _ptr(rg), _ptr(lo), _ptr(hi), off.ctypes.data, _ptr(seq), int(seq.shape[0]), written))
+    return int(written[0]), int(written[1])
+
+
+def cluster_precursors(engine, features_result, trim_result, parts, out_stem, threads=None, timings=None, parts_libs=None):
+    """The reference's miRge2.0.py:608 (get_precursors) from the arrays: for every line cluster_features wrote, the two
+    genome windows around the stable part of the cluster, as RNA -- the file RNAfold is fed.  features_result: what
+    cluster_features(..., keep_device=True) returned (its "device" and "index"); trim_result: as cluster_features takes it;
+    parts: the genome's FmIndex list, resident on `engine` (parts_libs: their keys there; None: looked up by object).
+    Writes `<out_stem>_vs_representative_seq_modified_selected_sorted_features_precusor.fa`; returns the dict of
+    Engine.predict_precursors plus records and bytes (of the file).  timings gets device_ms, download_ms and write_s."""
+    import time
+    path = out_stem + REMAP_SUFFIX[:-4] + PRECURSOR_SUFFIX
+    dev = features_result.get("device")
+    if dev is None:   # (no retained cluster or no row: the feature file is its header)
+        with open(path, "w"):
+            pass
+        return dict(written=np.zeros(0, np.uint8), rec_group=np.zeros(0, np.uint32), rec_lo=np.zeros(0, np.uint32),
+                    rec_hi=np.zeros(0, np.uint32), rec_off=np.zeros(1, np.uint64), seq=b"", n_written=0, device_ms=None,
+                    download_ms=None, records=0, bytes=0)
+    if parts_libs is None:
+        by_id = {id(ix): k for k, ix in engine.indexes.items()}
+        try:
+            parts_libs = [by_id[id(ix)] for ix in parts]
+        except KeyError:
+            raise ValueError("cluster_precursors: a genome part is not resident on this engine (genome_libraries adds them)")
+    res = engine.predict_precursors(dev, None, None, parts_libs, timings)
+    if int(res["written"].sum()) != int(features_result["lines"]):
+        raise ValueError("cluster_precursors: %d groups written, the feature file holds %d lines" % (int(res["written"].sum()),
+                                                                                                  int(features_result["lines"])))
+    t0 = time.perf_counter()
+    records, nbytes = write_precursors(path, parts, features_result["index"], trim_result["clusters"]["entry"],
+                                       features_result["group_cluster"], res, threads)
+    if timings is not None:
+        timings["write_s"] = time.perf_counter() - t0
+    res.update(records=records, bytes=nbytes)
+    return res
+
+
+def rename_str_file(fasta, str_tmp, str_out):
+    """The reference's renameStrFile (miRge2.0.py:612) for users who fold `_precusor.fa` with their own RNAfold: RNAfold
+    cuts the names short, so every three-line record of `str_tmp` (name, sequence, structure) gets the name line of the
+    record at the same position of `fasta` back.  Pure host code; writes `str_out`, returns the records written."""
+    with open(fasta) as fh:
+        names = fh.readlines()[0::2]
+    with open(str_tmp) as fh:
+        lines = fh.readlines()
+    n = (len(lines) + 2) // 3
+    if n > len(names):
+        raise ValueError("rename_str_file: %d folded records for %d sequences" % (n, len(names)))
+    with open(str_out, "w") as out:
+        for i in range(n):
+            out.write(names[i])
+            out.writelines(lines[3 * i + 1:3 * i + 3])
+    return n
 
 
 _FEATURES_HEADER_HEAD = ("realMicRNA\trealMicRNAName\tchr\tstartPos\tendPos\tclusterName\tclusterSeq\tmajoritySeq\tstableClusterSeq\t"
@@ -607,7 +695,7 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None, remap=False, numbers=None, features=False):
+                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
     as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`)."""
     from .engine import STRATUM_ALL
@@ -615,6 +703,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
         raise ValueError("remap needs trim: the reads are mapped to the clusters the trim retains")
     if features and not remap:
         raise ValueError("features needs remap: the feature table is built from the rows of the second mapping")
+    if precursors and not features:
+        raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
     keys, parts = genome_libraries(engine, genome_prefix)
     if trim is not None:
         repeats, cutoff = trim
@@ -645,15 +735,20 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
             cl["remap"] = map_reads_to_clusters(engine, rs, numbers, counts, cl["trim"], seedLength, out_stem, names,
                                                 keep_device=bool(features))
         if features:
-            cl["features"] = cluster_features(engine, rs, counts, dict(cl["trim"], clusters=retained_clusters(cl, cl["trim"])),
-                                              cl["remap"], parts, out_stem)
+            trimmed = dict(cl["trim"], clusters=retained_clusters(cl, cl["trim"]))
+            cl["features"] = cluster_features(engine, rs, counts, trimmed, cl["remap"], parts, out_stem,
+                                              **({"keep_device": True} if precursors else {}))
+            if precursors:
+                cl["precursors"] = cluster_precursors(engine, cl["features"], trimmed, parts, out_stem, parts_libs=keys)
+                cl["features"].pop("device", None)
+                cl["features"].pop("index", None)
             cl["remap"].pop("device", None)
             cl["remap"].pop("index", None)
     return cl
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None, trim=None, remap=False, features=False):
+                    timings=None, trim=None, remap=False, features=False, precursors=False):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
@@ -662,8 +757,11 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     gains "trim"); repeats = load_repeats' dict over this genome, or the path of the file (None: no table).
     remap=True (needs trim) adds :566-601 (map_reads_to_clusters: `<out_stem>_vs_representative_seq_modified_selected_sorted.tsv`;
     the return value gains "remap").  features=True (needs remap) adds :604 (cluster_features: the table's `_features.tsv` and
-    `_cluster.txt`; the return value gains "features")."""
+    `_cluster.txt`; the return value gains "features").  precursors=True (needs features) adds :608 (cluster_precursors: the
+    table's `_features_precusor.fa`; the return value gains "precursors")."""
     from .engine import ReadSet
+    if precursors and not features:
+        raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
     if longest > bowtie.MAX_READ_LEN:
@@ -675,17 +773,20 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, features=features)
+                              out_stem, sam, timings, trim, remap, features=features, precursors=precursors)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None, trim=None, remap=False, features=False):
+                          sam=True, timings=None, trim=None, remap=False, features=False, precursors=False):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
-    names; no FASTA is parsed and no Python string is made per read.  trim / remap / features: as map_and_cluster's."""
+    names; no FASTA is parsed and no Python string is made per read.  trim / remap / features / precursors: as
+    map_and_cluster's."""
     import torch
     from .engine import ReadSet
+    if precursors and not features:
+        raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
     _check_policy(mapping_loc, seedLength, overlapLenCutoff)
 
     def host_u32(x):   # (a device tensor holds uint32 in int32 storage)
@@ -713,7 +814,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
             seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, numbers, features=features)
+                              out_stem, sam, timings, trim, remap, numbers, features=features, precursors=precursors)
 
 
 def sample_stem(sample):
@@ -822,7 +923,10 @@ def clusters_main(argv):
     ap.add_argument("-clc", dest="cluster_len_cutoff", type=int, default=30)
     ap.add_argument("--remap", action="store_true", help="with --trim: also map the reads to the retained clusters (the sorted table)")
     ap.add_argument("--features", action="store_true", help="with --remap: also build the cluster feature table (_features.tsv, _cluster.txt)")
+    ap.add_argument("--precursors", action="store_true", help="with --features: also cut the precursor candidates (_features_precusor.fa)")
     a = ap.parse_args(argv)
+    if a.precursors and not a.features:
+        ap.error("--precursors needs --features")
     if a.remap and not a.trim:
         ap.error("--remap needs --trim")
     if a.features and not a.remap:
@@ -833,7 +937,7 @@ def clusters_main(argv):
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
                                  sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap,
-                                 features=a.features)
+                                 features=a.features, precursors=a.precursors)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -848,6 +952,8 @@ def clusters_main(argv):
     if a.features:
         sys.stderr.write("# features: %d groups, %d pass the filter, %d written (%d feature lines), %d worked out on the host\n" % tuple(
             cl["features"][k] for k in ("seen", "passed", "written", "lines", "host_groups")))
+    if a.precursors:
+        sys.stderr.write("# precursors: %d records, %d bytes\n" % (cl["precursors"]["records"], cl["precursors"]["bytes"]))
     return 0
 
 
@@ -855,7 +961,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
-                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features]]]\n")
+                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features [--precursors]]]]\n")
         return 1
     return clusters_main(argv[1:])
 
