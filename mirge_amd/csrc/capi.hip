@@ -269,7 +269,7 @@ struct mrg_ctx {
   int64_t device_tables = 1;  // mrg_ctx_add_library: a large library's derived tables (dictionary, wide rows, seed buckets) are filled on the device
   mrg::CollapseInfo last_collapse;  // mrg_ctx_last_collapse: what the last mrg_collapse_run that succeeded did
   int64_t collapse_fast = 1;  // mrg_collapse_run: batches that fit it take the duplication-aware path (0: always the general sort)
-  int64_t seed_impl = -1;  // -1 = per launch (run_seed), 0 = seed_kernel (tiles), 1 = wave_seed_kernel, 2 = the same with more registers
+  int64_t seed_impl = -1;  // -1 = per launch (launch_seed), 0 = seed_kernel (tiles), 1 = wave_seed_kernel, 2 = the same with more registers
   std::vector<DevLib> libs;
   std::vector<std::unique_ptr<SeedLib>> seed_libs;
   // last run
@@ -1093,6 +1093,896 @@ int get_seed_lib(mrg_ctx* ctx, const std::vector<int32_t>& lib_ids, SeedLib** ou
 }  // extern "C"
 
 namespace {
+
+// ---- shared fills of the kernels' parameter blocks (kernels.hpp): by field name, for every struct that has the fields ----
+
+// the FM arrays of a resident library (what else a struct takes of it -- simple_segs, ctx, sa16, nblk, nsup, text_words -- and
+// whether tabs.k[0] is cleared for "ftab" = 0 is its call site's business)
+template <class P>
+void fill_lib(P& p, const DevLib& l) {
+  p.blocks = l.blocks;
+  p.super = l.super;
+  p.text = l.text;
+  p.sa = l.sa;
+  p.ftab = l.ftab;
+  p.tabs = l.tabs;
+  p.seg_start = l.seg_start;
+  p.seg_ref = l.seg_ref;
+  p.seg_off = l.seg_off;
+  p.chunk_seg = l.chunk_seg;
+  p.n = l.n;
+  p.primary = l.primary;
+}
+
+// a pass's read window: the trims, the length range, the poly-T rule
+template <class P>
+void fill_window(P& p, const mrg_pass_cfg& c) {
+  p.trim5 = c.trim5;
+  p.trim3 = c.trim3;
+  p.min_len = c.min_len;
+  p.max_len = c.max_len;
+  p.poly_t = c.poly_t;
+}
+
+// ... and its seed length and mismatch budget (max_mm_seed and pass_index where the struct has them: at the call site)
+template <class P>
+void fill_policy(P& p, const mrg_pass_cfg& c) {
+  fill_window(p, c);
+  p.seed_len = c.seed_len;
+  p.max_mm_total = c.max_mm_total;
+}
+
+// ---- routing decisions of the cascade: each is made here and nowhere else ----
+
+// Pass c can take the exact-match dictionary of its library for the stratum of `mm_seed` seed mismatches it starts with
+// (the dictionary's key is matched letter for letter: only a pass whose seed covers it may take it)
+bool pass_takes_dict(const mrg_pass_cfg& c, const DevLib& l, int32_t mm_seed = 0) {
+  return c.max_mm_seed == mm_seed && l.dict_slots != nullptr && c.seed_len >= (int32_t)l.dict_key;
+}
+
+// A 2-mismatch pass goes through the anchor pairs of its library: for every read long enough to hold the four anchors,
+// all strata of the pigeonhole search for the shorter ones, in one launch
+bool pass_takes_pairs(const mrg_ctx& ctx, const mrg_pass_cfg& c, const DevLib& l) {
+  return c.max_mm_seed == 2 && ctx.pair_seeds && l.pair_anchor && ctx.force_lds_mode < 0 && !c.poly_t &&
+         c.seed_len >= (int32_t)(4u * l.pair_anchor);
+}
+
+// ... and it does so in pair_wave_kernel (dict.hip: one-word reads without N), not in stratum_kernel
+bool pairs_by_wave(const mrg_ctx& ctx, bool dict_batch) { return dict_batch && ctx.pair_impl != 0; }
+
+// One large library under a one-mismatch policy and (by the length hints) reads whose seed region is 3 A .. 4 A - 1 bases:
+// three anchor pairs instead of two pieces of less than 2 A bases.  The anchor length A of the tables the pass wants
+// (pairs.hip; built on the device at first use: ensure_bpair), or 0.
+int64_t three_anchor_tables(const mrg_ctx& ctx, const mrg_pass_cfg& c, const DevLib& l) {
+  const int64_t A = ctx.pair_big;
+  if (!A || c.max_mm_seed != 1 || c.poly_t || l.n < mrg::kWideRowMinBases) return 0;
+  const int64_t r_min = std::min<int64_t>(std::max<int64_t>(ctx.hint_min_len, c.min_len) - c.trim5 - c.trim3, c.seed_len);
+  const int64_t r_max = std::min<int64_t>(std::min<int64_t>(ctx.hint_max_len, c.max_len) - c.trim5 - c.trim3, c.seed_len);
+  return (r_min < 4 * A && r_max >= 3 * A) ? A : 0;
+}
+
+// A pass whose length window excludes every read of the batch (caller's hint: e.g. the hairpin
+// pass, len > 25, on 22-nt reads) would only copy its input list: it is not launched; its
+// counters stay zero and the next pass reads the same list.  (Never the last pass: that one
+// writes the "unannotated" values.)
+bool pass_skipped(const mrg_ctx& ctx, const mrg_pass_cfg& c, bool last_pass) {
+  return !last_pass && (c.min_len > ctx.hint_max_len || c.max_len < ctx.hint_min_len);
+}
+
+// a library whose 9-mer bitmap filters the seed pieces of the FM kernels
+bool small_lib(const mrg_ctx& ctx, const DevLib& l) { return l.kbits != nullptr && ctx.kmer_filter; }
+
+// the read lengths of 33..63 nt a pass's window holds (bit b = length 33 + b); wave_lib = the library of a pass that runs in
+// pair_wave_kernel: only those of them the kernel cannot take -- it sees the trimmed read, which must fit one word unless it
+// is longer than the library's longest entry (then it cannot align at all)
+uint64_t window_bits(const mrg_pass_cfg& c, const DevLib* wave_lib = nullptr) {
+  uint64_t m = 0;
+  for (int L = 33; L <= 63; ++L) {
+    const int Lt = L - c.trim5 - c.trim3;
+    if (L >= c.min_len && L <= c.max_len && (!wave_lib || (Lt > 32 && Lt <= (int)wave_lib->max_ref_len))) m |= 1ull << (L - 33);
+  }
+  return m;
+}
+
+// residency decision of match_kernel.  The superblock table (16 B per 65536 bp) and the segment
+// prefix always sit in LDS (`overhead`, with the control block and the 9-mer bitmap).  With the jump table most seed
+// searches need few LF steps, so the packed text (read by every verification) is the first thing worth
+// staging and two resident workgroups per CU (<= 80 KB each) beat a fuller LDS:
+//   2 = blocks + text, 3 = text only, 1 = blocks only, 0 = nothing.
+struct Residency {
+  int mode;
+  uint64_t bytes;
+};
+Residency match_residency(const mrg_ctx& ctx, const DevLib& l, uint64_t overhead) {
+  const uint64_t blk_bytes = (uint64_t)l.nblk * 16, txt_bytes = (uint64_t)l.text_words * 4;
+  const uint64_t budget = (uint64_t)ctx.lds_budget, hard = 160 * 1024, half = 80 * 1024;
+  Residency r{0, 0};
+  if (blk_bytes + txt_bytes <= budget && overhead + blk_bytes + txt_bytes <= half)
+    r = {2, blk_bytes + txt_bytes};
+  else if (ctx.prefer_two_blocks && txt_bytes <= budget && overhead + txt_bytes <= half)
+    r = {3, txt_bytes};
+  else if (blk_bytes + txt_bytes <= budget && overhead + blk_bytes + txt_bytes <= hard)
+    r = {2, blk_bytes + txt_bytes};
+  else if (txt_bytes <= budget && overhead + txt_bytes <= hard)
+    r = {3, txt_bytes};
+  else if (blk_bytes <= budget && overhead + blk_bytes <= hard)
+    r = {1, blk_bytes};
+  if (ctx.force_lds_mode >= 0) {  // test hook: exercise a specific kernel variant
+    const int m = (int)ctx.force_lds_mode;
+    const uint64_t need = (m == 2 ? blk_bytes + txt_bytes : m == 3 ? txt_bytes : m == 1 ? blk_bytes : 0);
+    if (overhead + need <= hard) r = {m, need};
+  }
+  return r;
+}
+
+// ---- launch plan: which passes run, and which consecutive ones share a (fused or seed) launch ----
+
+// one unit of a seed launch (dict.hip): 0 = an FM search over its members' libraries, 1 = a dictionary lookup
+struct SeedUnitPlan {
+  uint32_t kind;
+  std::vector<uint32_t> members;
+  bool stratum0 = false;  // the exact stratum of a LATER 2-mismatch pass (see plan_chain)
+};
+
+struct Launch {
+  enum Kind { kExact, kStrata, kPairs, kFused, kSeed };  // exact_dict_kernel; match / stratum kernel; anchor pairs; fused_kernel; seed kernels
+  Kind kind = kStrata;
+  uint32_t first = 0, end = 0;    // the passes it covers: [first, end), hint-skipped ones that ride inside a group included
+  std::vector<uint32_t> members;  // those of them that run (kSeed: see units)
+  int32_t k_first = 1, k_last = 1;             // kStrata / kPairs: the strata of the pigeonhole search it runs ...
+  bool first_part = true, last_part = true;   // ... and whether it is the pass's first / last launch
+  std::vector<SeedUnitPlan> units;  // kSeed
+  bool small = false;               // kSeed: the size class of its libraries
+  bool ends_cascade = false;        // nothing reads a survivor list behind it
+};
+
+// The launches of one chain -- the whole batch, or the FM side (dict_batch = false) or the one-word lane (dict_batch = true)
+// of a split batch -- in the order they are issued.  Pure: no HIP call, nothing of the context is written.
+// lane_long: the lane of a batch that may hold reads of 33..63 nt ("long_lane").
+// A 2-mismatch `--best` pass on a library with an exact-match dictionary, right behind a seed
+// launch: its exact stratum -- what most isomiRs are after the -5 / -3 trims -- rides in that launch
+// as a dictionary unit (a 0-mismatch hit is final: nothing beats it, the lowest (entry, offset) wins
+// ties as always); the pass's own launch then searches the reads that are left and does not count
+// "processed" again ("stratum0_unit").
+std::vector<Launch> plan_chain(const mrg_ctx& ctx, const mrg_pass_cfg* passes, uint32_t n_pass, uint64_t n, bool dict_batch,
+                               bool lane_long) {
+  auto lib = [&](uint32_t i) -> const DevLib& { return ctx.libs[passes[i].lib]; };
+  bool runs[MRG_MAX_PASSES], stratum0_done[MRG_MAX_PASSES] = {false};
+  for (uint32_t i = 0; i < n_pass; ++i) runs[i] = !pass_skipped(ctx, passes[i], i + 1 == n_pass);
+  auto fusable = [&](uint32_t i) {
+    // the first launched pass streams the whole read set and keeps the classic kernel (library
+    // text + full bitmap in LDS); 2-mismatch policies have their own stratum-first instantiation.
+    // (A fused launch counts offered / aligned reads in 16-bit per-lane fields: one workgroup per
+    // CU must see fewer than 65536 chunks.)
+    return ctx.fuse != 0 && passes[i].max_mm_seed <= 1 && n / (1024ull * (uint64_t)std::max(ctx.n_cu, 1)) < 60000ull;
+  };
+  // a pass seed_kernel can take as (part of) a unit, and the size class of its library
+  auto seedable = [&](uint32_t i) {
+    if (!dict_batch || !ctx.seed_units || ctx.force_lds_mode >= 0 || !fusable(i)) return false;
+    return pass_takes_dict(passes[i], lib(i)) || !lib(i).host_seqs.empty() || lib(i).sa16 != nullptr;
+  };
+  auto small_class = [&](uint32_t i) { return !lib(i).host_seqs.empty(); };
+
+  std::vector<Launch> plan;
+  bool launched_any = false;
+  for (uint32_t i = 0; i < n_pass;) {
+    if (!runs[i]) {
+      ++i;
+      continue;
+    }
+    // (a batch that may hold reads of 33..63 nt: the one-word lane reads a list from its first launch on, and only a seed
+    // launch can take such reads -- e.g. a batch of long reads only, whose first pass to run is the hairpin pass, len > 25)
+    const bool lane_first = lane_long && window_bits(passes[i]) != 0;
+    if ((launched_any || lane_first) && seedable(i)) {
+      Launch L;
+      L.kind = Launch::kSeed;
+      L.first = i;
+      L.small = small_class(i);
+      uint32_t j = i;
+      while (j < n_pass) {
+        if (!runs[j]) {
+          ++j;
+          continue;
+        }
+        if (!seedable(j) || small_class(j) != L.small) break;
+        const mrg_pass_cfg& c = passes[j];
+        const bool k1 = pass_takes_dict(c, lib(j));
+        int join = -1;
+        if (!k1 && L.small)  // small libraries searched with one policy: one unit over their concatenation
+          for (size_t u = 0; u < L.units.size(); ++u) {
+            if (L.units[u].kind != 0u || L.units[u].members.size() >= mrg::kSeedMaxMembers) continue;
+            const mrg_pass_cfg& d = passes[L.units[u].members[0]];
+            if (d.max_mm_seed == c.max_mm_seed && d.trim5 == c.trim5 && d.trim3 == c.trim3 && d.min_len == c.min_len &&
+                d.max_len == c.max_len && d.poly_t == c.poly_t) {
+              join = (int)u;
+              break;
+            }
+          }
+        if (join >= 0) {
+          L.units[join].members.push_back(j);
+        } else {
+          if (L.units.size() == mrg::kSeedMaxUnits) break;
+          L.units.push_back(SeedUnitPlan{k1 ? 1u : 0u, {j}});
+        }
+        ++j;
+      }
+      // (passes skipped by the length hint at the end of the run stay with it: never the last pass)
+      if (ctx.stratum0_unit && j < n_pass && runs[j] && !passes[j].poly_t && pass_takes_dict(passes[j], lib(j), 2) &&
+          L.units.size() < mrg::kSeedMaxUnits && ctx.pair_seeds && ctx.force_lds_mode < 0) {
+        SeedUnitPlan s0{1u, {j}};
+        s0.stratum0 = true;
+        L.units.push_back(s0);
+        stratum0_done[j] = true;
+      }
+      L.end = j;
+      L.ends_cascade = j == n_pass;
+      plan.push_back(std::move(L));
+      i = j;
+      // (a seed launch does NOT set launched_any: behind a long lane's first launch the passes still see "no launch yet" --
+      // a seed launch only where lane_first holds, never a fused one.  Kept: tests/test_gpu_split.py pins the lane's routes.)
+      continue;
+    }
+    Launch L;
+    L.first = i;
+    uint32_t j = i;
+    if (launched_any && fusable(i)) {
+      const bool cls = small_lib(ctx, lib(i));
+      while (j < n_pass && L.members.size() < mrg::kMaxFused) {
+        if (!runs[j]) {
+          ++j;
+          continue;
+        }
+        if (!fusable(j)) break;
+        if (ctx.fuse != 2 && small_lib(ctx, lib(j)) != cls) break;
+        if (ctx.fuse == 3 && !cls) break;
+        L.members.push_back(j++);
+      }
+      // passes skipped by the hint at the end of the run stay with the group (their events share
+      // the group's); a trailing skipped pass is never the last pass of the cascade
+    }
+    launched_any = true;
+    if (L.members.size() >= 2) {
+      L.kind = Launch::kFused;
+      L.end = j;
+      L.ends_cascade = L.members.back() + 1 == n_pass;
+      plan.push_back(std::move(L));
+      i = j;
+      continue;
+    }
+    const mrg_pass_cfg& c = passes[i];
+    L.members.assign(1, i);
+    L.end = i + 1;
+    L.ends_cascade = i + 1 == n_pass;
+    L.k_last = c.max_mm_seed + 1;
+    L.first_part = !stratum0_done[i];
+    if (dict_batch && pass_takes_dict(c, lib(i)) && ctx.force_lds_mode < 0) {
+      // no seed mismatch, one-word reads, a library with an exact-match dictionary: dict.hip
+      L.kind = Launch::kExact;
+    } else if (pass_takes_pairs(ctx, c, lib(i))) {
+      L.kind = Launch::kPairs;  // (whatever the batch or "pair_impl": stratum_kernel walks the pairs where pair_wave_kernel cannot)
+    } else if (c.max_mm_seed == 2 && ctx.split_strata) {
+      // strata 1..2 on the incoming reads, stratum 3 on the compacted survivors (kernels.hpp)
+      Launch head = L;
+      head.kind = Launch::kStrata;
+      head.k_last = 2;
+      head.last_part = head.ends_cascade = false;
+      plan.push_back(std::move(head));
+      L.kind = Launch::kStrata;
+      L.k_first = L.k_last = 3;
+      L.first_part = false;
+    } else {
+      L.kind = Launch::kStrata;
+    }
+    plan.push_back(std::move(L));
+    ++i;
+  }
+  return plan;
+}
+
+// Round 6: which read lengths beyond 32 nt the one-word lane of a split batch takes (bit b = length 33 + b, up to 63): the
+// seed kernels have instantiations that carry a read's second word (seeds from the first 32 bases, the rest compared
+// where an alignment is verified; dictionary units answer such reads by FM search); exact_dict_kernel and the FM kernels
+// of the lane do not, pair_wave_kernel takes a read whose TRIMMED length fits one word.  A length is let in when every
+// pass of the cascade either runs in a seed launch, or cannot hold a read of that length in its window, or
+// (pair_wave_kernel) sees at most 32 bases of it or could not align it at all (longer than the library's longest entry).
+// Read off the lane's own plan; 0 = the lane is for reads of at most 32 nt.
+uint64_t lane_long_mask(const mrg_ctx& ctx, const mrg_pass_cfg* passes, const std::vector<Launch>& lane_plan) {
+  uint64_t mask = (1ull << 31) - 1ull;
+  for (const Launch& L : lane_plan) {
+    if (L.kind == Launch::kSeed) continue;  // every length
+    // exact_dict_kernel, an FM kernel: only lengths its window keeps out (the lane is a dict_batch: with "pair_impl" = 0 its
+    // anchor-pair launch is stratum_kernel, an FM kernel)
+    const bool wave = L.kind == Launch::kPairs && pairs_by_wave(ctx, true);
+    for (uint32_t i : L.members) mask &= ~window_bits(passes[i], wave ? &ctx.libs[passes[i].lib] : nullptr);
+  }
+  return mask;
+}
+
+// pair tables of a large library (three anchors of A bases, gaps A and 2 A: pairs.hip), built on the device the first
+// time a cascade meets reads whose seed region is 3 A .. 4 A - 1 bases under a one-mismatch policy
+int ensure_bpair(DevLib& lm, int64_t A, hipStream_t stream) {
+  if (lm.bpair_anchor == (uint32_t)A || lm.bpair_failed) return MRG_OK;
+  (void)hipFree(lm.bpair_jump);
+  (void)hipFree(lm.bpair_rows);
+  lm.bpair_jump = nullptr;
+  lm.bpair_rows = nullptr;
+  lm.bpair_anchor = 0;
+  const uint64_t n_rows = (uint64_t)lm.n + 1, n_codes1 = (1ull << (4u * (uint32_t)A)) + 1ull;
+  const uint64_t need = 2 * n_codes1 * 4 + 2 * n_rows * 8 + 4 * n_rows * 4 + (256ull << 20);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (free_b < need || hipMalloc((void**)&lm.bpair_jump, 2 * n_codes1 * 4) != hipSuccess ||
+      hipMalloc((void**)&lm.bpair_rows, 2 * n_rows * 8) != hipSuccess ||
+      mrg::build_pair_tables_device(lm.sa, lm.text, (uint32_t)n_rows, (uint32_t)A, 2, lm.bpair_jump, lm.bpair_rows, lm.bpair_row_off,
+                                    stream) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(lm.bpair_jump);
+    (void)hipFree(lm.bpair_rows);
+    lm.bpair_jump = nullptr;
+    lm.bpair_rows = nullptr;
+    lm.bpair_failed = true;
+  } else {
+    lm.bpair_anchor = (uint32_t)A;
+  }
+  return MRG_OK;
+}
+// ... and handed to a parameter block (left as it is, anchor 0, where the build found no room: the pigeonhole pieces stay)
+int bind_bpair(DevLib& lm, int64_t A, hipStream_t stream, const uint32_t** jump, const uint64_t** rows, uint32_t* row_off,
+               uint32_t* anchor) {
+  if (const int rc = ensure_bpair(lm, A, stream)) return rc;
+  if (lm.bpair_anchor != (uint32_t)A) return MRG_OK;
+  *jump = lm.bpair_jump;
+  *rows = lm.bpair_rows;
+  row_off[0] = lm.bpair_row_off[0];
+  row_off[1] = lm.bpair_row_off[1];
+  *anchor = (uint32_t)A;
+  return MRG_OK;
+}
+
+// ---- issuing a plan ----
+
+// What one mrg_cascade_run call puts onto its stream: the call's arguments and carved workspace (fixed), and the state the
+// launches of the chain that is being issued hand on to one another -- which survivor list is the newest and in which form,
+// and the per-pass events.
+struct CascadeRun {
+  mrg_ctx* ctx;
+  const mrg_pass_cfg* passes;
+  uint32_t n_pass;
+  const uint64_t* d_reads;
+  const uint8_t* d_lens;
+  uint64_t n;
+  int8_t* d_pass_id;
+  int32_t *d_ref_id, *d_pos;
+  uint8_t* d_mm;
+  uint32_t* d_packed;
+  uint32_t *idx[3], *counts;  // the workspace: three list buffers and their segment counts,
+  uint64_t* stats;            // the per-pass counters,
+  uint4* ws_walk;             // the records wave_seed_kernel's waves leave behind their stream
+  hipStream_t stream;
+  bool timed;  // ("fused_step": no event lives inside the step: nothing between its launches)
+  // the chain: what its kernels see of the batch
+  bool dict_batch;
+  uint32_t words_eff;
+  const uint64_t* nmask_eff;
+  uint64_t long_mask = 0;  // the lengths beyond 32 nt its reads may have (lane_long_mask; only the lane of a split batch)
+  // its survivor lists
+  int cur_list = 0;          // which list buffer holds the newest survivor list
+  bool have_list = false;    // false: the next pass that runs reads the identity list of all reads
+  bool list_fat = false;     // the newest list carries its reads (16-byte entries, written by a seed launch or pair_wave_kernel)
+  bool out_init = false;     // the first launch wrote every output (exact_dict_kernel, streaming): later ones write claims only
+  int pair0 = 0, pair1 = 1;  // the two buffers the chain alternates between
+  uint32_t prev_grid = 0, prev_seg_cap = 0;  // segments of the newest list and their capacity
+  // its per-pass events
+  hipEvent_t* evs = nullptr;
+  uint8_t* ev_ix = nullptr;
+  uint32_t ev_last = 0;
+
+  int other_list(int cur) const { return cur == pair0 ? pair1 : pair0; }
+
+  // "grid_pct": every launch with this share of its workgroups (the kernels loop over their chunks, so fewer
+  // workgroups only means more trips each): leaves room on the CUs for the launches of ANOTHER cascade
+  // running on another stream at the same time
+  uint32_t scale_grid(uint32_t grid) const {
+    return std::max<uint32_t>(1u, (uint32_t)((uint64_t)grid * (uint64_t)ctx->grid_pct / 100u));
+  }
+  // Capacity of a producer workgroup's list segment: it must hold every read the workgroup may be
+  // offered -- its share of an identity list in chunks of `chunk` reads, or, reading a list, the
+  // chunks it walks (chunk c belongs to segment c % in_nseg and goes to workgroup c % grid: of
+  // in_nseg x depth chunks every grid-th one).
+  // (0 = the segments would not fit the workspace: every launch adds at most grid x chunk entries of
+  // rounding, kListSlack covers sixteen launches)
+  uint32_t segment_capacity(uint32_t grid, uint64_t chunk, bool reads_list) const {
+    uint64_t cap;
+    if (!reads_list) {
+      const uint64_t per_trip = chunk * grid;
+      cap = ((n + per_trip - 1) / per_trip) * chunk;
+    } else {
+      const uint64_t depth = ((uint64_t)prev_seg_cap + chunk - 1) / chunk;  // chunks of the longest input segment
+      cap = (((uint64_t)prev_grid * depth + grid - 1) / grid) * chunk;
+    }
+    if (cap * grid > n + mrg::kListSlack) return 0u;
+    return (uint32_t)cap;
+  }
+  // a launch's grid -- per_cu workgroups per CU, at most max_grid, scaled -- and the capacity of its output segments when a
+  // workgroup takes `chunk` reads per trip
+  template <class P>
+  int size_launch(P& p, uint32_t per_cu, uint32_t max_grid, uint64_t chunk, uint32_t* grid) const {
+    *grid = scale_grid(std::min<uint32_t>((uint32_t)ctx->n_cu * per_cu, max_grid));
+    p.out_seg_cap = segment_capacity(*grid, chunk, have_list);
+    if (!p.out_seg_cap && n) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
+    return MRG_OK;
+  }
+
+  // exact_dict_kernel and the FM kernels read index lists: a list that carries its reads is thinned into the other buffer
+  // first (the spike-in pass and non-default plans only)
+  int thin_list() {
+    if (!have_list || !list_fat) return MRG_OK;
+    const int other = other_list(cur_list);
+    HIP_TRY(mrg::launch_list_thin(reinterpret_cast<const uint4*>(idx[cur_list]), idx[other], counts + cur_list * mrg::kMaxSegments,
+                                  counts + other * mrg::kMaxSegments, prev_grid, prev_seg_cap, stream));
+    cur_list = other;
+    list_fat = false;
+    return MRG_OK;
+  }
+  // list wiring of a launch: it reads the newest list (or the identity list) and, if anything runs behind it, writes the
+  // chain's other buffer -- which becomes the newest list once the launch is issued (commit)
+  template <class P>
+  int wire_lists(P& p, bool wants_out) const {
+    const int next_list = have_list ? other_list(cur_list) : pair0;
+    p.idx_in = have_list ? idx[cur_list] : nullptr;
+    p.in_count = counts + cur_list * mrg::kMaxSegments;
+    p.in_nseg = prev_grid;
+    p.in_seg_cap = prev_seg_cap;
+    p.idx_out = wants_out ? idx[next_list] : nullptr;
+    p.out_count = counts + next_list * mrg::kMaxSegments;
+    return next_list;
+  }
+  template <class P>
+  void commit(const P& p, int next_list, uint32_t grid, bool fat) {
+    if (!p.idx_out) return;
+    cur_list = next_list;
+    have_list = true;
+    list_fat = fat;
+    prev_grid = grid;
+    prev_seg_cap = p.out_seg_cap;
+  }
+  template <class P>
+  void fill_outputs(P& p) const {
+    p.pass_id = d_pass_id;
+    p.ref_id = d_ref_id;
+    p.pos = d_pos;
+    p.mm = d_mm;
+    p.packed = d_packed;
+  }
+
+  // the chain's events: the opening one, then one per pass boundary
+  hipError_t begin_events(hipEvent_t* chain_evs, uint8_t* chain_ev_ix) {
+    evs = chain_evs;
+    ev_ix = chain_ev_ix;
+    ev_last = 0;
+    ev_ix[0] = 0;
+    return timed ? hipEventRecord(evs[0], stream) : hipSuccess;
+  }
+  // pass i is issued: `fresh` = something was launched since the boundary before
+  hipError_t mark(uint32_t i, bool fresh) {
+    if (!fresh || !timed) {
+      ev_ix[i + 1] = (uint8_t)ev_last;
+      return hipSuccess;
+    }
+    ev_ix[i + 1] = (uint8_t)(i + 1);
+    ev_last = i + 1;
+    return hipEventRecord(evs[i + 1], stream);
+  }
+
+  int launch_exact(const Launch& L);
+  int launch_fm(const Launch& L);
+  int launch_fused(const Launch& L);
+  int launch_seed(const Launch& L);
+  int issue(const std::vector<Launch>& plan);
+};
+
+// one exact_dict_kernel launch (dict.hip) for pass L.first
+int CascadeRun::launch_exact(const Launch& L) {
+  const uint32_t i = L.first;
+  const mrg_pass_cfg& c = passes[i];
+  const DevLib& l = ctx->libs[c.lib];
+  if (const int rc = thin_list()) return rc;
+  mrg::ExactParams e;
+  e.slots = reinterpret_cast<const uint4*>(l.dict_slots);
+  e.log2_slots = l.dict_log2;
+  e.key_bases = l.dict_key;
+  e.kbits = (ctx->kmer_filter && c.seed_len >= (int32_t)mrg::kKmerBitsK) ? l.kbits : nullptr;
+  fill_lib(e, l);
+  e.simple_segs = l.simple ? 1u : 0u;
+  e.reads = d_reads;
+  e.lens = d_lens;
+  e.n_total = (uint32_t)n;
+  const int next_list = wire_lists(e, !L.ends_cascade);
+  fill_outputs(e);
+  e.counters = stats + (size_t)i * kStatsPerPass;
+  fill_policy(e, c);
+  e.pass_index = (int32_t)i;
+  // (a workgroup takes chunks of 4096 reads: four per lane)
+  uint32_t grid;
+  if (const int rc = size_launch(e, 2u, 512u, mrg::kExactChunk, &grid)) return rc;
+  ctx->last_lds[i] = 0u;
+  ctx->last_mode[i] = 7u;
+  ctx->last_group[i] = i;
+  if (long_mask & window_bits(c))
+    return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached exact_dict_kernel (pass %u)", i);
+  if (n) HIP_TRY(mrg::launch_exact_dict(e, grid, stream));
+  ctx->last_variant[i] = (n && mrg::exact_dict_stretches(e, grid)) ? 16u : 0u;
+  ctx->last_launches[i] += 1;
+  HIP_TRY(mark(i, true));
+  if (n && mrg::exact_dict_streams(e)) out_init = true;  // (every output of the batch is written: later launches write claims only)
+  commit(e, next_list, grid, false);
+  return MRG_OK;
+}
+
+// the classic path: one launch of match_kernel, stratum_kernel or pair_wave_kernel for strata [k_first, k_last] of pass L.first
+int CascadeRun::launch_fm(const Launch& L) {
+  const uint32_t i = L.first;
+  const mrg_pass_cfg& c = passes[i];
+  const DevLib& l = ctx->libs[c.lib];
+  const bool by_pairs = L.kind == Launch::kPairs;
+  // (the plan says whether the pass takes the pairs; the batch and "pair_impl" only pick the kernel that walks them.
+  // pair_wave_kernel reads either list form; everything else launched here reads index lists)
+  const bool pair_wave_route = by_pairs && pairs_by_wave(*ctx, dict_batch);
+  if (!pair_wave_route)
+    if (const int rc = thin_list()) return rc;
+  mrg::MatchParams p;
+  fill_lib(p, l);
+  p.ctx = l.ctx;
+  if (!ctx->use_ftab) p.tabs.k[0] = 0u;
+  p.nblk = l.nblk;
+  p.nsup = l.nsup;
+  p.text_words = l.text_words;
+  p.simple_segs = l.simple ? 1u : 0u;
+  p.reads = d_reads;
+  p.reads_hi = nullptr;
+  p.lens = d_lens;
+  p.nmask = nmask_eff;
+  p.n_total = (uint32_t)n;
+  const int next_list = wire_lists(p, !L.ends_cascade);
+  p.in_stride = list_fat ? 4u : 1u;
+  p.out_init = out_init ? 1u : 0u;
+  p.k_first = L.k_first;
+  p.k_last = L.k_last;
+  p.count_processed = L.first_part ? 1u : 0u;
+  // (the length hints only decide which passes are launched: every kernel reads the length array --
+  // a caller whose equal hints do not describe the batch gets a skipped pass at worst, never a read
+  // aligned with somebody else's length)
+  p.uniform_len = 0u;
+  fill_outputs(p);
+  p.counters = stats + (size_t)i * kStatsPerPass;
+  fill_policy(p, c);
+  p.max_mm_seed = c.max_mm_seed;
+  p.pass_index = (int32_t)i;
+  p.wstop = (uint32_t)ctx->wstop;
+  // a large library's wide intervals are pre-filtered by row context in the cooperative path:
+  // send them there early (lane-serial verification of 100+ rows is what hurts short reads)
+  p.wide_rows = l.ctx ? (uint32_t)std::min<int64_t>(ctx->wide_rows, ctx->ctx_wide_rows) : (uint32_t)ctx->wide_rows;
+
+  // a small library's 9-mer bitmap (32 KB; only built for libraries whose text leaves room for
+  // it next to a second workgroup) rides in LDS ("kmer_filter" = 0 switches it off)
+  const bool use_kbits = small_lib(*ctx, l);
+  const uint64_t kb_bytes = use_kbits ? (uint64_t)mrg::kKmerBitsWords * 4 : 0;
+  p.kbits = use_kbits ? l.kbits : nullptr;
+  const uint64_t txt_bytes = (uint64_t)l.text_words * 4, hard = 160 * 1024;
+  const uint64_t overhead = (uint64_t)l.nsup * 16 + mrg::kMatchCtlBytes + kb_bytes;
+  if (overhead > hard) return fail(MRG_ERR_ARG, "mrg_cascade_run: the superblock table of library %d does not fit LDS", c.lib);
+  Residency res = match_residency(*ctx, l, overhead);
+  // a strata launch of a 2-mismatch pass whose rows are compacted over the wave (stratum_kernel):
+  // text in LDS when it fits, occ blocks always from L2
+  const bool rows_kernel = c.max_mm_seed == 2 && ctx->force_lds_mode < 0 &&
+                           (by_pairs || ctx->stratum_rows == 2 || (ctx->stratum_rows == 1 && L.k_first == L.k_last));
+  p.pair_anchor = by_pairs ? l.pair_anchor : 0u;
+  p.pair_jump = l.pair_jump;
+  p.pair_rows = l.pair_rows;
+  p.pair_jump_s = l.pair_jump_s;
+  for (int t = 0; t < 3; ++t) {
+    p.pair_row_off[t] = l.pair_row_off[t];
+    p.pair_row_off_s[t] = l.pair_row_off_s[t];
+  }
+  const uint64_t rows_overhead = (uint64_t)l.nsup * 16 + mrg::kStratumCtlBytes + kb_bytes;
+  bool rows_lds_text = false;
+  if (rows_kernel) {
+    if (rows_overhead > hard) return fail(MRG_ERR_ARG, "mrg_cascade_run: the superblock table of library %d does not fit LDS", c.lib);
+    rows_lds_text = txt_bytes <= (uint64_t)ctx->lds_budget && rows_overhead + txt_bytes <= hard;
+    res = rows_lds_text ? Residency{3, txt_bytes} : Residency{0, 0};
+  }
+  // one-word reads without N through the anchor pairs: pair_wave_kernel (dict.hip; every wave on its own, items
+  // and rows compacted over the wave; nothing staged in LDS but the wave's 256 reads)
+  const bool pair_wave = pair_wave_route && rows_kernel;
+  if (pair_wave) res = Residency{0, 0};
+  const uint32_t lds_total = pair_wave ? mrg::pair_wave_lds_total() : (uint32_t)((rows_kernel ? rows_overhead : overhead) + res.bytes);
+  const uint32_t per_cu = pair_wave ? std::min<uint32_t>(5u, (160u * 1024u) / lds_total) : ((lds_total * 2u <= 160u * 1024u) ? 2u : 1u);
+  // a workgroup's segment must hold every read it may be offered
+  uint32_t grid;
+  if (const int rc = size_launch(p, per_cu, mrg::kMaxSegments, 1024, &grid)) return rc;
+  ctx->last_lds[i] = (uint32_t)res.bytes;
+  ctx->last_mode[i] = !rows_kernel ? (uint32_t)res.mode : pair_wave ? 11u : (rows_lds_text ? 5u : 6u);
+  ctx->last_group[i] = i;
+  ctx->last_kbits_log2[i] = use_kbits ? 18u : 0u;
+  ctx->last_pair_anchor[i] = p.pair_anchor;
+  if (long_mask && !pair_wave && (long_mask & window_bits(c)))
+    return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached a one-word kernel (pass %u)", i);
+  if (n && pair_wave) {
+    p.reads_hi = long_mask ? d_reads + n : nullptr;
+    ctx->last_variant[i] = long_mask ? 8u : 0u;
+    HIP_TRY(mrg::launch_pair_wave(p, grid, stream));
+  } else if (n && rows_kernel) {
+    HIP_TRY(mrg::launch_stratum(p, words_eff, rows_lds_text, grid, lds_total, stream));
+  } else if (n) {
+    HIP_TRY(mrg::launch_match(p, words_eff, res.mode, grid, lds_total, stream));
+  }
+  ctx->last_launches[i] += 1;
+  if (L.last_part) HIP_TRY(mark(i, true));
+  commit(p, next_list, grid, pair_wave);
+  return MRG_OK;
+}
+
+// one fused_kernel launch for the running passes L.members
+int CascadeRun::launch_fused(const Launch& L) {
+  const std::vector<uint32_t>& members = L.members;
+  const uint32_t n_sub = (uint32_t)members.size();
+  for (uint32_t q = 0; q < n_sub; ++q)
+    if (long_mask & window_bits(passes[members[q]]))
+      return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached fused_kernel<1> (pass %u)", members[q]);
+  mrg::FusedParams fp;
+  std::memset(&fp, 0, sizeof fp);
+  fp.n_sub = n_sub;
+  // which sub-passes filter seed pieces with their library's 9-mer bitmap
+  uint32_t lg[mrg::kMaxFused];
+  for (uint32_t q = 0; q < n_sub; ++q) lg[q] = small_lib(*ctx, ctx->libs[passes[members[q]].lib]) ? 18u : 0u;
+  // one 1024-thread workgroup per CU (128 VGPRs per lane), so the whole LDS is its own
+  const uint64_t fixed = mrg::fused_fixed_lds_bytes();
+  const uint64_t lds_cap = 160 * 1024;
+  const uint64_t budget = std::min<uint64_t>((uint64_t)std::max<int64_t>(ctx->lds_budget, (int64_t)fixed), lds_cap) - fixed;
+  // rounds: the sub-passes of a run of bitmap-filtered libraries are looked up together (few
+  // items per read), with "round_large" = 1 so are those of a run of large ones (measured equal,
+  // default 0: every unclaimed read has items in each of them)
+  fp.n_rounds = 0;
+  for (uint32_t q = 0; q < n_sub;) {
+    uint32_t e = q + 1;
+    if (lg[q] || ctx->round_large)
+      while (e < n_sub && (lg[e] != 0) == (lg[q] != 0) && e - q < mrg::kMaxRoundSubs) ++e;
+    fp.round_first[fp.n_rounds] = (uint8_t)q;
+    fp.round_count[fp.n_rounds] = (uint8_t)(e - q);
+    ++fp.n_rounds;
+    q = e;
+  }
+  // the 9-mer table of each bitmap round: one entry per code with a bit per sub-pass, as many
+  // codes (2^18 = every 9-mer, else folded: entry h = OR of the codes = h mod 2^log2) as the LDS
+  // left by the other rounds' tables allows
+  uint32_t n_tab_rounds = 0;
+  for (uint32_t r = 0; r < fp.n_rounds; ++r) n_tab_rounds += lg[fp.round_first[r]] ? 1u : 0u;
+  uint32_t kb_words = 0;
+  for (uint32_t q = 0; q < n_sub; ++q) {
+    const uint32_t i = members[q];
+    const mrg_pass_cfg& c = passes[i];
+    DevLib& l = ctx->libs[c.lib];
+    mrg::SubPass& sp = fp.sub[q];
+    fill_lib(sp, l);
+    sp.ctx = l.ctx;
+    sp.sa16 = reinterpret_cast<const uint4*>(l.sa16);
+    if (!ctx->use_ftab) sp.tabs.k[0] = 0u;
+    sp.nmask = nmask_eff;
+    sp.counters = stats + (size_t)i * kStatsPerPass;
+    sp.simple_segs = l.simple ? 1u : 0u;
+    sp.kb_bit = 0xFFu;
+    fill_policy(sp, c);
+    sp.max_mm_seed = c.max_mm_seed;
+    sp.pass_index = (int32_t)i;
+    sp.pair_anchor = 0u;
+    // (with "round_large" the large libraries' sub-passes share a round: no reads are set aside for the three anchor pairs)
+    if (const int64_t A = ctx->round_large ? 0 : three_anchor_tables(*ctx, c, l))
+      if (const int rc = bind_bpair(l, A, stream, &sp.pair_jump, &sp.pair_rows, sp.pair_row_off, &sp.pair_anchor)) return rc;
+    ctx->last_pair_anchor[i] = sp.pair_anchor;
+    ctx->last_lds[i] = 0u;
+    ctx->last_mode[i] = 4u;
+    ctx->last_group[i] = members[0];
+    ctx->last_kbits_log2[i] = 0u;
+  }
+  for (uint32_t r = 0; r < fp.n_rounds; ++r) {
+    const uint32_t q0 = fp.round_first[r], nq = fp.round_count[r];
+    fp.round_kb_log2[r] = 0;
+    fp.round_kb_bits[r] = 0;
+    fp.round_kb_off[r] = 0;
+    fp.round_kb_src[r] = nullptr;
+    if (!lg[q0]) continue;
+    const uint32_t bits = nq <= 4 ? 4u : 8u;
+    uint32_t log2c = 18;
+    while (log2c > 13 && ((uint64_t)(1u << log2c) * bits / 8) * n_tab_rounds > budget) --log2c;
+    if (((uint64_t)(1u << log2c) * bits / 8) * n_tab_rounds > budget) {  // no room: unfiltered
+      for (uint32_t q = q0; q < q0 + nq; ++q) ctx->last_kbits_log2[members[q]] = 255u;
+      continue;
+    }
+    std::string key;
+    for (uint32_t q = q0; q < q0 + nq; ++q) key += std::to_string(passes[members[q]].lib) + ",";
+    key += "|" + std::to_string(log2c) + "|" + std::to_string(bits);
+    uint32_t* d_tab = nullptr;
+    for (auto& kv : ctx->round_tables)
+      if (kv.first == key) d_tab = kv.second;
+    if (!d_tab) {
+      std::vector<uint32_t> tab(((size_t)1 << log2c) * bits / 32, 0u);
+      for (uint32_t q = q0; q < q0 + nq; ++q) {
+        const std::vector<uint32_t>& kbh = ctx->libs[passes[members[q]].lib].kbits_host;
+        for (uint32_t c = 0; c < (1u << 18); ++c) {
+          if (!((kbh[c >> 5] >> (c & 31u)) & 1u)) continue;
+          const uint64_t bit = (uint64_t)(c & ((1u << log2c) - 1u)) * bits + (q - q0);
+          tab[bit >> 5] |= 1u << (bit & 31u);
+        }
+      }
+      HIP_TRY(hipMalloc((void**)&d_tab, tab.size() * 4));
+      HIP_TRY(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+      ctx->round_tables.emplace_back(key, d_tab);
+    }
+    fp.round_kb_src[r] = d_tab;
+    fp.round_kb_off[r] = kb_words;
+    fp.round_kb_log2[r] = (uint8_t)log2c;
+    fp.round_kb_bits[r] = (uint8_t)bits;
+    const uint32_t words = (uint32_t)(((size_t)1 << log2c) * bits / 32);
+    kb_words += words;
+    for (uint32_t q = q0; q < q0 + nq; ++q) {
+      fp.sub[q].kb_bit = q - q0;
+      ctx->last_lds[members[q]] = words * 4u / nq;
+      ctx->last_kbits_log2[members[q]] = log2c;
+    }
+  }
+  fp.kb_words = kb_words;
+  fp.reads = d_reads;
+  fp.lens = d_lens;
+  fp.nmask = nmask_eff;
+  fp.n_total = (uint32_t)n;
+  fp.uniform_len = 0u;  // (see launch_fm)
+  if (const int rc = thin_list()) return rc;
+  const int next_list = wire_lists(fp, !L.ends_cascade);
+  fill_outputs(fp);
+  fp.wstop = (uint32_t)ctx->wstop;
+  const uint32_t lds_total = kb_words * 4u + (uint32_t)fixed;
+  // 128 VGPRs per lane (no spills in the pipelined walk): 16 waves = one workgroup per CU
+  uint32_t grid;
+  if (const int rc = size_launch(fp, 1u, mrg::kMaxSegments, 1024, &grid)) return rc;
+  if (n) HIP_TRY(mrg::launch_fused(fp, words_eff, grid, lds_total, stream));
+  ctx->last_launches[L.first] = 1;
+  // (the hint-skipped passes inside the group share its event)
+  for (uint32_t q = L.first; q < L.end; ++q) HIP_TRY(mark(q, q == L.first));
+  commit(fp, next_list, grid, false);
+  return MRG_OK;
+}
+
+// one seed_kernel / wave_seed_kernel launch (dict.hip) for the units of L
+int CascadeRun::launch_seed(const Launch& L) {
+  const std::vector<SeedUnitPlan>& plan = L.units;
+  mrg::SeedParams sp;
+  std::memset(&sp, 0, sizeof sp);
+  sp.n_units = (uint32_t)plan.size();
+  for (uint32_t u = 0; u < sp.n_units; ++u) {
+    mrg::SeedUnit& un = sp.unit[u];
+    const mrg_pass_cfg& c0 = passes[plan[u].members[0]];
+    un.kind = plan[u].kind;
+    const DevLib* fm = &ctx->libs[c0.lib];
+    SeedLib* sl = nullptr;
+    if (un.kind == 0u) {
+      std::vector<int32_t> ids;
+      for (uint32_t i : plan[u].members) ids.push_back(passes[i].lib);
+      if (const int rc = get_seed_lib(ctx, ids, &sl)) return rc;
+      fm = &sl->lib;
+      un.kbits = sl->kbits;
+    } else {
+      un.slots = reinterpret_cast<const uint4*>(fm->dict_slots);
+      un.log2_slots = fm->dict_log2;
+      un.key_bases = fm->dict_key;
+    }
+    // an FM unit of one library that wants its three-anchor tables (wave_seed_kernel parks those reads for the three anchor
+    // pairs); a unit over several libraries is a small-library unit, a stratum-0 unit is a dictionary unit: neither has any
+    if (const int64_t A = (un.kind == 0u && plan[u].members.size() == 1 && !plan[u].stratum0)
+                              ? three_anchor_tables(*ctx, c0, ctx->libs[c0.lib]) : 0)
+      if (const int rc = bind_bpair(ctx->libs[c0.lib], A, stream, &un.bpair_jump, &un.bpair_rows, un.bpair_row_off, &un.bpair_anchor))
+        return rc;
+    fill_lib(un, *fm);
+    un.sa16 = reinterpret_cast<const uint4*>(fm->sa16);
+    un.buckets = ctx->seed_buckets ? reinterpret_cast<const uint4*>(fm->buckets) : nullptr;
+    un.bucket_k = fm->bucket_k;
+    un.pos_rows = (ctx->seed_buckets && ctx->pos_scan) ? reinterpret_cast<const uint4*>(fm->pos_rows) : nullptr;
+    un.simple_segs = fm->simple ? 1u : 0u;
+    fill_window(un, c0);
+    un.max_mm_seed = plan[u].stratum0 ? 0 : c0.max_mm_seed;
+    un.n_members = (uint32_t)plan[u].members.size();
+    un.min_seed_len = 0x7FFFFFFF;
+    un.max_total = 0;
+    for (uint32_t mi = 0; mi < un.n_members; ++mi) {
+      const uint32_t i = plan[u].members[mi];
+      const mrg_pass_cfg& c = passes[i];
+      un.m[mi].pass_index = (int32_t)i;
+      un.m[mi].seed_len = c.seed_len;
+      un.m[mi].max_mm_total = c.max_mm_total;
+      un.m[mi].entry_lo = sl ? sl->entry_lo[mi] : 0u;
+      un.min_seed_len = std::min(un.min_seed_len, c.seed_len);
+      un.max_total = std::max(un.max_total, c.max_mm_total);
+      if (plan[u].stratum0) continue;  // (that pass has its own launch afterwards and reports that one)
+      ctx->last_lds[i] = 0u;
+      ctx->last_mode[i] = 8u;
+      ctx->last_group[i] = L.first;
+      ctx->last_kbits_log2[i] = un.kbits ? 22u : 0u;
+    }
+  }
+  // which kernel: by default (-1) the tile kernel for the small libraries' launch (its waves are bound by what
+  // they do per read; with more registers and fewer waves the wave kernel only draws level, and its parked
+  // reads leave the list's order) and the wave kernel, 96 registers, for a launch on large libraries (bound by
+  // the L2 misses of its bucket / slot lines: no barrier, nothing parked but overflowing buckets: 2.08 -> 1.8 ms)
+  {
+    const int64_t impl = ctx->seed_impl >= 0 ? ctx->seed_impl : (L.small ? 0 : 2);
+    sp.impl = impl ? 1u : 0u;
+    sp.wave_regs = impl >= 2 ? 1u : 0u;
+    for (uint32_t q = L.first; q < L.end; ++q)
+      ctx->last_variant[q] = (sp.impl ? ((sp.wave_regs & 1u) ? 2u : 1u) : 0u) | ((have_list && list_fat) ? 4u : 0u) | (long_mask ? 8u : 0u);
+  }
+  sp.reads_per_lane = 1u;
+  sp.item_cap = mrg::kSeedThreads * sp.reads_per_lane * 2u;
+  sp.row_cap = sp.impl ? 192u : (L.small ? 1024u : 2048u);
+  sp.stats = stats;
+  sp.reads = d_reads;
+  sp.reads_hi = long_mask ? d_reads + n : nullptr;
+  sp.lens = d_lens;
+  sp.n_total = (uint32_t)n;
+  const int next_list = wire_lists(sp, !L.ends_cascade);
+  sp.in_stride = list_fat ? 4u : 1u;
+  sp.out_init = out_init ? 1u : 0u;
+  fill_outputs(sp);
+  {
+    // which instantiation the launch gets: mrg_pass_stats.lds_mode 8 = seed_kernel<false, 8>, 9 = <true, 6>
+    bool with_buckets = false;
+    for (uint32_t u = 0; u < sp.n_units; ++u) with_buckets |= sp.unit[u].kind == 0u && sp.unit[u].buckets != nullptr;
+    if (with_buckets)
+      for (uint32_t q = L.first; q < L.end; ++q)
+        if (ctx->last_mode[q] == 8u) ctx->last_mode[q] = 9u;
+    // mrg_pass_stats.pair_anchor, as a fused launch reports it: only wave_seed_kernel's instantiation with buckets
+    // parks the reads of 3 A .. 4 A - 1 seed bases for the three anchor pairs
+    for (uint32_t u = 0; u < sp.n_units; ++u)
+      if (sp.impl && with_buckets && sp.unit[u].bpair_anchor)
+        for (uint32_t i : plan[u].members) ctx->last_pair_anchor[i] = sp.unit[u].bpair_anchor;
+  }
+  const uint32_t per_cu = ctx->seed_wgs > 0 ? (uint32_t)ctx->seed_wgs : mrg::seed_wgs_per_cu(sp);
+  uint32_t grid;
+  if (const int rc = size_launch(sp, per_cu, mrg::kMaxSegments, (uint64_t)mrg::kSeedThreads * sp.reads_per_lane, &grid)) return rc;
+  sp.walk_buf = nullptr;
+  sp.walk_cap = 0;
+  sp.walk_diag = (uint32_t)ctx->walk_diag;
+  if (sp.impl) {
+    // units with position lists (round 6): every wave keeps the records of the reads it leaves to them in its own stretch
+    // of a context buffer and walks the lists behind its stream
+    bool lists = false;
+    for (uint32_t u = 0; u < sp.n_units; ++u) lists |= sp.unit[u].kind == 0u && sp.unit[u].pos_rows != nullptr;
+    if (lists) {
+      sp.walk_buf = ws_walk;
+      sp.walk_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(ctx->walk_cap, 0), (int64_t)kWalkCap);
+    }
+  }
+  if (n) HIP_TRY(mrg::launch_seed(sp, grid, stream));
+  ctx->last_launches[L.first] = 1;
+  for (uint32_t q = L.first; q < L.end; ++q) HIP_TRY(mark(q, q == L.first));
+  commit(sp, next_list, grid, true);
+  return MRG_OK;
+}
+
+// the launches of the chain's plan, in order; a pass no launch covers was skipped by the length hint and shares the event of
+// the boundary before it
+int CascadeRun::issue(const std::vector<Launch>& plan) {
+  uint32_t next = 0;
+  for (const Launch& L : plan) {
+    for (; next < L.first; ++next) HIP_TRY(mark(next, false));
+    const int rc = L.kind == Launch::kExact ? launch_exact(L)
+                   : L.kind == Launch::kFused ? launch_fused(L)
+                   : L.kind == Launch::kSeed ? launch_seed(L)
+                                             : launch_fm(L);
+    if (rc != MRG_OK) return rc;
+    next = L.end;
+  }
+  return MRG_OK;
+}
+
 // mrg_cascade_run / mrg_cascade_run_packed: d_packed != null = the one-array output form
 int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read,
                     const uint8_t* d_lens, const uint64_t* d_nmask, uint64_t n,
@@ -1129,107 +2019,6 @@ int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
     ctx->ev_ready = true;
   }
 
-  char* ws = (char*)d_workspace;
-  uint32_t* idx[3] = {(uint32_t*)ws, (uint32_t*)(ws + ws_idx_bytes(n)), (uint32_t*)(ws + 2 * ws_idx_bytes(n))};
-  uint32_t* counts = (uint32_t*)(ws + 3 * ws_idx_bytes(n));
-  uint64_t* stats = (uint64_t*)(ws + 3 * ws_idx_bytes(n) + kWsCountsBytes);
-  uint4* const ws_walk = (uint4*)(ws + 3 * ws_idx_bytes(n) + kWsCountsBytes + kWsStatsBytes);
-  // per-pass counters only; the outputs need no memset (the last pass writes the
-  // "unannotated" values for whatever it does not claim)
-  HIP_TRY(hipMemsetAsync(stats, 0, kWsStatsBytes, stream));
-  uint32_t prev_grid = 0, prev_seg_cap = 0;
-  // "grid_pct": every launch with this share of its workgroups (the kernels loop over their chunks, so fewer
-  // workgroups only means more trips each): leaves room on the CUs for the launches of ANOTHER cascade
-  // running on another stream at the same time
-  auto scale_grid = [&](uint32_t grid) -> uint32_t {
-    return std::max<uint32_t>(1u, (uint32_t)((uint64_t)grid * (uint64_t)ctx->grid_pct / 100u));
-  };
-  // Capacity of a producer workgroup's list segment: it must hold every read the workgroup may be
-  // offered -- its share of an identity list in chunks of `chunk` reads, or, reading a list, the
-  // chunks it walks (chunk c belongs to segment c % in_nseg and goes to workgroup c % grid: of
-  // in_nseg x depth chunks every grid-th one).
-  // (0 = the segments would not fit the workspace: every launch adds at most grid x chunk entries of
-  // rounding, kListSlack covers sixteen launches)
-  auto segment_capacity = [&](uint32_t grid, uint64_t chunk, bool reads_list) -> uint32_t {
-    uint64_t cap;
-    if (!reads_list) {
-      const uint64_t per_trip = chunk * grid;
-      cap = ((n + per_trip - 1) / per_trip) * chunk;
-    } else {
-      const uint64_t depth = ((uint64_t)prev_seg_cap + chunk - 1) / chunk;  // chunks of the longest input segment
-      cap = (((uint64_t)prev_grid * depth + grid - 1) / grid) * chunk;
-    }
-    if (cap * grid > n + mrg::kListSlack) return 0u;
-    return (uint32_t)cap;
-  };
-  int cur_list = 0;        // which list buffer holds the newest survivor list
-  bool have_list = false;  // false: the next pass that runs reads the identity list of all reads
-  bool list_fat = false;   // the newest list carries its reads (16-byte entries, written by a seed launch or pair_wave_kernel)
-  bool out_init = false;   // the first launch wrote every output (exact_dict_kernel, streaming): later ones write claims only
-  int pair0 = 0, pair1 = 1;  // the two buffers the running cascade alternates between
-  auto other_list = [&](int cur) { return cur == pair0 ? pair1 : pair0; };
-
-  // exact_dict_kernel and the FM kernels read index lists: a list that carries its reads is thinned into the other buffer
-  // first (the spike-in pass and non-default plans only)
-  auto want_thin_list = [&]() -> int {
-    if (!have_list || !list_fat) return MRG_OK;
-    const int other = other_list(cur_list);
-    HIP_TRY(mrg::launch_list_thin(reinterpret_cast<const uint4*>(idx[cur_list]), idx[other], counts + cur_list * mrg::kMaxSegments,
-                                  counts + other * mrg::kMaxSegments, prev_grid, prev_seg_cap, stream));
-    cur_list = other;
-    list_fat = false;
-    return MRG_OK;
-  };
-
-  hipEvent_t* evs = ctx->ev;  // the per-pass events of the cascade that is being issued
-  uint8_t* ev_ix = ctx->ev_ix;
-  uint32_t ev_last = 0;
-  const bool timed = !ctx->fused_step;  // ("fused_step": no event lives inside the step: nothing between its launches)
-  ctx->last_timed = timed;
-  if (timed) HIP_TRY(hipEventRecord(evs[0], stream));
-  ev_ix[0] = 0;
-  // pass i is issued: `fresh` = something was launched since the boundary before
-  auto mark = [&](uint32_t i, bool fresh) -> hipError_t {
-    if (!fresh || !timed) {
-      ev_ix[i + 1] = (uint8_t)ev_last;
-      return hipSuccess;
-    }
-    ev_ix[i + 1] = (uint8_t)(i + 1);
-    ev_last = i + 1;
-    return hipEventRecord(evs[i + 1], stream);
-  };
-
-  // ---- launch plan: which passes run, and which consecutive ones share a (fused) launch ----
-  // A pass whose length window excludes every read of the batch (caller's hint: e.g. the hairpin
-  // pass, len > 25, on 22-nt reads) would only copy its input list: it is not launched; its
-  // counters stay zero and the next pass reads the same list.  (Never the last pass: that one
-  // writes the "unannotated" values.)
-  // A 2-mismatch `--best` pass on a library with an exact-match dictionary, right behind a seed
-  // launch: its exact stratum -- what most isomiRs are after the -5 / -3 trims -- rides in that launch
-  // as a dictionary unit (a 0-mismatch hit is final: nothing beats it, the lowest (entry, offset) wins
-  // ties as always); the pass's own launch then searches the reads that are left and does not count
-  // "processed" again.
-  bool stratum0_done[MRG_MAX_PASSES] = {false};
-  bool runs[MRG_MAX_PASSES];
-  for (uint32_t i = 0; i < n_pass; ++i) {
-    const mrg_pass_cfg& c = passes[i];
-    runs[i] = !(i + 1 < n_pass && (c.min_len > ctx->hint_max_len || c.max_len < ctx->hint_min_len));
-    ctx->last_lds[i] = 0;
-    ctx->last_mode[i] = 0;
-    ctx->last_group[i] = i;
-    ctx->last_launches[i] = 0;
-    ctx->last_kbits_log2[i] = 0;
-    ctx->last_pair_anchor[i] = 0;
-    ctx->last_variant[i] = 0;
-  }
-  auto fusable = [&](uint32_t i) {
-    // the first launched pass streams the whole read set and keeps the classic kernel (library
-    // text + full bitmap in LDS); 2-mismatch policies have their own stratum-first instantiation.
-    // (A fused launch counts offered / aligned reads in 16-bit per-lane fields: one workgroup per
-    // CU must see fewer than 65536 chunks.)
-    return ctx->fuse != 0 && passes[i].max_mm_seed <= 1 && n / (1024ull * (uint64_t)std::max(ctx->n_cu, 1)) < 60000ull;
-  };
-  auto small_lib = [&](uint32_t i) { return ctx->libs[passes[i].lib].kbits != nullptr && ctx->kmer_filter; };
   // one-word reads without N: the batches the dictionary kernels (dict.hip) take.  A batch with
   // longer reads, reads with N or very short reads is SPLIT: the reads of split_min_len .. 32 nt
   // without N -- most of any small-RNA read set -- go through the cascade as the one-word batch they
@@ -1237,705 +2026,43 @@ int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
   // backtracking search does not mind a 16-nt read's 8-base seeds); two cascades over disjoint lists,
   // one after the other, adding to the same counters.  (The length hint only says whether a one-word
   // batch may hold such short reads: a wrong hint costs time, never a result.)
-  bool dict_batch = ctx->dict && words_per_read == 1 && !d_nmask;
-  uint32_t words_eff = words_per_read;
-  const uint64_t* nmask_eff = d_nmask;
+  const bool dict_batch = ctx->dict && words_per_read == 1 && !d_nmask;
   const bool split = ctx->dict && ctx->split_mixed && n > 0 && ctx->force_lds_mode < 0 &&
                      (!dict_batch || ctx->hint_min_len < ctx->split_min_len) &&
                      (ctx->hint_min_len <= 32 || (ctx->long_lane && words_per_read >= 2 && ctx->hint_min_len <= 63)) &&
                      ctx->hint_max_len >= ctx->split_min_len;  // (some read may be on either side)
+  // the one-word lane of a split batch may take reads of 33..63 nt ("long_lane"): the lengths its plan lets in
+  const bool lane_long = split && ctx->long_lane && words_per_read >= 2 && ctx->hint_max_len > 32;
+  // chain 0: the whole batch, or the FM side of a split one (long reads and reads with N); chain 1: the one-word lane
+  std::vector<Launch> plans[2];
+  plans[0] = plan_chain(*ctx, passes, n_pass, n, split ? false : dict_batch, false);
+  if (split) plans[1] = plan_chain(*ctx, passes, n_pass, n, true, lane_long);
+  const uint64_t long_plan = lane_long ? lane_long_mask(*ctx, passes, plans[1]) : 0;
 
-  // Round 6: which read lengths beyond 32 nt the one-word lane of a split batch takes (bit b = length 33 + b, up to 63): the
-  // seed kernels have instantiations that carry a read's second word (seeds from the first 32 bases, the rest compared
-  // where an alignment is verified; dictionary units answer such reads by FM search); exact_dict_kernel and the FM kernels
-  // of the lane do not, pair_wave_kernel takes a read whose TRIMMED length fits one word.  A length is let in when every
-  // pass of the cascade either runs in a seed launch, or cannot hold a read of that length in its window, or
-  // (pair_wave_kernel) sees at most 32 bases of it or could not align it at all (longer than the library's longest entry).
-  // Decided below, once the lambdas that route a pass exist; 0 = the lane is for reads of at most 32 nt, as before.
-  uint64_t long_mask = 0;
-  auto window_bits = [](const mrg_pass_cfg& c) -> uint64_t {
-    uint64_t m = 0;
-    for (int L = 33; L <= 63; ++L)
-      if (L >= c.min_len && L <= c.max_len) m |= 1ull << (L - 33);
-    return m;
-  };
-  // the classic path: one match_kernel launch for pass i
-  auto run_single = [&](uint32_t i, int32_t k_first, int32_t k_last, bool first_part, bool last_part, bool by_pairs = false) -> int {
-    const mrg_pass_cfg& c = passes[i];
-    const DevLib& l = ctx->libs[c.lib];
-    // (pair_wave_kernel reads either list form; everything else launched here reads index lists)
-    const bool pair_wave_route = by_pairs && dict_batch && ctx->pair_impl != 0 && c.max_mm_seed == 2 && ctx->force_lds_mode < 0;
-    if (!pair_wave_route) {
-      const int rc_form = want_thin_list();
-      if (rc_form != MRG_OK) return rc_form;
-    }
-    // (the dictionary's key is matched letter for letter: only a pass whose seed covers it may take it)
-    if (dict_batch && c.max_mm_seed == 0 && l.dict_slots && c.seed_len >= (int32_t)l.dict_key && ctx->force_lds_mode < 0) {
-      // no seed mismatch, one-word reads, a library with an exact-match dictionary: dict.hip
-      mrg::ExactParams e;
-      e.slots = reinterpret_cast<const uint4*>(l.dict_slots);
-      e.log2_slots = l.dict_log2;
-      e.key_bases = l.dict_key;
-      e.kbits = (ctx->kmer_filter && c.seed_len >= (int32_t)mrg::kKmerBitsK) ? l.kbits : nullptr;
-      e.blocks = l.blocks;
-      e.super = l.super;
-      e.primary = l.primary;
-      e.ftab = l.ftab;
-      e.tabs = l.tabs;
-      e.sa = l.sa;
-      e.text = l.text;
-      e.n = l.n;
-      e.seg_start = l.seg_start;
-      e.seg_ref = l.seg_ref;
-      e.seg_off = l.seg_off;
-      e.chunk_seg = l.chunk_seg;
-      e.simple_segs = l.simple ? 1u : 0u;
-      e.reads = d_reads;
-      e.lens = d_lens;
-      e.n_total = (uint32_t)n;
-      const int next_list = have_list ? other_list(cur_list) : pair0;
-      e.idx_in = have_list ? idx[cur_list] : nullptr;
-      e.in_count = counts + cur_list * mrg::kMaxSegments;
-      e.in_nseg = prev_grid;
-      e.in_seg_cap = prev_seg_cap;
-      e.idx_out = (i + 1 < n_pass) ? idx[next_list] : nullptr;
-      e.out_count = counts + next_list * mrg::kMaxSegments;
-      e.pass_id = d_pass_id;
-      e.ref_id = d_ref_id;
-      e.pos = d_pos;
-      e.mm = d_mm;
-      e.packed = d_packed;
-      e.counters = stats + (size_t)i * kStatsPerPass;
-      e.seed_len = c.seed_len;
-      e.max_mm_total = c.max_mm_total;
-      e.trim5 = c.trim5;
-      e.trim3 = c.trim3;
-      e.min_len = c.min_len;
-      e.max_len = c.max_len;
-      e.poly_t = c.poly_t;
-      e.pass_index = (int32_t)i;
-      uint32_t grid = (uint32_t)ctx->n_cu * 2u;
-      if (grid > 512u) grid = 512u;
-      grid = scale_grid(grid);
-      // (a workgroup takes chunks of 4096 reads: four per lane)
-      const uint32_t seg_cap = segment_capacity(grid, mrg::kExactChunk, have_list);
-      if (!seg_cap && n) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
-      e.out_seg_cap = seg_cap;
-      ctx->last_lds[i] = 0u;
-      ctx->last_mode[i] = 7u;
-      ctx->last_group[i] = i;
-      if (long_mask & window_bits(c))
-        return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached exact_dict_kernel (pass %u)", i);
-      if (n) HIP_TRY(mrg::launch_exact_dict(e, grid, stream));
-      ctx->last_variant[i] = (n && mrg::exact_dict_stretches(e, grid)) ? 16u : 0u;
-      ctx->last_launches[i] += 1;
-      HIP_TRY(mark(i, true));
-      if (n && mrg::exact_dict_streams(e)) out_init = true;  // (every output of the batch is written: later launches write claims only)
-      if (e.idx_out) {
-        cur_list = next_list;
-        have_list = true;
-        list_fat = false;
-        prev_grid = grid;
-        prev_seg_cap = seg_cap;
-      }
-      return MRG_OK;
-    }
-    mrg::MatchParams p;
-    p.blocks = l.blocks;
-    p.super = l.super;
-    p.text = l.text;
-    p.sa = l.sa;
-    p.ctx = l.ctx;
-    p.ftab = l.ftab;
-    p.tabs = l.tabs;
-    if (!ctx->use_ftab) p.tabs.k[0] = 0u;
-    p.seg_start = l.seg_start;
-    p.seg_ref = l.seg_ref;
-    p.seg_off = l.seg_off;
-    p.chunk_seg = l.chunk_seg;
-    p.n = l.n;
-    p.nblk = l.nblk;
-    p.nsup = l.nsup;
-    p.primary = l.primary;
-    p.text_words = l.text_words;
-    p.simple_segs = l.simple ? 1u : 0u;
-    p.reads = d_reads;
-    p.reads_hi = nullptr;
-    p.lens = d_lens;
-    p.nmask = nmask_eff;
-    p.n_total = (uint32_t)n;
-    const int next_list = have_list ? other_list(cur_list) : pair0;
-    p.idx_in = have_list ? idx[cur_list] : nullptr;
-    p.in_count = counts + cur_list * mrg::kMaxSegments;
-    p.in_nseg = prev_grid;
-    p.in_seg_cap = prev_seg_cap;
-    p.idx_out = (i + 1 < n_pass || !last_part) ? idx[next_list] : nullptr;
-    p.in_stride = list_fat ? 4u : 1u;
-    p.out_init = out_init ? 1u : 0u;
-    p.k_first = k_first;
-    p.k_last = k_last;
-    p.count_processed = first_part ? 1u : 0u;
-    // (the length hints only decide which passes are launched: every kernel reads the length array --
-    // a caller whose equal hints do not describe the batch gets a skipped pass at worst, never a read
-    // aligned with somebody else's length)
-    p.uniform_len = 0u;
-    p.out_count = counts + next_list * mrg::kMaxSegments;
-    p.pass_id = d_pass_id;
-    p.ref_id = d_ref_id;
-    p.pos = d_pos;
-    p.mm = d_mm;
-    p.packed = d_packed;
-    p.counters = stats + (size_t)i * kStatsPerPass;
-    p.seed_len = c.seed_len;
-    p.max_mm_seed = c.max_mm_seed;
-    p.max_mm_total = c.max_mm_total;
-    p.trim5 = c.trim5;
-    p.trim3 = c.trim3;
-    p.min_len = c.min_len;
-    p.max_len = c.max_len;
-    p.poly_t = c.poly_t;
-    p.pass_index = (int32_t)i;
-    p.wstop = (uint32_t)ctx->wstop;
-    // a large library's wide intervals are pre-filtered by row context in the cooperative path:
-    // send them there early (lane-serial verification of 100+ rows is what hurts short reads)
-    p.wide_rows = l.ctx ? (uint32_t)std::min<int64_t>(ctx->wide_rows, ctx->ctx_wide_rows) : (uint32_t)ctx->wide_rows;
-
-    // residency decision.  The superblock table (16 B per 65536 bp) and the segment
-    // prefix always sit in LDS.  With the jump table most seed searches need few LF
-    // steps, so the packed text (read by every verification) is the first thing worth
-    // staging and two resident workgroups per CU (<= 80 KB each) beat a fuller LDS:
-    //   2 = blocks + text, 3 = text only, 1 = blocks only, 0 = nothing.
-    const uint64_t blk_bytes = (uint64_t)l.nblk * 16, txt_bytes = (uint64_t)l.text_words * 4;
-    // a small library's 9-mer bitmap (32 KB; only built for libraries whose text leaves room for
-    // it next to a second workgroup) rides in LDS ("kmer_filter" = 0 switches it off)
-    const uint64_t kb_bytes = (l.kbits && ctx->kmer_filter) ? (uint64_t)mrg::kKmerBitsWords * 4 : 0;
-    const bool use_kbits = kb_bytes != 0;
-    p.kbits = use_kbits ? l.kbits : nullptr;
-    const uint64_t overhead = (uint64_t)l.nsup * 16 + mrg::kMatchCtlBytes + (use_kbits ? kb_bytes : 0);
-    const uint64_t budget = (uint64_t)ctx->lds_budget, hard = 160 * 1024, half = 80 * 1024;
-    if (overhead > hard)
-      return fail(MRG_ERR_ARG, "mrg_cascade_run: the superblock table of library %d does not fit LDS", c.lib);
-    int lds_mode = 0;
-    uint64_t lib_bytes = 0;
-    if (blk_bytes + txt_bytes <= budget && overhead + blk_bytes + txt_bytes <= half) {
-      lds_mode = 2;
-      lib_bytes = blk_bytes + txt_bytes;
-    } else if (ctx->prefer_two_blocks && txt_bytes <= budget && overhead + txt_bytes <= half) {
-      lds_mode = 3;
-      lib_bytes = txt_bytes;
-    } else if (blk_bytes + txt_bytes <= budget && overhead + blk_bytes + txt_bytes <= hard) {
-      lds_mode = 2;
-      lib_bytes = blk_bytes + txt_bytes;
-    } else if (txt_bytes <= budget && overhead + txt_bytes <= hard) {
-      lds_mode = 3;
-      lib_bytes = txt_bytes;
-    } else if (blk_bytes <= budget && overhead + blk_bytes <= hard) {
-      lds_mode = 1;
-      lib_bytes = blk_bytes;
-    }
-    if (ctx->force_lds_mode >= 0) {  // test hook: exercise a specific kernel variant
-      const int m = (int)ctx->force_lds_mode;
-      const uint64_t need = (m == 2 ? blk_bytes + txt_bytes : m == 3 ? txt_bytes : m == 1 ? blk_bytes : 0);
-      if (overhead + need <= hard) {
-        lds_mode = m;
-        lib_bytes = need;
-      }
-    }
-    // a strata launch of a 2-mismatch pass whose rows are compacted over the wave (stratum_kernel):
-    // text in LDS when it fits, occ blocks always from L2
-    const bool rows_kernel = c.max_mm_seed == 2 && ctx->force_lds_mode < 0 &&
-                             (by_pairs || ctx->stratum_rows == 2 || (ctx->stratum_rows == 1 && k_first == k_last));
-    p.pair_anchor = by_pairs ? l.pair_anchor : 0u;
-    p.pair_jump = l.pair_jump;
-    p.pair_rows = l.pair_rows;
-    p.pair_jump_s = l.pair_jump_s;
-    for (int t = 0; t < 3; ++t) {
-      p.pair_row_off[t] = l.pair_row_off[t];
-      p.pair_row_off_s[t] = l.pair_row_off_s[t];
-    }
-    bool rows_lds_text = false;
-    if (rows_kernel) {
-      const uint64_t ov = (uint64_t)l.nsup * 16 + mrg::kStratumCtlBytes + (use_kbits ? kb_bytes : 0);
-      if (ov > hard)
-        return fail(MRG_ERR_ARG, "mrg_cascade_run: the superblock table of library %d does not fit LDS", c.lib);
-      rows_lds_text = txt_bytes <= budget && ov + txt_bytes <= hard;
-      lds_mode = rows_lds_text ? 3 : 0;
-      lib_bytes = rows_lds_text ? txt_bytes : 0;
-    }
-    // one-word reads without N through the anchor pairs: pair_wave_kernel (dict.hip; every wave on its own, items
-    // and rows compacted over the wave; nothing staged in LDS but the wave's 256 reads)
-    const bool pair_wave = pair_wave_route && rows_kernel;
-    if (pair_wave) {
-      lds_mode = 0;
-      lib_bytes = 0;
-    }
-    const uint32_t lds_total = pair_wave ? mrg::pair_wave_lds_total()
-                               : rows_kernel ? (uint32_t)((uint64_t)l.nsup * 16 + mrg::kStratumCtlBytes + (use_kbits ? kb_bytes : 0) + lib_bytes)
-                                             : (uint32_t)(overhead + lib_bytes);
-    const uint32_t lds_bytes = (uint32_t)lib_bytes;
-    const uint32_t per_cu = pair_wave ? std::min<uint32_t>(5u, (160u * 1024u) / lds_total) : ((lds_total * 2u <= 160u * 1024u) ? 2u : 1u);
-    uint32_t grid = (uint32_t)ctx->n_cu * per_cu;
-    if (grid > mrg::kMaxSegments) grid = mrg::kMaxSegments;
-    grid = scale_grid(grid);
-    // a workgroup's segment must hold every read it may be offered
-    const uint32_t seg_cap = segment_capacity(grid, 1024, have_list);
-    if (!seg_cap && n) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
-    p.out_seg_cap = seg_cap;
-    ctx->last_lds[i] = lds_bytes;
-    ctx->last_mode[i] = (uint32_t)lds_mode;
+  char* ws = (char*)d_workspace;
+  CascadeRun run{ctx, passes, n_pass, d_reads, d_lens, n, d_pass_id, d_ref_id, d_pos, d_mm, d_packed};
+  for (int b = 0; b < 3; ++b) run.idx[b] = (uint32_t*)(ws + b * ws_idx_bytes(n));
+  run.counts = (uint32_t*)(ws + 3 * ws_idx_bytes(n));
+  run.stats = (uint64_t*)(ws + 3 * ws_idx_bytes(n) + kWsCountsBytes);
+  run.ws_walk = (uint4*)(ws + 3 * ws_idx_bytes(n) + kWsCountsBytes + kWsStatsBytes);
+  run.stream = stream;
+  run.timed = !ctx->fused_step;
+  run.dict_batch = dict_batch;
+  run.words_eff = words_per_read;
+  run.nmask_eff = d_nmask;
+  // per-pass counters only; the outputs need no memset (the last pass writes the
+  // "unannotated" values for whatever it does not claim)
+  HIP_TRY(hipMemsetAsync(run.stats, 0, kWsStatsBytes, stream));
+  ctx->last_timed = run.timed;
+  HIP_TRY(run.begin_events(ctx->ev, ctx->ev_ix));
+  for (uint32_t i = 0; i < n_pass; ++i) {
+    ctx->last_lds[i] = 0;
+    ctx->last_mode[i] = 0;
     ctx->last_group[i] = i;
-    ctx->last_kbits_log2[i] = use_kbits ? 18u : 0u;
-    ctx->last_pair_anchor[i] = p.pair_anchor;
-    if (rows_kernel) ctx->last_mode[i] = pair_wave ? 11u : (rows_lds_text ? 5u : 6u);
-    if (long_mask && !pair_wave && (long_mask & window_bits(c)))
-      return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached a one-word kernel (pass %u)", i);
-    if (n && pair_wave) {
-      p.reads_hi = long_mask ? d_reads + n : nullptr;
-      ctx->last_variant[i] = long_mask ? 8u : 0u;
-      HIP_TRY(mrg::launch_pair_wave(p, grid, stream));
-    } else if (n && rows_kernel) {
-      HIP_TRY(mrg::launch_stratum(p, words_eff, rows_lds_text, grid, lds_total, stream));
-    } else if (n) {
-      HIP_TRY(mrg::launch_match(p, words_eff, lds_mode, grid, lds_total, stream));
-    }
-    ctx->last_launches[i] += 1;
-    if (last_part) HIP_TRY(mark(i, true));
-    if (p.idx_out) {
-      cur_list = next_list;
-      have_list = true;
-      list_fat = pair_wave;
-      prev_grid = grid;
-      prev_seg_cap = seg_cap;
-    }
-    return MRG_OK;
-  };
-
-  // pair tables of a large library (three anchors of A bases, gaps A and 2 A: pairs.hip), built on the device the first
-  // time a cascade meets reads whose seed region is 3 A .. 4 A - 1 bases under a one-mismatch policy
-  auto ensure_bpair = [&](DevLib& lm, int64_t A) -> int {
-    if (lm.bpair_anchor == (uint32_t)A || lm.bpair_failed) return MRG_OK;
-    (void)hipFree(lm.bpair_jump);
-    (void)hipFree(lm.bpair_rows);
-    lm.bpair_jump = nullptr;
-    lm.bpair_rows = nullptr;
-    lm.bpair_anchor = 0;
-    const uint64_t n_rows = (uint64_t)lm.n + 1, n_codes1 = (1ull << (4u * (uint32_t)A)) + 1ull;
-    const uint64_t need = 2 * n_codes1 * 4 + 2 * n_rows * 8 + 4 * n_rows * 4 + (256ull << 20);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (free_b < need || hipMalloc((void**)&lm.bpair_jump, 2 * n_codes1 * 4) != hipSuccess ||
-        hipMalloc((void**)&lm.bpair_rows, 2 * n_rows * 8) != hipSuccess ||
-        mrg::build_pair_tables_device(lm.sa, lm.text, (uint32_t)n_rows, (uint32_t)A, 2, lm.bpair_jump, lm.bpair_rows, lm.bpair_row_off,
-                                      stream) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(lm.bpair_jump);
-      (void)hipFree(lm.bpair_rows);
-      lm.bpair_jump = nullptr;
-      lm.bpair_rows = nullptr;
-      lm.bpair_failed = true;
-    } else {
-      lm.bpair_anchor = (uint32_t)A;
-    }
-    return MRG_OK;
-  };
-
-  // one fused_kernel launch for the running passes among [first, last]
-  auto run_fused = [&](const uint32_t* members, uint32_t n_sub, bool ends_cascade) -> int {
-    for (uint32_t q = 0; q < n_sub; ++q)
-      if (long_mask & window_bits(passes[members[q]]))
-        return fail(MRG_ERR_ARG, "mrg_cascade_run: internal: reads of more than 32 nt reached fused_kernel<1> (pass %u)", members[q]);
-    mrg::FusedParams fp;
-    std::memset(&fp, 0, sizeof fp);
-    fp.n_sub = n_sub;
-    // which sub-passes filter seed pieces with their library's 9-mer bitmap
-    uint32_t lg[mrg::kMaxFused];
-    for (uint32_t q = 0; q < n_sub; ++q) lg[q] = small_lib(members[q]) ? 18u : 0u;
-    // one 1024-thread workgroup per CU (128 VGPRs per lane), so the whole LDS is its own
-    const uint64_t fixed = mrg::fused_fixed_lds_bytes();
-    const uint64_t lds_cap = 160 * 1024;
-    const uint64_t budget = std::min<uint64_t>((uint64_t)std::max<int64_t>(ctx->lds_budget, (int64_t)fixed), lds_cap) - fixed;
-    // rounds: the sub-passes of a run of bitmap-filtered libraries are looked up together (few
-    // items per read), with "round_large" = 1 so are those of a run of large ones (measured equal,
-    // default 0: every unclaimed read has items in each of them)
-    fp.n_rounds = 0;
-    for (uint32_t q = 0; q < n_sub;) {
-      uint32_t e = q + 1;
-      if (lg[q] || ctx->round_large)
-        while (e < n_sub && (lg[e] != 0) == (lg[q] != 0) && e - q < mrg::kMaxRoundSubs) ++e;
-      fp.round_first[fp.n_rounds] = (uint8_t)q;
-      fp.round_count[fp.n_rounds] = (uint8_t)(e - q);
-      ++fp.n_rounds;
-      q = e;
-    }
-    // the 9-mer table of each bitmap round: one entry per code with a bit per sub-pass, as many
-    // codes (2^18 = every 9-mer, else folded: entry h = OR of the codes = h mod 2^log2) as the LDS
-    // left by the other rounds' tables allows
-    uint32_t n_tab_rounds = 0;
-    for (uint32_t r = 0; r < fp.n_rounds; ++r) n_tab_rounds += lg[fp.round_first[r]] ? 1u : 0u;
-    uint32_t kb_words = 0;
-    for (uint32_t q = 0; q < n_sub; ++q) {
-      const uint32_t i = members[q];
-      const mrg_pass_cfg& c = passes[i];
-      const DevLib& l = ctx->libs[c.lib];
-      mrg::SubPass& sp = fp.sub[q];
-      sp.blocks = l.blocks;
-      sp.super = l.super;
-      sp.text = l.text;
-      sp.sa = l.sa;
-      sp.ctx = l.ctx;
-      sp.sa16 = reinterpret_cast<const uint4*>(l.sa16);
-      sp.ftab = l.ftab;
-      sp.tabs = l.tabs;
-      if (!ctx->use_ftab) sp.tabs.k[0] = 0u;
-      sp.seg_start = l.seg_start;
-      sp.seg_ref = l.seg_ref;
-      sp.seg_off = l.seg_off;
-      sp.chunk_seg = l.chunk_seg;
-      sp.nmask = nmask_eff;
-      sp.counters = stats + (size_t)i * kStatsPerPass;
-      sp.n = l.n;
-      sp.primary = l.primary;
-      sp.simple_segs = l.simple ? 1u : 0u;
-      sp.kb_bit = 0xFFu;
-      sp.seed_len = c.seed_len;
-      sp.max_mm_seed = c.max_mm_seed;
-      sp.max_mm_total = c.max_mm_total;
-      sp.trim5 = c.trim5;
-      sp.trim3 = c.trim3;
-      sp.min_len = c.min_len;
-      sp.max_len = c.max_len;
-      sp.poly_t = c.poly_t;
-      sp.pass_index = (int32_t)i;
-      sp.pair_anchor = 0u;
-      {
-        // reads whose seed region is 3A .. 4A - 1 bases: three anchor pairs instead of two pieces of
-        // less than 2A bases (tables built on the device at first use, pairs.hip)
-        const int64_t A = ctx->pair_big;
-        const int64_t r_min = std::min<int64_t>(std::max<int64_t>(ctx->hint_min_len, c.min_len) - c.trim5 - c.trim3, c.seed_len);
-        const int64_t r_max = std::min<int64_t>(std::min<int64_t>(ctx->hint_max_len, c.max_len) - c.trim5 - c.trim3, c.seed_len);
-        if (A && c.max_mm_seed == 1 && !c.poly_t && l.n >= mrg::kWideRowMinBases && !ctx->round_large && r_min < 4 * A &&
-            r_max >= 3 * A) {
-          DevLib& lm = ctx->libs[c.lib];
-          {
-            const int rc_bp = ensure_bpair(lm, A);
-            if (rc_bp != MRG_OK) return rc_bp;
-          }
-          if (lm.bpair_anchor == (uint32_t)A) {
-            sp.pair_jump = lm.bpair_jump;
-            sp.pair_rows = lm.bpair_rows;
-            sp.pair_row_off[0] = lm.bpair_row_off[0];
-            sp.pair_row_off[1] = lm.bpair_row_off[1];
-            sp.pair_anchor = (uint32_t)A;
-          }
-        }
-      }
-      ctx->last_pair_anchor[i] = sp.pair_anchor;
-      ctx->last_lds[i] = 0u;
-      ctx->last_mode[i] = 4u;
-      ctx->last_group[i] = members[0];
-      ctx->last_kbits_log2[i] = 0u;
-    }
-    for (uint32_t r = 0; r < fp.n_rounds; ++r) {
-      const uint32_t q0 = fp.round_first[r], nq = fp.round_count[r];
-      fp.round_kb_log2[r] = 0;
-      fp.round_kb_bits[r] = 0;
-      fp.round_kb_off[r] = 0;
-      fp.round_kb_src[r] = nullptr;
-      if (!lg[q0]) continue;
-      const uint32_t bits = nq <= 4 ? 4u : 8u;
-      uint32_t log2c = 18;
-      while (log2c > 13 && ((uint64_t)(1u << log2c) * bits / 8) * n_tab_rounds > budget) --log2c;
-      if (((uint64_t)(1u << log2c) * bits / 8) * n_tab_rounds > budget) {  // no room: unfiltered
-        for (uint32_t q = q0; q < q0 + nq; ++q) ctx->last_kbits_log2[members[q]] = 255u;
-        continue;
-      }
-      std::string key;
-      for (uint32_t q = q0; q < q0 + nq; ++q) key += std::to_string(passes[members[q]].lib) + ",";
-      key += "|" + std::to_string(log2c) + "|" + std::to_string(bits);
-      uint32_t* d_tab = nullptr;
-      for (auto& kv : ctx->round_tables)
-        if (kv.first == key) d_tab = kv.second;
-      if (!d_tab) {
-        std::vector<uint32_t> tab(((size_t)1 << log2c) * bits / 32, 0u);
-        for (uint32_t q = q0; q < q0 + nq; ++q) {
-          const std::vector<uint32_t>& kbh = ctx->libs[passes[members[q]].lib].kbits_host;
-          for (uint32_t c = 0; c < (1u << 18); ++c) {
-            if (!((kbh[c >> 5] >> (c & 31u)) & 1u)) continue;
-            const uint64_t bit = (uint64_t)(c & ((1u << log2c) - 1u)) * bits + (q - q0);
-            tab[bit >> 5] |= 1u << (bit & 31u);
-          }
-        }
-        HIP_TRY(hipMalloc((void**)&d_tab, tab.size() * 4));
-        HIP_TRY(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        ctx->round_tables.emplace_back(key, d_tab);
-      }
-      fp.round_kb_src[r] = d_tab;
-      fp.round_kb_off[r] = kb_words;
-      fp.round_kb_log2[r] = (uint8_t)log2c;
-      fp.round_kb_bits[r] = (uint8_t)bits;
-      const uint32_t words = (uint32_t)(((size_t)1 << log2c) * bits / 32);
-      kb_words += words;
-      for (uint32_t q = q0; q < q0 + nq; ++q) {
-        fp.sub[q].kb_bit = q - q0;
-        ctx->last_lds[members[q]] = words * 4u / nq;
-        ctx->last_kbits_log2[members[q]] = log2c;
-      }
-    }
-    fp.kb_words = kb_words;
-    fp.reads = d_reads;
-    fp.lens = d_lens;
-    fp.nmask = nmask_eff;
-    fp.n_total = (uint32_t)n;
-    fp.uniform_len = 0u;  // (see run_single)
-    {
-      const int rc_form = want_thin_list();
-      if (rc_form != MRG_OK) return rc_form;
-    }
-    const int next_list = have_list ? other_list(cur_list) : pair0;
-    fp.idx_in = have_list ? idx[cur_list] : nullptr;
-    fp.in_count = counts + cur_list * mrg::kMaxSegments;
-    fp.in_nseg = prev_grid;
-    fp.in_seg_cap = prev_seg_cap;
-    fp.idx_out = ends_cascade ? nullptr : idx[next_list];
-    fp.out_count = counts + next_list * mrg::kMaxSegments;
-    fp.pass_id = d_pass_id;
-    fp.ref_id = d_ref_id;
-    fp.pos = d_pos;
-    fp.mm = d_mm;
-    fp.packed = d_packed;
-    fp.wstop = (uint32_t)ctx->wstop;
-    const uint32_t lds_total = kb_words * 4u + (uint32_t)fixed;
-    // 128 VGPRs per lane (no spills in the pipelined walk): 16 waves = one workgroup per CU
-    const uint32_t per_cu = 1u;
-    uint32_t grid = (uint32_t)ctx->n_cu * per_cu;
-    if (grid > mrg::kMaxSegments) grid = mrg::kMaxSegments;
-    grid = scale_grid(grid);
-    const uint32_t seg_cap = segment_capacity(grid, 1024, have_list);
-    if (!seg_cap && n) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
-    fp.out_seg_cap = seg_cap;
-    if (n) HIP_TRY(mrg::launch_fused(fp, words_eff, grid, lds_total, stream));
-    ctx->last_launches[members[0]] = 1;
-    for (uint32_t q = 0; q < n_sub; ++q) HIP_TRY(mark(members[q], q == 0));
-    if (fp.idx_out) {
-      cur_list = next_list;
-      have_list = true;
-      list_fat = false;
-      prev_grid = grid;
-      prev_seg_cap = seg_cap;
-    }
-    return MRG_OK;
-  };
-
-  // one seed_kernel launch (dict.hip) for the passes of `plan`: each entry = one unit = (kind, member passes)
-  struct UnitPlan {
-    uint32_t kind;
-    std::vector<uint32_t> members;
-    bool stratum0 = false;  // the exact stratum of a LATER 2-mismatch pass (see stratum0_done)
-  };
-  auto run_seed = [&](const std::vector<UnitPlan>& plan, uint32_t first, uint32_t end, bool ends_cascade, bool small) -> int {
-    mrg::SeedParams sp;
-    std::memset(&sp, 0, sizeof sp);
-    sp.n_units = (uint32_t)plan.size();
-    for (uint32_t u = 0; u < sp.n_units; ++u) {
-      mrg::SeedUnit& un = sp.unit[u];
-      const mrg_pass_cfg& c0 = passes[plan[u].members[0]];
-      un.kind = plan[u].kind;
-      const DevLib* fm = &ctx->libs[c0.lib];
-      SeedLib* sl = nullptr;
-      if (un.kind == 0u) {
-        std::vector<int32_t> ids;
-        for (uint32_t i : plan[u].members) ids.push_back(passes[i].lib);
-        int rc = get_seed_lib(ctx, ids, &sl);
-        if (rc != MRG_OK) return rc;
-        fm = &sl->lib;
-        un.kbits = sl->kbits;
-      } else {
-        un.slots = reinterpret_cast<const uint4*>(fm->dict_slots);
-        un.log2_slots = fm->dict_log2;
-        un.key_bases = fm->dict_key;
-      }
-      // one large library under a one-mismatch policy, and (by the length hint) reads whose seed region is 3 A .. 4 A - 1
-      // bases: its pair tables (wave_seed_kernel parks those reads for the three anchor pairs)
-      if (un.kind == 0u && plan[u].members.size() == 1 && !c0.poly_t && c0.max_mm_seed == 1 && ctx->pair_big && !plan[u].stratum0 &&
-          ctx->libs[c0.lib].n >= mrg::kWideRowMinBases) {
-        const int64_t A = ctx->pair_big;
-        const int64_t r_min = std::min<int64_t>(std::max<int64_t>(ctx->hint_min_len, c0.min_len) - c0.trim5 - c0.trim3, c0.seed_len);
-        const int64_t r_max = std::min<int64_t>(std::min<int64_t>(ctx->hint_max_len, c0.max_len) - c0.trim5 - c0.trim3, c0.seed_len);
-        if (r_min < 4 * A && r_max >= 3 * A) {
-          DevLib& lm = ctx->libs[c0.lib];
-          const int rc_bp = ensure_bpair(lm, A);
-          if (rc_bp != MRG_OK) return rc_bp;
-          if (lm.bpair_anchor == (uint32_t)A) {
-            un.bpair_jump = lm.bpair_jump;
-            un.bpair_rows = lm.bpair_rows;
-            un.bpair_row_off[0] = lm.bpair_row_off[0];
-            un.bpair_row_off[1] = lm.bpair_row_off[1];
-            un.bpair_anchor = (uint32_t)A;
-          }
-        }
-      }
-      un.ftab = fm->ftab;
-      un.tabs = fm->tabs;
-      un.sa16 = reinterpret_cast<const uint4*>(fm->sa16);
-      un.buckets = ctx->seed_buckets ? reinterpret_cast<const uint4*>(fm->buckets) : nullptr;
-      un.bucket_k = fm->bucket_k;
-      un.pos_rows = (ctx->seed_buckets && ctx->pos_scan) ? reinterpret_cast<const uint4*>(fm->pos_rows) : nullptr;
-      un.sa = fm->sa;
-      un.text = fm->text;
-      un.blocks = fm->blocks;
-      un.super = fm->super;
-      un.primary = fm->primary;
-      un.n = fm->n;
-      un.seg_start = fm->seg_start;
-      un.seg_ref = fm->seg_ref;
-      un.seg_off = fm->seg_off;
-      un.chunk_seg = fm->chunk_seg;
-      un.simple_segs = fm->simple ? 1u : 0u;
-      un.max_mm_seed = plan[u].stratum0 ? 0 : c0.max_mm_seed;
-      un.trim5 = c0.trim5;
-      un.trim3 = c0.trim3;
-      un.min_len = c0.min_len;
-      un.max_len = c0.max_len;
-      un.poly_t = c0.poly_t;
-      un.n_members = (uint32_t)plan[u].members.size();
-      un.min_seed_len = 0x7FFFFFFF;
-      un.max_total = 0;
-      for (uint32_t mi = 0; mi < un.n_members; ++mi) {
-        const uint32_t i = plan[u].members[mi];
-        const mrg_pass_cfg& c = passes[i];
-        un.m[mi].pass_index = (int32_t)i;
-        un.m[mi].seed_len = c.seed_len;
-        un.m[mi].max_mm_total = c.max_mm_total;
-        un.m[mi].entry_lo = sl ? sl->entry_lo[mi] : 0u;
-        un.min_seed_len = std::min(un.min_seed_len, c.seed_len);
-        un.max_total = std::max(un.max_total, c.max_mm_total);
-        if (plan[u].stratum0) continue;  // (that pass has its own launch afterwards and reports that one)
-        ctx->last_lds[i] = 0u;
-        ctx->last_mode[i] = 8u;
-        ctx->last_group[i] = first;
-        ctx->last_kbits_log2[i] = un.kbits ? 22u : 0u;
-      }
-    }
-    // which kernel: by default (-1) the tile kernel for the small libraries' launch (its waves are bound by what
-    // they do per read; with more registers and fewer waves the wave kernel only draws level, and its parked
-    // reads leave the list's order) and the wave kernel, 96 registers, for a launch on large libraries (bound by
-    // the L2 misses of its bucket / slot lines: no barrier, nothing parked but overflowing buckets: 2.08 -> 1.8 ms)
-    {
-      const int64_t impl = ctx->seed_impl >= 0 ? ctx->seed_impl : (small ? 0 : 2);
-      sp.impl = impl ? 1u : 0u;
-      sp.wave_regs = impl >= 2 ? 1u : 0u;
-      for (uint32_t q = first; q < end; ++q)
-        ctx->last_variant[q] = (sp.impl ? ((sp.wave_regs & 1u) ? 2u : 1u) : 0u) | ((have_list && list_fat) ? 4u : 0u) | (long_mask ? 8u : 0u);
-    }
-    sp.reads_per_lane = 1u;
-    sp.item_cap = mrg::kSeedThreads * sp.reads_per_lane * 2u;
-    sp.row_cap = sp.impl ? 192u : (small ? 1024u : 2048u);
-    sp.stats = stats;
-    sp.reads = d_reads;
-    sp.reads_hi = long_mask ? d_reads + n : nullptr;
-    sp.lens = d_lens;
-    sp.n_total = (uint32_t)n;
-    const int next_list = have_list ? other_list(cur_list) : pair0;
-    sp.idx_in = have_list ? idx[cur_list] : nullptr;
-    sp.in_stride = list_fat ? 4u : 1u;
-    sp.out_init = out_init ? 1u : 0u;
-    sp.in_count = counts + cur_list * mrg::kMaxSegments;
-    sp.in_nseg = prev_grid;
-    sp.in_seg_cap = prev_seg_cap;
-    sp.idx_out = ends_cascade ? nullptr : idx[next_list];
-    sp.out_count = counts + next_list * mrg::kMaxSegments;
-    sp.pass_id = d_pass_id;
-    sp.ref_id = d_ref_id;
-    sp.pos = d_pos;
-    sp.mm = d_mm;
-    sp.packed = d_packed;
-    {
-      // which instantiation the launch gets: mrg_pass_stats.lds_mode 8 = seed_kernel<false, 8>, 9 = <true, 6>
-      bool with_buckets = false;
-      for (uint32_t u = 0; u < sp.n_units; ++u) with_buckets |= sp.unit[u].kind == 0u && sp.unit[u].buckets != nullptr;
-      if (with_buckets)
-        for (uint32_t q = first; q < end; ++q)
-          if (ctx->last_mode[q] == 8u) ctx->last_mode[q] = 9u;
-      // mrg_pass_stats.pair_anchor, as a fused launch reports it: only wave_seed_kernel's instantiation with buckets
-      // parks the reads of 3 A .. 4 A - 1 seed bases for the three anchor pairs
-      for (uint32_t u = 0; u < sp.n_units; ++u)
-        if (sp.impl && with_buckets && sp.unit[u].bpair_anchor)
-          for (uint32_t i : plan[u].members) ctx->last_pair_anchor[i] = sp.unit[u].bpair_anchor;
-    }
-    const uint32_t lds = mrg::seed_lds_bytes(sp);
-    (void)lds;
-    uint32_t grid = (uint32_t)ctx->n_cu * (ctx->seed_wgs > 0 ? (uint32_t)ctx->seed_wgs : mrg::seed_wgs_per_cu(sp));
-    if (grid > mrg::kMaxSegments) grid = mrg::kMaxSegments;
-    grid = scale_grid(grid);
-    const uint32_t seg_cap = segment_capacity(grid, (uint64_t)mrg::kSeedThreads * sp.reads_per_lane, have_list);
-    if (!seg_cap && n) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
-    sp.out_seg_cap = seg_cap;
-    sp.walk_buf = nullptr;
-    sp.walk_cap = 0;
-    sp.walk_diag = (uint32_t)ctx->walk_diag;
-    if (sp.impl) {
-      // units with position lists (round 6): every wave keeps the records of the reads it leaves to them in its own stretch
-      // of a context buffer and walks the lists behind its stream
-      bool lists = false;
-      for (uint32_t u = 0; u < sp.n_units; ++u) lists |= sp.unit[u].kind == 0u && sp.unit[u].pos_rows != nullptr;
-      if (lists) {
-        sp.walk_buf = ws_walk;
-        sp.walk_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(ctx->walk_cap, 0), (int64_t)kWalkCap);
-      }
-    }
-    if (n) HIP_TRY(mrg::launch_seed(sp, grid, stream));
-    ctx->last_launches[first] = 1;
-    for (uint32_t q = first; q < end; ++q) HIP_TRY(mark(q, q == first));
-    if (sp.idx_out) {
-      cur_list = next_list;
-      have_list = true;
-      list_fat = true;
-      prev_grid = grid;
-      prev_seg_cap = seg_cap;
-    }
-    return MRG_OK;
-  };
-  // a pass seed_kernel can take as (part of) a unit, and the size class of its library
-  auto seedable = [&](uint32_t i) {
-    if (!dict_batch || !ctx->seed_units || ctx->force_lds_mode >= 0 || !fusable(i)) return false;
-    const mrg_pass_cfg& c = passes[i];
-    const DevLib& l = ctx->libs[c.lib];
-    if (c.max_mm_seed == 0 && l.dict_slots && c.seed_len >= (int32_t)l.dict_key) return true;
-    return !l.host_seqs.empty() || l.sa16 != nullptr;
-  };
-  auto small_class = [&](uint32_t i) { return !ctx->libs[passes[i].lib].host_seqs.empty(); };
-
-  uint64_t long_plan = 0;  // the lengths the lane will take (long_mask is set while the lane's cascade runs)
-  bool long_plan_tried = false;
-  if (split && ctx->long_lane && words_per_read >= 2 && ctx->hint_max_len > 32) {
-    long_plan_tried = true;
-    // a dry run of the lane's launch plan (the loop below with dict_batch = true)
-    long_plan = (1ull << 31) - 1ull;
-    const bool saved = dict_batch;
-    dict_batch = true;
-    bool la = false;
-    for (uint32_t i = 0; i < n_pass && long_plan; ++i) {
-      if (!runs[i]) continue;
-      const mrg_pass_cfg& c = passes[i];
-      const DevLib& l = ctx->libs[c.lib];
-      // a seed launch: every length (the lane's first launch may be one when its pass can hold such reads: below)
-      if ((la || window_bits(c)) && seedable(i)) {
-        la = true;
-        continue;
-      }
-      la = true;
-      const bool pair_route = c.max_mm_seed == 2 && ctx->pair_seeds && l.pair_anchor && ctx->force_lds_mode < 0 && !c.poly_t &&
-                              c.seed_len >= (int32_t)(4u * l.pair_anchor) && ctx->pair_impl != 0;
-      if (pair_route) {
-        for (int L = 33; L <= 63; ++L) {
-          const int Lt = L - c.trim5 - c.trim3;
-          if (L >= c.min_len && L <= c.max_len && Lt > 32 && Lt <= (int)l.max_ref_len) long_plan &= ~(1ull << (L - 33));
-        }
-      } else {
-        long_plan &= ~window_bits(c);  // exact_dict_kernel, an FM kernel: only lengths its window keeps out
-      }
-    }
-    dict_batch = saved;
+    ctx->last_launches[i] = 0;
+    ctx->last_kbits_log2[i] = 0;
+    ctx->last_pair_anchor[i] = 0;
+    ctx->last_variant[i] = 0;
   }
   uint32_t split_grid = 0, split_cap = 0;
   if (split) {
@@ -1947,149 +2074,38 @@ int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
     sp.nmask_hi = (d_nmask && words_per_read >= 2) ? d_nmask + n : nullptr;
     sp.min_len = (uint32_t)ctx->split_min_len;
     split_grid = std::min<uint32_t>((uint32_t)ctx->n_cu * 2u, mrg::kMaxSegments);
-    split_cap = segment_capacity(split_grid, 1024, false);
+    split_cap = run.segment_capacity(split_grid, 1024, false);
     if (!split_cap) return fail(MRG_ERR_ARG, "mrg_cascade_run: survivor lists outgrew the workspace");
     sp.seg_cap = split_cap;
-    sp.idx_rest = idx[0];
-    sp.cnt_rest = counts;
-    sp.idx_short = idx[2];
-    sp.cnt_short = counts + 2 * mrg::kMaxSegments;
+    sp.idx_rest = run.idx[0];
+    sp.cnt_rest = run.counts;
+    sp.idx_short = run.idx[2];
+    sp.cnt_short = run.counts + 2 * mrg::kMaxSegments;
     HIP_TRY(mrg::launch_split(sp, split_grid, stream));
   }
   ctx->last_split = split ? 1u : 0u;
-  // (a split batch: each cascade records its own per-pass events: mrg_pass_stats.ms / .ms_rest)
   for (int chain = 0; chain < (split ? 2 : 1); ++chain) {
-  if (split) {
-    have_list = true;
-    prev_grid = split_grid;
-    prev_seg_cap = split_cap;
-    for (auto& b : stratum0_done) b = false;
-    list_fat = false;  // (split_kernel writes index lists)
-    out_init = false;
-    if (chain == 0) {  // long reads and reads with N: lists in buffers 0 / 1
-      pair0 = 0, pair1 = 1, cur_list = 0;
-      dict_batch = false;
-      evs = ctx->ev0;
-      ev_ix = ctx->ev0_ix;
-      ev_last = 0;
-      ev_ix[0] = 0;
-      if (timed) HIP_TRY(hipEventRecord(evs[0], stream));
-    } else {
-      evs = ctx->ev;
-      ev_ix = ctx->ev_ix;
-      ev_last = 0;
-      ev_ix[0] = 0;
-      if (timed) HIP_TRY(hipEventRecord(evs[0], stream));
-    }
-    if (chain == 1) {  // the one-word reads: parked in buffer 2, alternating with buffer 1
-      pair0 = 2, pair1 = 1, cur_list = 2;
-      dict_batch = true;
-      words_eff = 1u;
-      nmask_eff = nullptr;
-      long_mask = long_plan;  // (... and the reads of 33..63 nt the plan lets in)
-    }
-  }
-  bool launched_any = false;
-  for (uint32_t i = 0; i < n_pass;) {
-    if (!runs[i]) {
-      HIP_TRY(mark(i, false));
-      ++i;
-      continue;
-    }
-    // (a batch that may hold reads of 33..63 nt: the one-word lane reads a list from its first launch on, and only a seed
-    // launch can take such reads -- e.g. a batch of long reads only, whose first pass to run is the hairpin pass, len > 25)
-    const bool lane_first = split && chain == 1 && ctx->long_lane && words_per_read >= 2 && long_plan_tried && window_bits(passes[i]) != 0;
-    if ((launched_any || lane_first) && seedable(i)) {
-      std::vector<UnitPlan> plan;
-      const bool cls = small_class(i);
-      uint32_t j = i;
-      while (j < n_pass) {
-        if (!runs[j]) {
-          ++j;
-          continue;
-        }
-        if (!seedable(j) || small_class(j) != cls) break;
-        const mrg_pass_cfg& c = passes[j];
-        const bool k1 = c.max_mm_seed == 0 && ctx->libs[c.lib].dict_slots != nullptr && c.seed_len >= (int32_t)ctx->libs[c.lib].dict_key;
-        int join = -1;
-        if (!k1 && cls)  // small libraries searched with one policy: one unit over their concatenation
-          for (size_t u = 0; u < plan.size(); ++u) {
-            if (plan[u].kind != 0u || plan[u].members.size() >= mrg::kSeedMaxMembers) continue;
-            const mrg_pass_cfg& d = passes[plan[u].members[0]];
-            if (d.max_mm_seed == c.max_mm_seed && d.trim5 == c.trim5 && d.trim3 == c.trim3 && d.min_len == c.min_len &&
-                d.max_len == c.max_len && d.poly_t == c.poly_t) {
-              join = (int)u;
-              break;
-            }
-          }
-        if (join >= 0) {
-          plan[join].members.push_back(j);
-        } else {
-          if (plan.size() == mrg::kSeedMaxUnits) break;
-          plan.push_back(UnitPlan{k1 ? 1u : 0u, {j}});
-        }
-        ++j;
+    if (split) {
+      // split_kernel wrote index lists: the long reads and the reads with N in buffer 0 (alternating with 1), the one-word
+      // reads parked in buffer 2 (alternating with 1)
+      run.have_list = true;
+      run.list_fat = false;
+      run.out_init = false;
+      run.prev_grid = split_grid;
+      run.prev_seg_cap = split_cap;
+      run.pair0 = run.cur_list = chain == 0 ? 0 : 2;
+      run.pair1 = 1;
+      run.dict_batch = chain == 1;
+      if (chain == 1) {
+        run.words_eff = 1u;
+        run.nmask_eff = nullptr;
+        run.long_mask = long_plan;  // (... and the reads of 33..63 nt the plan lets in)
       }
-      // (passes skipped by the length hint at the end of the run stay with it: never the last pass)
-      if (ctx->stratum0_unit && j < n_pass && runs[j] && passes[j].max_mm_seed == 2 && !passes[j].poly_t &&
-          ctx->libs[passes[j].lib].dict_slots && passes[j].seed_len >= (int32_t)ctx->libs[passes[j].lib].dict_key &&
-          plan.size() < mrg::kSeedMaxUnits && ctx->pair_seeds && ctx->force_lds_mode < 0) {
-        UnitPlan s0{1u, {j}};
-        s0.stratum0 = true;
-        plan.push_back(s0);
-        stratum0_done[j] = true;
-      }
-      int rc = run_seed(plan, i, j, j == n_pass, cls);
-      if (rc != MRG_OK) return rc;
-      i = j;
-      continue;
+      // (each cascade records its own per-pass events: mrg_pass_stats.ms / .ms_rest)
+      HIP_TRY(run.begin_events(chain == 0 ? ctx->ev0 : ctx->ev, chain == 0 ? ctx->ev0_ix : ctx->ev_ix));
     }
-    uint32_t members[mrg::kMaxFused];
-    uint32_t n_sub = 0, j = i;
-    if (launched_any && fusable(i)) {
-      const bool cls = small_lib(i);
-      while (j < n_pass && n_sub < mrg::kMaxFused) {
-        if (!runs[j]) {
-          ++j;
-          continue;
-        }
-        if (!fusable(j)) break;
-        if (ctx->fuse != 2 && small_lib(j) != cls) break;
-        if (ctx->fuse == 3 && !cls) break;
-        members[n_sub++] = j++;
-      }
-      // passes skipped by the hint at the end of the run stay with the group (their events are
-      // recorded below); a trailing skipped pass is never the last pass of the cascade
-    }
-    if (n_sub >= 2) {
-      const bool ends = members[n_sub - 1] + 1 == n_pass;
-      // events of hint-skipped passes inside the group
-      int rc = run_fused(members, n_sub, ends);
-      if (rc != MRG_OK) return rc;
-      for (uint32_t q = i; q < j; ++q)
-        if (!runs[q]) HIP_TRY(mark(q, false));
-      i = j;
-    } else {
-      const int32_t kfull = passes[i].max_mm_seed + 1;
-      int rc;
-      const DevLib& l8 = ctx->libs[passes[i].lib];
-      if (passes[i].max_mm_seed == 2 && ctx->pair_seeds && l8.pair_anchor && ctx->force_lds_mode < 0 && !passes[i].poly_t &&
-          passes[i].seed_len >= (int32_t)(4u * l8.pair_anchor)) {
-        // anchor pairs for every read long enough to hold the four anchors, all strata of the
-        // pigeonhole search for the shorter ones: one launch (kernels.hip: stratum_kernel)
-        rc = run_single(i, 1, kfull, !stratum0_done[i], true, true);
-      } else if (passes[i].max_mm_seed == 2 && ctx->split_strata) {
-        // strata 1..2 on the incoming reads, stratum 3 on the compacted survivors (kernels.hpp)
-        rc = run_single(i, 1, 2, !stratum0_done[i], false);
-        if (rc == MRG_OK) rc = run_single(i, 3, 3, false, true);
-      } else {
-        rc = run_single(i, 1, kfull, !stratum0_done[i], true);
-      }
-      if (rc != MRG_OK) return rc;
-      ++i;
-    }
-    launched_any = true;
-  }
+    const int rc = run.issue(plans[chain]);
+    if (rc != MRG_OK) return rc;
   }
   ctx->pending_export_out = nullptr;
   if (d_pass_counts) {
@@ -2097,11 +2113,11 @@ int cascade_run_impl(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_r
       ctx->pending_export_out = d_pass_counts;  // (the tally launch behind this cascade copies them: mrg_tally_run*)
       ctx->pending_export_stream = stream;
     } else {
-      HIP_TRY(mrg::launch_export_pass_counts(stats, n_pass, d_pass_counts, stream));
+      HIP_TRY(mrg::launch_export_pass_counts(run.stats, n_pass, d_pass_counts, stream));
     }
   }
   ctx->last_stream = stream;
-  ctx->last_stats_dev = stats;
+  ctx->last_stats_dev = run.stats;
   ctx->last_n_pass = n_pass;
   ++ctx->run_id;
   // a length hint describes ONE batch: it never outlives the run it was set for
@@ -2197,28 +2213,11 @@ int mrg_cascade_run_long(mrg_ctx* ctx, const uint64_t* d_words, const uint64_t* 
     const DevLib& l = ctx->libs[c.lib];
     mrg::LongPass& q = host[i];
     std::memset(&q, 0, sizeof q);
-    q.blocks = l.blocks;
-    q.super = l.super;
-    q.text = l.text;
-    q.sa = l.sa;
-    q.ftab = l.ftab;
-    q.tabs = l.tabs;
+    fill_lib(q, l);
     if (!ctx->use_ftab || !l.ftab) q.tabs.k[0] = 0u;
-    q.seg_start = l.seg_start;
-    q.seg_ref = l.seg_ref;
-    q.seg_off = l.seg_off;
-    q.chunk_seg = l.chunk_seg;
-    q.n = l.n;
-    q.primary = l.primary;
     q.simple_segs = l.simple ? 1u : 0u;
-    q.seed_len = c.seed_len;
+    fill_policy(q, c);
     q.max_mm_seed = c.max_mm_seed;
-    q.max_mm_total = c.max_mm_total;
-    q.trim5 = c.trim5;
-    q.trim3 = c.trim3;
-    q.min_len = c.min_len;
-    q.max_len = c.max_len;
-    q.poly_t = c.poly_t;
   }
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t)stream_;
@@ -2565,21 +2564,10 @@ int fill_count_params(mrg_ctx* ctx, const char* who, const uint64_t* d_reads, ui
   const uint64_t lds = (uint64_t)l.nsup * 16;
   if (lds > 160 * 1024) return fail(MRG_ERR_ARG, "%s: library too large for one call (split it)", who);
   std::memset(p, 0, sizeof(*p));
-  p->blocks = l.blocks;
-  p->super = l.super;
-  p->text = l.text;
-  p->sa = l.sa;
+  fill_lib(*p, l);
   p->ctx = l.ctx;
-  p->ftab = l.ftab;
-  p->tabs = l.tabs;
   if (!ctx->use_ftab) p->tabs.k[0] = 0u;
-  p->n = l.n;
   p->nsup = l.nsup;
-  p->primary = l.primary;
-  p->seg_start = l.seg_start;
-  p->seg_ref = l.seg_ref;
-  p->seg_off = l.seg_off;
-  p->chunk_seg = l.chunk_seg;
   p->reads = d_reads;
   p->lens = d_lens;
   p->nmask = d_nmask;
