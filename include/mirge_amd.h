@@ -1137,6 +1137,73 @@ int mrg_write_precursors(const char *path, const mrg_index *const *parts, uint32
                          uint64_t n_rec, const uint32_t *rec_group, const uint32_t *rec_lo, const uint32_t *rec_hi,
                          const uint64_t *rec_off, const char *seq, uint64_t seq_len, uint64_t *written);
 
+/* Predict mode's screening of the folded precursor candidates (reference miRge2.0.py:626: utils/screen_precusor_candidates.py
+ * with classes/readPrecusor.py, prunedLength 15) around the two folds the caller runs (csrc/predict_screen.hip,
+ * csrc/predict_screen_write.cpp; the rule: tests/predict_screen_model.py).  Strings travel as offsets
+ * [n + 1] (uint64, ascending from 0 to the text's length) plus bytes; a record's sequence and structure share their offsets.
+ * Line i of the feature file owns records 2 i (precusor_1) and 2 i + 1 (precusor_2) and miRNA i (its stableClusterSeq,
+ * transcribed).  Candidates live in four slots a line: candidate c = 4 i + k.  Every DEVICE call synchronises and takes
+ * mrg_predict_screen_temp_bytes(n_cand) bytes of scratch; arrays that contradict each other are MRG_ERR_ARG.
+ *
+ *   mrg_predict_screen_candidates  d_line_group [n_lines]: the lines' groups; d_nb_flags / d_nb_up / d_nb_down [n_groups] as
+ *       mrg_predict_feature_neighbors left them (a `None` distance counts as 10000).  Not Good: the line's own two records,
+ *       its own miRNA.  Good, with up = 9 <= upstreamDistance <= 44 and down likewise: down only -- records 2 i + 1, 2 i + 2,
+ *       miRNAs (i, i + 1); both -- 2 i - 1 .. 2 i + 2, miRNAs (i, i - 1) for the first two and (i, i + 1) for the others; up
+ *       only -- 2 i - 1, 2 i, miRNAs (i, i - 1).  d_cand_n [n_lines] = 2 or 4; d_cand_rec [4 n_lines] (0xffffffff: unused
+ *       slot); d_cand_mir [8 n_lines] (0xffffffff: no second miRNA).  Where the reference dies of an IndexError (neither, or a
+ *       neighbour before the first or behind the last line): MRG_ERR_ARG naming the line.
+ *   mrg_predict_screen_prune  One wave per candidate: getPrunedPrecusor up to its fold.  d_status [n_cand]: 0 = None, 1 = cut,
+ *       2 = left to the caller (a record beyond 256 or a miRNA beyond 255 characters), 3 = unused slot; d_lo / d_hi: the slice
+ *       of the record (Python's slice semantics); d_pruned_off [n_cand + 1] and d_pruned (room for pruned_cap bytes): the
+ *       slices' bytes, compacted; *pruned_len = their sum.  MRG_ERR_ARG naming the candidate for brackets that do not balance
+ *       or an absent miRNA two or more longer than its record (the reference's IndexError).
+ *   mrg_predict_screen_features  One wave per candidate with d_status 1, from the pruned sequence and its new structure
+ *       (d_p_off [n_cand + 1], d_p_seq, d_p_str): d_feat [n_cand][16] int32 = state (0 the all-None row; 1 computed; 2 left
+ *       to the caller: beyond 256 characters, or 10 or more stems or hairpins), hairpinCount, bindingCount,
+ *       interiorLoopCount, the first miRNA's arm (0 loop, 1 arm5, 2 arm3, 3 unmatchedRegion), apicalLoopSize, its overlap and
+ *       distanceToLoop, the second miRNA's arm (-1: none), overlap and distance, stemLen, the UGU flag, the brackets in the
+ *       first miRNA's stretch, that stretch's length, the stems.  MRG_ERR_ARG naming the record for brackets that do not
+ *       balance or a hairpin loop under 3.
+ *   mrg_predict_screen_select  One lane per line: selcteOptimalPrecusor with `threshold` over the candidates of state 1 -- the
+ *       retained ones, otherwise all; the lowest d_rec_mfe [n_rec] of the candidate's record, ties to the lower slot.  d_best
+ *       [n_lines] = the slot or -1.  A row of state 2 is MRG_ERR_ARG: the caller fills those in first.
+ *   mrg_read_str_file  HOST: RNAfold's output, three lines a record, into *handle: sequence, structure (the third line's
+ *       first field) and the energy as the reference parses `(-12.30)` / `( -2.30)`, 0.0 where that fails.  MRG_ERR_ARG naming
+ *       both counts when the records are not `expected`.  mrg_str_file_copy copies out off [n_rec + 1], seq and structure
+ *       [text_len], mfe [n_rec]; mrg_str_file_free releases the handle.
+ *   mrg_write_pruned_fasta  HOST: `>c<k>` and string k for every k with keep[k] != 0.
+ *   mrg_write_screened_features  HOST: `<table>_features_updated_stableClusterSeq_15.tsv`: every line of the feature file
+ *       stripped as line.strip() does, a tab, and the chosen candidate's 14 columns (best [n_lines], feat [4 n_lines][16],
+ *       p_off [4 n_lines + 1] into p_seq / p_str, p_mfe [4 n_lines]) in the reference's format, or 14 x None.  Checked before
+ *       the file is opened.  Worker threads: MIRGE_AMD_TABLE_THREADS.
+ */
+int mrg_predict_screen_temp_bytes(uint64_t n_cand, uint64_t *bytes);
+int mrg_predict_screen_candidates(mrg_ctx *ctx, uint64_t n_lines, const uint32_t *d_line_group, uint64_t n_groups,
+                                  const uint8_t *d_nb_flags, const int64_t *d_nb_up, const int64_t *d_nb_down,
+                                  uint8_t *d_cand_n, uint32_t *d_cand_rec, uint32_t *d_cand_mir, void *d_tmp,
+                                  uint64_t tmp_bytes, void *stream);
+int mrg_predict_screen_prune(mrg_ctx *ctx, uint64_t n_cand, const uint32_t *d_cand_rec, const uint32_t *d_cand_mir,
+                             uint64_t n_rec, const uint64_t *d_rec_off, const char *d_seq, const char *d_str, uint64_t seq_len,
+                             uint64_t n_mir, const uint64_t *d_mir_off, const char *d_mir, uint64_t mir_len,
+                             int32_t pruned_length, uint8_t *d_status, uint32_t *d_lo, uint32_t *d_hi, uint64_t *d_pruned_off,
+                             char *d_pruned, uint64_t pruned_cap, uint64_t *pruned_len, void *d_tmp, uint64_t tmp_bytes,
+                             void *stream);
+int mrg_predict_screen_features(mrg_ctx *ctx, uint64_t n_cand, const uint8_t *d_status, const uint32_t *d_cand_mir,
+                                const uint64_t *d_p_off, const char *d_p_seq, const char *d_p_str, uint64_t p_len,
+                                uint64_t n_mir, const uint64_t *d_mir_off, const char *d_mir, uint64_t mir_len, int32_t *d_feat,
+                                void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_predict_screen_select(mrg_ctx *ctx, uint64_t n_lines, const uint8_t *d_cand_n, const uint32_t *d_cand_rec,
+                              uint64_t n_rec, const double *d_rec_mfe, const int32_t *d_feat, int32_t threshold,
+                              int32_t *d_best, void *d_tmp, uint64_t tmp_bytes, void *stream);
+int mrg_read_str_file(const char *path, uint64_t expected, uint64_t *n_rec, uint64_t *text_len, void **handle);
+int mrg_str_file_copy(void *handle, uint64_t *off, char *seq, char *structure, double *mfe);
+void mrg_str_file_free(void *handle);
+int mrg_write_pruned_fasta(const char *path, uint64_t n, const uint64_t *off, const char *seq, const uint8_t *keep,
+                           uint64_t *written);
+int mrg_write_screened_features(const char *features_path, const char *out_path, uint64_t n_lines, const int32_t *best,
+                                const int32_t *feat, const uint64_t *p_off, const char *p_seq, const char *p_str,
+                                const double *p_mfe, uint64_t *written);
+
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are

@@ -30,7 +30,10 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     `--novel-features` (implies `--novel-map`) builds that stage's two files on the GPU from the same arrays:
     `..._sorted_features.tsv` and `..._sorted_cluster.txt`, as the reference's generate_featureFiles writes them;
     `--novel-precursors` (implies `--novel-features`) cuts the two precursor windows of every line of that table out of the
-    resident genome on the GPU: `..._sorted_features_precusor.fa`, the file the reference feeds to RNAfold.
+    resident genome on the GPU: `..._sorted_features_precusor.fa`, the file the reference feeds to RNAfold;
+    `--novel-screen` (implies `--novel-precursors`; needs `-pr <dir>` holding RNAfold, or `--fold-cmd <executable>`) folds
+    that file once, picks and prunes the candidates on the GPU, folds the pruned ones once, and writes
+    `..._sorted_features_updated_stableClusterSeq_15.tsv`, the table the reference's SVM reads.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -48,7 +51,7 @@ def novel_stages(args):
     """(reads, clusters, trim, map): which of predict mode's stages the `--novel-*` options ask for; each implies the ones
     before it."""
     novel_map = bool(getattr(args, "novel_map", False)) or bool(getattr(args, "novel_features", False)) or \
-        bool(getattr(args, "novel_precursors", False))
+        bool(getattr(args, "novel_precursors", False)) or bool(getattr(args, "novel_screen", False))
     novel_trim = novel_map or bool(getattr(args, "novel_trim", False))
     novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
     novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
@@ -104,6 +107,15 @@ def build_parser():
     p.add_argument("--novel-precursors", dest="novel_precursors", action="store_true",
                    help="extension: --novel-features, then the precursor candidates of every feature line cut out of the genome "
                         "on the GPU (<table>_features_precusor.fa, as the reference's get_precursors writes it)")
+    p.add_argument("--novel-screen", dest="novel_screen", action="store_true",
+                   help="extension: --novel-precursors, then RNAfold over that file, the candidates picked and pruned on the GPU, "
+                        "RNAfold over the pruned ones, and their features and the choice on the GPU "
+                        "(<table>_features_updated_stableClusterSeq_15.tsv, as the reference's screen_precusor_candidates writes it); "
+                        "needs -pr or --fold-cmd")
+    p.add_argument("-pr", default=None, dest="rnafoldBinary", metavar="<dir>", help="the directory RNAfold is in (--novel-screen)")
+    p.add_argument("--fold-cmd", default=None, dest="fold_cmd", metavar="<executable>",
+                   help="extension: the fold command itself, started as `<executable> --noPS --noLP` with the FASTA on its "
+                        "standard input; overrides -pr")
     p.add_argument("-minl", default="16", dest="minLength", metavar="<int>")
     p.add_argument("-maxl", default="25", dest="maxLength", metavar="<int>")
     p.add_argument("-cc", default="2", dest="countCutoff", metavar="<int>")
@@ -230,6 +242,13 @@ def annotate_main(args, engine_factory=None, materialize=False):
         if rank == 0:
             print(msg, file=out)
         sys.exit(1)
+    novel_fold = None
+    if bool(getattr(args, "novel_screen", False)):   # before any GPU work: MAIN's check of -pr
+        from . import predict as _predict
+        try:
+            novel_fold = _predict.fold_command(_predict.resolve_fold_cmd(getattr(args, "rnafoldBinary", None), getattr(args, "fold_cmd", None)))
+        except ValueError as e:
+            novel_die(str(e))
     if novel_reads:
         try:
             novel_min, novel_max, novel_cc = int(args.minLength), int(args.maxLength), int(args.countCutoff)
@@ -564,7 +583,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
             if novel_trim:   # MAIN:557-562; a missing file is the reference's "no repeat table"
                 trim = (predict.load_repeats(predict.repeats_path(lib, sp), predict.genome_libraries(engine, novel_genome)[1]),
                         cluster_len_cutoff)
-            novel_precursors = bool(getattr(args, "novel_precursors", False))
+            novel_screen = novel_fold is not None
+            novel_precursors = novel_screen or bool(getattr(args, "novel_precursors", False))
             novel_features = novel_precursors or bool(getattr(args, "novel_features", False))
             for s, stem in enumerate(stems):
                 if stem in stems[s + 1:]:   # (a later sample wrote this stem's files)
@@ -577,7 +597,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
                 predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
                                               seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
-                                              remap=novel_map, features=novel_features, precursors=novel_precursors)
+                                              remap=novel_map, features=novel_features, precursors=novel_precursors,
+                                              screen=novel_screen, fold=novel_fold)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

@@ -32,6 +32,7 @@
 #include "predict_features.hpp"
 #include "predict_precursors.hpp"
 #include "predict_reads.hpp"
+#include "predict_screen.hpp"
 #include "prims.hpp"
 #include "sa_build.hpp"
 #include "tables.hpp"
@@ -3751,6 +3752,253 @@ int mrg_write_precursors(const char* path, const mrg_index* const* parts, uint32
     const mrg::PrecWriteArgs a{path, &ix, clusters ? &clusters->ix : nullptr, n_clusters, cl_entry, n_groups, group_cluster, n_rec, rec_group,
                                rec_lo, rec_hi, rec_off, seq, seq_len};
     mrg::write_precursors(a, written);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+// ------------------------------------------- predict mode: screening the folded candidates (csrc/predict_screen.hip)
+namespace {
+constexpr uint64_t kScreenMaxLines = (1ull << 28) - 1, kScreenMaxItems = (1ull << 31) - 1;
+// the screen calls' scratch: the stat words, the slices' lengths [n_cand + 1] and the scan's own
+struct ScreenScratch {
+  size_t len32, scan, total;
+  explicit ScreenScratch(uint64_t n_cand) {
+    len32 = up8(mrg::kScreenStatWords * sizeof(uint32_t));
+    scan = len32 + up8((size_t)(n_cand + 1) * sizeof(uint32_t));
+    total = scan + up8(mrg::prims::scan_temp_bytes(n_cand + 1));
+  }
+};
+int screen_scratch_ok(const char* fn, void* d_tmp, uint64_t tmp_bytes, uint64_t n_cand) {
+  if (!d_tmp || tmp_bytes < ScreenScratch(n_cand).total || ((uintptr_t)d_tmp & 7))
+    return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_screen_temp_bytes, unaligned or null", fn);
+  return MRG_OK;
+}
+// the first candidate of a state, for the message (n > 0)
+int screen_first_of(const uint8_t* d_state, size_t stride, uint64_t n, uint8_t what, hipStream_t st, uint64_t* first) {
+  std::vector<uint8_t> h((size_t)n * stride);
+  HIP_TRY(hipMemcpyAsync(h.data(), d_state, h.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *first = n;
+  for (uint64_t i = 0; i < n; ++i)
+    if (h[(size_t)i * stride] == what) {
+      *first = i;
+      break;
+    }
+  return MRG_OK;
+}
+int screen_read_stat(uint32_t* stat, uint32_t* h_stat, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, mrg::kScreenStatWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+}  // namespace
+
+int mrg_predict_screen_temp_bytes(uint64_t n_cand, uint64_t* bytes) {
+  const char* fn = "mrg_predict_screen_temp_bytes";
+  if (!bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_cand > 4 * kScreenMaxLines) return fail(MRG_ERR_ARG, "%s: %llu candidates; the limit is 2^30 - 4", fn, (unsigned long long)n_cand);
+  *bytes = ScreenScratch(n_cand).total;
+  return MRG_OK;
+}
+
+int mrg_predict_screen_candidates(mrg_ctx* ctx, uint64_t n_lines, const uint32_t* d_line_group, uint64_t n_groups, const uint8_t* d_nb_flags,
+                                  const int64_t* d_nb_up, const int64_t* d_nb_down, uint8_t* d_cand_n, uint32_t* d_cand_rec,
+                                  uint32_t* d_cand_mir, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_screen_candidates";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_lines > kScreenMaxLines || n_groups > kScreenMaxItems)
+    return fail(MRG_ERR_ARG, "%s: lines are limited to 2^28 - 1, groups to 2^31 - 1", fn);
+  if (int rc = screen_scratch_ok(fn, d_tmp, tmp_bytes, 0)) return rc;
+  if (n_lines == 0) return MRG_OK;
+  if (!d_line_group || !d_nb_flags || !d_nb_up || !d_nb_down || !d_cand_n || !d_cand_rec || !d_cand_mir) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = reinterpret_cast<uint32_t*>(d_tmp);
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kScreenStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::screen_candidates_launch((uint32_t)n_lines, d_line_group, (uint32_t)n_groups, d_nb_flags, d_nb_up, d_nb_down, d_cand_n, d_cand_rec,
+                                        d_cand_mir, stat, st));
+  uint32_t h_stat[mrg::kScreenStatWords] = {0};
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
+  if (h_stat[mrg::kScreenStatBadGroup]) return fail(MRG_ERR_ARG, "%s: a line names no group", fn);
+  if (h_stat[mrg::kScreenStatBadLine]) {
+    uint64_t first = 0;
+    if (int rc = screen_first_of(d_cand_n, 1, n_lines, 0, st, &first)) return rc;
+    return fail(MRG_ERR_ARG, "%s: line %llu is Good, but its distances name no neighbour, or one before the first or behind the last line "
+                "(the reference dies of an IndexError there)", fn, (unsigned long long)first);
+  }
+  return MRG_OK;
+}
+
+int mrg_predict_screen_prune(mrg_ctx* ctx, uint64_t n_cand, const uint32_t* d_cand_rec, const uint32_t* d_cand_mir, uint64_t n_rec,
+                             const uint64_t* d_rec_off, const char* d_seq, const char* d_str, uint64_t seq_len, uint64_t n_mir,
+                             const uint64_t* d_mir_off, const char* d_mir, uint64_t mir_len, int32_t pruned_length, uint8_t* d_status,
+                             uint32_t* d_lo, uint32_t* d_hi, uint64_t* d_pruned_off, char* d_pruned, uint64_t pruned_cap, uint64_t* pruned_len,
+                             void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_screen_prune";
+  if (!ctx || !pruned_len) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *pruned_len = 0;
+  if (n_cand > 4 * kScreenMaxLines || n_rec > kScreenMaxItems || n_mir > kScreenMaxItems)
+    return fail(MRG_ERR_ARG, "%s: candidates are limited to 2^30 - 4, records and miRNAs to 2^31 - 1", fn);
+  if (pruned_length < 0 || pruned_length > 1000) return fail(MRG_ERR_ARG, "%s: a pruned length of %d", fn, pruned_length);
+  if (int rc = screen_scratch_ok(fn, d_tmp, tmp_bytes, n_cand)) return rc;
+  if (!d_rec_off || !d_mir_off || !d_pruned_off) return fail(MRG_ERR_ARG, "%s: null offsets", fn);
+  if ((seq_len && (!d_seq || !d_str)) || (mir_len && !d_mir)) return fail(MRG_ERR_ARG, "%s: null text", fn);
+  if (n_cand && (!d_cand_rec || !d_cand_mir || !d_status || !d_lo || !d_hi)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const ScreenScratch sc(n_cand);
+  char* base = static_cast<char*>(d_tmp);
+  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
+  uint32_t* len32 = reinterpret_cast<uint32_t*>(base + sc.len32);
+  const mrg::ScreenBlob rec{(uint32_t)n_rec, d_rec_off, d_seq, d_str, seq_len}, mir{(uint32_t)n_mir, d_mir_off, d_mir, nullptr, mir_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kScreenStatWords * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(len32 + n_cand, 0, sizeof(uint32_t), st));
+  HIP_TRY(mrg::screen_check_offsets_launch(rec, stat, st));
+  HIP_TRY(mrg::screen_check_offsets_launch(mir, stat, st));
+  HIP_TRY(mrg::screen_check_cands_launch((uint32_t)n_cand, d_cand_rec, nullptr, d_cand_mir, (uint32_t)n_rec, (uint32_t)n_mir, stat, st));
+  uint32_t h_stat[mrg::kScreenStatWords] = {0};
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;   // (before a byte is read through them: the kernels trust the arrays)
+  if (h_stat[mrg::kScreenStatBadOffsets]) return fail(MRG_ERR_ARG, "%s: offsets that do not ascend from 0 to the length of their text", fn);
+  if (h_stat[mrg::kScreenStatBadCand]) return fail(MRG_ERR_ARG, "%s: a candidate names no record or no miRNA", fn);
+  HIP_TRY(mrg::screen_prune_launch((uint32_t)n_cand, d_cand_rec, d_cand_mir, rec, mir, pruned_length, d_status, d_lo, d_hi, len32, stat, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_pruned_off, n_cand + 1, base + sc.scan, st));
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_pruned_off + n_cand, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
+  if (h_stat[mrg::kScreenStatRefused]) {
+    uint64_t first = 0;
+    if (int rc = screen_first_of(d_status, 1, n_cand, mrg::kScreenRefused, st, &first)) return rc;
+    return fail(MRG_ERR_ARG, "%s: candidate %llu: a structure whose brackets do not balance, or an absent miRNA longer than the sequence "
+                "(the reference dies of an IndexError there)", fn, (unsigned long long)first);
+  }
+  if (total > pruned_cap || (total && !d_pruned))
+    return fail(MRG_ERR_ARG, "%s: %llu pruned bytes, room for %llu", fn, (unsigned long long)total, (unsigned long long)pruned_cap);
+  HIP_TRY(mrg::screen_copy_launch((uint32_t)n_cand, d_cand_rec, rec, d_status, d_lo, d_hi, d_pruned_off, d_pruned, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *pruned_len = total;
+  return MRG_OK;
+}
+
+int mrg_predict_screen_features(mrg_ctx* ctx, uint64_t n_cand, const uint8_t* d_status, const uint32_t* d_cand_mir, const uint64_t* d_p_off,
+                                const char* d_p_seq, const char* d_p_str, uint64_t p_len, uint64_t n_mir, const uint64_t* d_mir_off,
+                                const char* d_mir, uint64_t mir_len, int32_t* d_feat, void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_screen_features";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_cand > 4 * kScreenMaxLines || n_mir > kScreenMaxItems) return fail(MRG_ERR_ARG, "%s: candidates are limited to 2^30 - 4, miRNAs to 2^31 - 1", fn);
+  if (int rc = screen_scratch_ok(fn, d_tmp, tmp_bytes, n_cand)) return rc;
+  if (!d_p_off || !d_mir_off) return fail(MRG_ERR_ARG, "%s: null offsets", fn);
+  if ((p_len && (!d_p_seq || !d_p_str)) || (mir_len && !d_mir)) return fail(MRG_ERR_ARG, "%s: null text", fn);
+  if (n_cand && (!d_status || !d_cand_mir || !d_feat)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = reinterpret_cast<uint32_t*>(d_tmp);
+  const mrg::ScreenBlob text{(uint32_t)n_cand, d_p_off, d_p_seq, d_p_str, p_len}, mir{(uint32_t)n_mir, d_mir_off, d_mir, nullptr, mir_len};
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kScreenStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::screen_check_offsets_launch(text, stat, st));
+  HIP_TRY(mrg::screen_check_offsets_launch(mir, stat, st));
+  HIP_TRY(mrg::screen_check_cands_launch((uint32_t)n_cand, nullptr, d_status, d_cand_mir, 0u, (uint32_t)n_mir, stat, st));
+  uint32_t h_stat[mrg::kScreenStatWords] = {0};
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
+  if (h_stat[mrg::kScreenStatBadOffsets]) return fail(MRG_ERR_ARG, "%s: offsets that do not ascend from 0 to the length of their text", fn);
+  if (h_stat[mrg::kScreenStatBadCand]) return fail(MRG_ERR_ARG, "%s: a candidate names no miRNA", fn);
+  HIP_TRY(mrg::screen_features_launch((uint32_t)n_cand, d_status, d_cand_mir, text, mir, d_feat, stat, st));
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
+  if (h_stat[mrg::kScreenStatRefused]) {
+    uint64_t first = 0;
+    if (int rc = screen_first_of(reinterpret_cast<const uint8_t*>(d_feat), mrg::kScreenFeatWords * sizeof(int32_t), n_cand, mrg::kScreenRefused, st,
+                                 &first))
+      return rc;
+    return fail(MRG_ERR_ARG, "%s: record %llu of the pruned structures: brackets that do not balance, or a hairpin loop under 3", fn,
+                (unsigned long long)first);
+  }
+  return MRG_OK;
+}
+
+int mrg_predict_screen_select(mrg_ctx* ctx, uint64_t n_lines, const uint8_t* d_cand_n, const uint32_t* d_cand_rec, uint64_t n_rec,
+                              const double* d_rec_mfe, const int32_t* d_feat, int32_t threshold, int32_t* d_best, void* d_tmp,
+                              uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_screen_select";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_lines > kScreenMaxLines || n_rec > kScreenMaxItems) return fail(MRG_ERR_ARG, "%s: lines are limited to 2^28 - 1, records to 2^31 - 1", fn);
+  if (int rc = screen_scratch_ok(fn, d_tmp, tmp_bytes, 0)) return rc;
+  if (n_lines == 0) return MRG_OK;
+  if (n_rec != 2 * n_lines) return fail(MRG_ERR_ARG, "%s: %llu records for %llu lines; every line has two", fn, (unsigned long long)n_rec, (unsigned long long)n_lines);
+  if (!d_cand_n || !d_cand_rec || !d_rec_mfe || !d_feat || !d_best) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* stat = reinterpret_cast<uint32_t*>(d_tmp);
+  HIP_TRY(hipMemsetAsync(stat, 0, mrg::kScreenStatWords * sizeof(uint32_t), st));
+  HIP_TRY(mrg::screen_select_launch((uint32_t)n_lines, d_cand_n, d_cand_rec, (uint32_t)n_rec, d_rec_mfe, d_feat, threshold, d_best, stat, st));
+  uint32_t h_stat[mrg::kScreenStatWords] = {0};
+  if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
+  if (h_stat[mrg::kScreenStatBadLine]) return fail(MRG_ERR_ARG, "%s: a line with neither two nor four candidates", fn);
+  if (h_stat[mrg::kScreenStatBadCand])
+    return fail(MRG_ERR_ARG, "%s: a candidate of no record, or a feature row left to the host and not filled in", fn);
+  return MRG_OK;
+}
+
+int mrg_read_str_file(const char* path, uint64_t expected, uint64_t* n_rec, uint64_t* text_len, void** handle) {
+  const char* fn = "mrg_read_str_file";
+  if (!path || !n_rec || !text_len || !handle) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *handle = nullptr;
+  *n_rec = *text_len = 0;
+  try {
+    std::unique_ptr<mrg::StrRecords> r(new mrg::StrRecords);
+    mrg::read_str_file(path, expected, r.get());
+    *n_rec = r->mfe.size();
+    *text_len = r->seq.size();
+    *handle = r.release();
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+int mrg_str_file_copy(void* handle, uint64_t* off, char* seq, char* structure, double* mfe) {
+  const char* fn = "mrg_str_file_copy";
+  if (!handle || !off || !mfe) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  const mrg::StrRecords* r = static_cast<const mrg::StrRecords*>(handle);
+  if (r->seq.size() && (!seq || !structure)) return fail(MRG_ERR_ARG, "%s: null text buffers", fn);
+  std::memcpy(off, r->off.data(), r->off.size() * sizeof(uint64_t));
+  if (r->seq.size()) {
+    std::memcpy(seq, r->seq.data(), r->seq.size());
+    std::memcpy(structure, r->structure.data(), r->structure.size());
+  }
+  if (r->mfe.size()) std::memcpy(mfe, r->mfe.data(), r->mfe.size() * sizeof(double));
+  return MRG_OK;
+}
+
+void mrg_str_file_free(void* handle) { delete static_cast<mrg::StrRecords*>(handle); }
+
+int mrg_write_pruned_fasta(const char* path, uint64_t n, const uint64_t* off, const char* seq, const uint8_t* keep, uint64_t* written) {
+  const char* fn = "mrg_write_pruned_fasta";
+  if (!path || !off || !written || (n && !keep)) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *written = 0;
+  try {
+    *written = mrg::write_pruned_fasta(path, n, off, seq, keep);
+    return MRG_OK;
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
+int mrg_write_screened_features(const char* features_path, const char* out_path, uint64_t n_lines, const int32_t* best, const int32_t* feat,
+                                const uint64_t* p_off, const char* p_seq, const char* p_str, const double* p_mfe, uint64_t* written) {
+  const char* fn = "mrg_write_screened_features";
+  if (!features_path || !out_path || !written || !p_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *written = 0;
+  if (n_lines && (!best || !feat || !p_mfe)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  try {
+    const mrg::ScreenWriteArgs a{features_path, out_path, n_lines, best, feat, p_off, p_seq, p_str, p_mfe};
+    *written = mrg::write_screened_features(a);
     return MRG_OK;
   } catch (const std::invalid_argument& e) {
     return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());

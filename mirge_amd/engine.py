@@ -1642,6 +1642,125 @@ class Engine:
             timings.update(device_ms=out["device_ms"], download_ms=out["download_ms"])
         return out
 
+    # ---- predict mode: the screening of the folded precursor candidates (csrc/predict_screen.hip)
+    def _screen_dev(self, x, np_dtype, torch_dtype, what):
+        """A device tensor of torch_dtype as it is; a host array (or bytes) uploaded with np_dtype's bits."""
+        torch = _torch()
+        if torch.is_tensor(x):
+            return self._expect(x, torch_dtype, what).contiguous()
+        if isinstance(x, (bytes, bytearray)):
+            x = np.frombuffer(bytes(x), dtype=np.uint8)
+        a = np.array(x, dtype=np_dtype)   # (a copy: torch wants writable memory)
+        signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype)
+        if a.size == 0:
+            return torch.zeros(1, dtype=torch_dtype, device=self.device)[:0]
+        return torch.from_numpy(a.view(signed) if signed else a).to(self.device)
+
+    def _screen_blob(self, off, text, what, text2=None):
+        """(offsets tensor, text tensor(s), n, length) of a list of strings given as offsets [n + 1] plus bytes."""
+        torch = _torch()
+        off = self._screen_dev(off, np.uint64, torch.int64, what + ": offsets")
+        if off.numel() < 1:
+            raise ValueError("%s: offsets [n + 1] must hold at least the closing one" % what)
+        texts = [self._screen_dev(t, np.uint8, torch.uint8, what + ": text") for t in ((text,) if text2 is None else (text, text2))]
+        if len(texts) == 2 and texts[0].numel() != texts[1].numel():
+            raise ValueError("%s: the sequences' and the structures' bytes must be equally many" % what)
+        return off, texts, int(off.numel()) - 1, int(texts[0].numel())
+
+    def _screen_tmp(self, n_cand):
+        need = C.c_uint64()
+        check(self._lib.mrg_predict_screen_temp_bytes(int(n_cand), C.byref(need)))
+        return _torch().empty(max(int(need.value), 64), dtype=_torch().uint8, device=self.device)
+
+    @staticmethod
+    def _p(t):
+        return t.data_ptr() if t.numel() else None
+
+    def predict_screen_candidates(self, line_group, nb_flags, nb_up, nb_down):
+        """mrg_predict_screen_candidates (screen_precusor_candidates.py:224-285): every feature line's candidate records and
+        their miRNAs.  line_group [n_lines]; nb_flags, nb_up, nb_down [n_groups] as Engine.predict_features leaves them (host
+        arrays or device tensors).  Returns device tensors cand_n [n_lines], cand_rec [4 n_lines] and cand_mir [8 n_lines]
+        (-1 = unused slot / no second miRNA).  MirgeAmdError naming the line where the reference dies."""
+        torch = _torch()
+        lg = self._dev_u32(line_group, "predict_screen_candidates: line_group")
+        flags = self._screen_dev(nb_flags, np.uint8, torch.uint8, "predict_screen_candidates: nb_flags")
+        up = self._screen_dev(nb_up, np.int64, torch.int64, "predict_screen_candidates: nb_up")
+        down = self._screen_dev(nb_down, np.int64, torch.int64, "predict_screen_candidates: nb_down")
+        n, G = int(lg.numel()), int(flags.numel())
+        if up.numel() != G or down.numel() != G:
+            raise ValueError("predict_screen_candidates: nb_flags, nb_up and nb_down must hold one entry a group")
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        cand_n, cand_rec, cand_mir = e(n, torch.uint8), e(4 * n, torch.int32), e(8 * n, torch.int32)
+        tmp = self._screen_tmp(0)
+        p = self._p
+        check(self._lib.mrg_predict_screen_candidates(self._h, n, p(lg), G, p(flags), p(up), p(down), p(cand_n), p(cand_rec), p(cand_mir),
+                                                      tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return dict(cand_n=cand_n, cand_rec=cand_rec, cand_mir=cand_mir)
+
+    def predict_screen_prune(self, cand_rec, cand_mir, rec_off, seq, structure, mir_off, mir, pruned_length=15):
+        """mrg_predict_screen_prune: getPrunedPrecusor up to its fold.  cand_rec [n_cand] / cand_mir [2 n_cand] as
+        predict_screen_candidates returns them; records and miRNAs as offsets [n + 1] plus bytes.  Returns host arrays: status
+        (0 None, 1 cut, 2 left to the host, 3 unused slot), lo, hi (the slice of the record), pruned_off [n_cand + 1], pruned."""
+        torch = _torch()
+        rec = self._dev_u32(cand_rec, "predict_screen_prune: cand_rec")
+        cm = self._dev_u32(cand_mir, "predict_screen_prune: cand_mir")
+        n = int(rec.numel())
+        if cm.numel() != 2 * n:
+            raise ValueError("predict_screen_prune: cand_mir must hold two entries a candidate")
+        roff, (d_seq, d_str), n_rec, seq_len = self._screen_blob(rec_off, seq, "predict_screen_prune: records", structure)
+        moff, (d_mir,), n_mir, mir_len = self._screen_blob(mir_off, mir, "predict_screen_prune: miRNAs")
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        status, lo, hi, poff = e(n, torch.uint8), e(n, torch.int32), e(n, torch.int32), e(n + 1, torch.int64)
+        cap = n * 256   # (a slice the kernel cuts comes from a record of at most 256 characters)
+        pruned = e(cap, torch.uint8)
+        tmp = self._screen_tmp(n)
+        total = C.c_uint64(0)
+        p = self._p
+        check(self._lib.mrg_predict_screen_prune(
+            self._h, n, p(rec), p(cm), n_rec, p(roff), p(d_seq), p(d_str), seq_len, n_mir, p(moff), p(d_mir), mir_len, int(pruned_length),
+            p(status), p(lo), p(hi), p(poff), p(pruned), cap, C.byref(total), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        u32 = lambda t: t.cpu().numpy().view(np.uint32)
+        return dict(status=status.cpu().numpy(), lo=u32(lo), hi=u32(hi), pruned_off=poff.cpu().numpy().view(np.uint64),
+                    pruned=pruned[:int(total.value)].cpu().numpy().tobytes())
+
+    def predict_screen_features(self, status, cand_mir, p_off, p_seq, p_str, mir_off, mir):
+        """mrg_predict_screen_features: featuresInPrecusor and its two companions for every candidate with status 1, from its
+        pruned sequence and new structure (p_off [n_cand + 1], p_seq, p_str).  Returns int32 [n_cand, 16] on the host
+        (include/mirge_amd.h names the words; word 0 = 2: left to the host)."""
+        torch = _torch()
+        st = self._screen_dev(status, np.uint8, torch.uint8, "predict_screen_features: status")
+        cm = self._dev_u32(cand_mir, "predict_screen_features: cand_mir")
+        n = int(st.numel())
+        poff, (d_seq, d_str), n_p, p_len = self._screen_blob(p_off, p_seq, "predict_screen_features: pruned", p_str)
+        moff, (d_mir,), n_mir, mir_len = self._screen_blob(mir_off, mir, "predict_screen_features: miRNAs")
+        if cm.numel() != 2 * n or n_p != n:
+            raise ValueError("predict_screen_features: status [n], cand_mir [2 n] and p_off [n + 1] must match")
+        feat = torch.empty(max(16 * n, 1), dtype=torch.int32, device=self.device)[:16 * n]
+        tmp = self._screen_tmp(n)
+        p = self._p
+        check(self._lib.mrg_predict_screen_features(self._h, n, p(st), p(cm), p(poff), p(d_seq), p(d_str), p_len, n_mir, p(moff), p(d_mir),
+                                                    mir_len, p(feat), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return feat.cpu().numpy().reshape(n, 16)
+
+    def predict_screen_select(self, cand_n, cand_rec, rec_mfe, feat, threshold=15):
+        """mrg_predict_screen_select: selcteOptimalPrecusor per line over feat [4 n_lines, 16] (the host's rows filled in) by
+        the records' original energies rec_mfe [2 n_lines].  Returns best (int32 [n_lines], -1 = None) on the host."""
+        torch = _torch()
+        cn = self._screen_dev(cand_n, np.uint8, torch.uint8, "predict_screen_select: cand_n")
+        rec = self._dev_u32(cand_rec, "predict_screen_select: cand_rec")
+        mfe = self._screen_dev(rec_mfe, np.float64, torch.float64, "predict_screen_select: rec_mfe")
+        ft = self._screen_dev(np.asarray(feat).reshape(-1) if not torch.is_tensor(feat) else feat.reshape(-1), np.int32, torch.int32,
+                              "predict_screen_select: feat")
+        n = int(cn.numel())
+        if rec.numel() != 4 * n or ft.numel() != 64 * n:
+            raise ValueError("predict_screen_select: cand_n [n], cand_rec [4 n] and feat [4 n, 16] must match")
+        best = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)[:n]
+        tmp = self._screen_tmp(0)
+        p = self._p
+        check(self._lib.mrg_predict_screen_select(self._h, n, p(cn), p(rec), int(mfe.numel()), p(mfe), p(ft), int(threshold), p(best),
+                                                  tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
+        return best.cpu().numpy()
+
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
         mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask

@@ -650,6 +650,291 @@ def rename_str_file(fasta, str_tmp, str_out):
     return n
 
 
+def screen_precursors(engine, features_result, precursors_result, fold, out_stem, pruned_length=15, threads=None, timings=None):
+    """The reference's miRge2.0.py:610-626 (RNAfold, renameStrFile, screen_precusor_candidates) from the arrays, with two
+    fold calls a sample.  features_result / precursors_result: what cluster_features (nb_flags, nb_up, nb_down) and
+    cluster_precursors (rec_group, records) returned; fold: a callable (fasta_path, str_path), or RNAfold's path.
+    Writes `_features_precusor_tmp.str`, `_features_precusor.str`, `_features_pruned_<length>.fa` / `.str` and
+    `<table>_features_updated_stableClusterSeq_<length>.tsv`; candidates beyond the kernels' limits go through host_prune /
+    host_screen_features.  Returns a dict: lines, candidates, pruned (folded again), host_candidates, folds, best, path.
+    timings gets fold1_s, fold2_s, parse_s, device_s (the device calls with their transfers), host_s and write_s."""
+    import time
+    if isinstance(fold, (str, bytes, os.PathLike)):
+        fold = fold_command(os.fspath(fold))
+    stem = out_stem + REMAP_SUFFIX[:-4]
+    features_path, fasta = stem + FEATURES_SUFFIX, stem + PRECURSOR_SUFFIX
+    out_path = stem + "_features_updated_stableClusterSeq_%d.tsv" % int(pruned_length)
+    t = dict(fold1_s=0.0, fold2_s=0.0, parse_s=0.0, device_s=0.0, host_s=0.0, write_s=0.0)
+    clock = time.perf_counter
+    n_rec = int(precursors_result["records"])
+    n = n_rec // 2
+    if n == 0:   # (the feature file is its header: nothing to fold)
+        write_screened_features(features_path, out_path, np.zeros(0, np.int32), np.zeros((0, 16), np.int32), np.zeros(1, np.uint64), b"", b"",
+                                np.zeros(0), threads)
+        if timings is not None:
+            timings.update(t)
+        return dict(lines=0, candidates=0, pruned=0, host_candidates=0, folds=0, best=np.zeros(0, np.int32), path=out_path)
+    t0 = clock()
+    fold(fasta, stem + "_features_precusor_tmp.str")
+    t["fold1_s"] = clock() - t0
+    t0 = clock()
+    rename_str_file(fasta, stem + "_features_precusor_tmp.str", stem + "_features_precusor.str")
+    rec_off, rec_seq, rec_str, rec_mfe = read_str_file(stem + "_features_precusor.str", n_rec)
+    with open(features_path) as fh:
+        rows = fh.read().split("\n")
+    col = rows[0].strip().split("\t").index("stableClusterSeq")
+    mirnas = [r.strip().split("\t")[col].replace("T", "U").encode("ascii") for r in rows[1:] if r != ""]
+    if len(mirnas) != n:
+        raise ValueError("screen_precursors: %d feature lines, %d precursor records" % (len(mirnas), n_rec))
+    mir_off = np.zeros(n + 1, np.uint64)
+    mir_off[1:] = np.cumsum([len(m) for m in mirnas])
+    mir = b"".join(mirnas)
+    t["parse_s"] = clock() - t0
+    t0 = clock()
+    line_group = np.ascontiguousarray(precursors_result["rec_group"][0::2], dtype=np.uint32)
+    cands = engine.predict_screen_candidates(line_group, features_result["nb_flags"], features_result["nb_up"], features_result["nb_down"])
+    pr = engine.predict_screen_prune(cands["cand_rec"], cands["cand_mir"], rec_off, rec_seq, rec_str, mir_off, mir, pruned_length)
+    cand_rec = cands["cand_rec"].cpu().numpy().view(np.uint32)
+    cand_mir = cands["cand_mir"].cpu().numpy().view(np.uint32).reshape(-1, 2)
+    t["device_s"] += clock() - t0
+    status, p_off, p_seq = pr["status"].copy(), pr["pruned_off"], pr["pruned"]
+    text = lambda blob, off, k: blob[int(off[k]):int(off[k + 1])].decode("ascii")
+    mirnas_of = lambda c: [text(mir, mir_off, int(m)) for m in cand_mir[c] if m != 0xffffffff]
+    todo = np.flatnonzero(status == 2)
+    host_candidates = set(int(c) for c in todo)
+    if todo.size:   # the pruned bytes again, with the host's slices in their places
+        t0 = clock()
+        parts = [p_seq[int(p_off[c]):int(p_off[c + 1])] for c in range(4 * n)]
+        for c in todo:
+            r = int(cand_rec[c])
+            cut = host_prune(text(rec_seq, rec_off, r), text(rec_str, rec_off, r), mirnas_of(c), pruned_length)
+            status[c] = 0 if cut is None else 1
+            if cut is not None:
+                parts[c] = rec_seq[int(rec_off[r]) + cut[0]:int(rec_off[r]) + cut[1]]
+        p_off = np.zeros(4 * n + 1, np.uint64)
+        p_off[1:] = np.cumsum([len(p) for p in parts])
+        p_seq = b"".join(parts)
+        t["host_s"] += clock() - t0
+    keep = (status == 1) & (np.diff(p_off.astype(np.int64)) > 0)   # (an empty slice folds to nothing: the all-None row)
+    pruned_fa = stem + "_features_pruned_%d.fa" % int(pruned_length)
+    n_pruned = write_pruned_fasta(pruned_fa, p_off, p_seq, keep)
+    t0 = clock()
+    fold(pruned_fa, pruned_fa[:-3] + ".str")
+    t["fold2_s"] = clock() - t0
+    t0 = clock()
+    f_off, f_seq, p_str, f_mfe = read_str_file(pruned_fa[:-3] + ".str", n_pruned)
+    if f_seq != p_seq:
+        raise ValueError("screen_precursors: %s does not hold the sequences of %s" % (pruned_fa[:-3] + ".str", pruned_fa))
+    p_mfe = np.zeros(4 * n, np.float64)
+    p_mfe[keep] = f_mfe
+    t["parse_s"] += clock() - t0
+    t0 = clock()
+    feat = engine.predict_screen_features(keep.astype(np.uint8), cands["cand_mir"], p_off, p_seq, p_str, mir_off, mir)
+    t["device_s"] += clock() - t0
+    t0 = clock()
+    for c in np.flatnonzero(feat[:, 0] == 2):
+        host_candidates.add(int(c))
+        row = host_screen_features(text(p_seq, p_off, c), text(p_str, p_off, c), mirnas_of(c))
+        feat[c] = 0 if row is None else row
+    t["host_s"] += clock() - t0
+    t0 = clock()
+    best = engine.predict_screen_select(cands["cand_n"], cands["cand_rec"], rec_mfe, feat, 19 - 1 - 3)
+    t["device_s"] += clock() - t0
+    t0 = clock()
+    lines = write_screened_features(features_path, out_path, best, feat, p_off, p_seq, p_str, p_mfe, threads)
+    t["write_s"] = clock() - t0
+    if timings is not None:
+        timings.update(t, host_candidates=len(host_candidates))
+    return dict(lines=lines, candidates=int((status != 3).sum()), pruned=n_pruned, host_candidates=len(host_candidates), folds=2, best=best,
+                path=out_path)
+
+
+def fold_command(cmd):
+    """The default `fold` of screen_precursors: a callable (fasta_path, str_path) that starts `cmd --noPS --noLP` once,
+    without a shell, the FASTA on its standard input and the answer written to str_path."""
+    import subprocess
+
+    def fold(fasta_path, str_path):
+        with open(fasta_path, "rb") as src, open(str_path, "wb") as dst:
+            done = subprocess.run([cmd, "--noPS", "--noLP"], stdin=src, stdout=dst)
+        if done.returncode != 0:
+            raise OSError("%s --noPS --noLP left with status %d" % (cmd, done.returncode))
+    return fold
+
+
+def resolve_fold_cmd(rnafold_dir=None, fold_cmd=None):
+    """The executable --novel-screen folds with: fold_cmd, else <rnafold_dir>/RNAfold (the reference's -pr).  ValueError
+    with the reference's message when neither names an executable file."""
+    cmd = fold_cmd if fold_cmd else (os.path.join(rnafold_dir, "RNAfold") if rnafold_dir else None)
+    if cmd and os.path.isfile(cmd) and os.access(cmd, os.X_OK):
+        return os.path.abspath(cmd)
+    raise ValueError("RNAfold can't be found in %s. Please check it." % (os.path.dirname(cmd) if fold_cmd else rnafold_dir))
+
+
+def read_str_file(path, expected):
+    """mrg_read_str_file: the records of an RNAfold output as arrays -- (off uint64 [n + 1], seq bytes, structure bytes, mfe
+    float64 [n]).  MirgeAmdError naming both counts when the file does not hold `expected` records."""
+    from . import _native
+    lib = _native.load()
+    n, length, h = C.c_uint64(), C.c_uint64(), C.c_void_p()
+    _native.check(lib.mrg_read_str_file(os.fsencode(path), int(expected), C.byref(n), C.byref(length), C.byref(h)))
+    try:
+        off, mfe = np.zeros(n.value + 1, np.uint64), np.zeros(n.value, np.float64)
+        seq, structure = np.zeros(max(length.value, 1), np.uint8), np.zeros(max(length.value, 1), np.uint8)
+        _native.check(lib.mrg_str_file_copy(h, off.ctypes.data, seq.ctypes.data, structure.ctypes.data, mfe.ctypes.data))
+    finally:
+        lib.mrg_str_file_free(h)
+    return off, seq[:length.value].tobytes(), structure[:length.value].tobytes(), mfe
+
+
+def write_pruned_fasta(path, off, seq, keep):
+    """mrg_write_pruned_fasta: `>c<k>` and string k (bytes [off[k], off[k + 1]) of seq) for every k with keep[k]."""
+    from . import _native
+    lib = _native.load()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    buf = np.frombuffer(bytes(seq), dtype=np.uint8)
+    if off.shape[0] != keep.shape[0] + 1 or int(off[-1]) != buf.shape[0]:
+        raise ValueError("write_pruned_fasta: off [n + 1] must close at the sequence bytes and keep hold n flags")
+    written = C.c_uint64()
+    _native.check(lib.mrg_write_pruned_fasta(os.fsencode(path), int(keep.shape[0]), off.ctypes.data, _ptr(buf), _ptr(keep), C.byref(written)))
+    return int(written.value)
+
+
+def write_screened_features(features_path, out_path, best, feat, p_off, p_seq, p_str, p_mfe, threads=None):
+    """mrg_write_screened_features: the feature file's lines, each with the 14 columns of its chosen candidate.  best [n],
+    feat [4 n, 16], p_off [4 n + 1] into p_seq / p_str, p_mfe [4 n].  Returns the lines written."""
+    from . import _native
+    lib = _native.load()
+    best = np.ascontiguousarray(best, dtype=np.int32)
+    feat = np.ascontiguousarray(feat, dtype=np.int32).reshape(-1)
+    p_off = np.ascontiguousarray(p_off, dtype=np.uint64)
+    p_mfe = np.ascontiguousarray(p_mfe, dtype=np.float64)
+    seq, structure = (np.frombuffer(bytes(b), dtype=np.uint8) for b in (p_seq, p_str))
+    n = int(best.shape[0])
+    if feat.shape[0] != 64 * n or p_off.shape[0] != 4 * n + 1 or p_mfe.shape[0] != 4 * n or int(p_off[-1]) != seq.shape[0] or \
+            seq.shape != structure.shape:
+        raise ValueError("write_screened_features: best [n], feat [4 n, 16], p_off [4 n + 1] closing at p_seq and p_str, p_mfe [4 n] must match")
+    written = C.c_uint64()
+    with _writer_threads(threads):
+        _native.check(lib.mrg_write_screened_features(os.fsencode(features_path), os.fsencode(out_path), n, _ptr(best), _ptr(feat),
+                                                      p_off.ctypes.data, _ptr(seq), _ptr(structure), _ptr(p_mfe), C.byref(written)))
+    return int(written.value)
+
+
+def _partners(structure):
+    """{position: partner} of a dot-bracket structure; ValueError where the brackets do not balance."""
+    open_at, pairs = [], {}
+    for x, ch in enumerate(structure):
+        if ch == "(":
+            open_at.append(x)
+        elif ch == ")":
+            if not open_at:
+                raise ValueError("the structure's brackets do not balance")
+            y = open_at.pop()
+            pairs[x], pairs[y] = y, x
+    if open_at:
+        raise ValueError("the structure's brackets do not balance")
+    return pairs
+
+
+def _arm(stretch):
+    """checkArm over the miRNA's stretch of the structure: 0 loop, 1 arm5, 2 arm3, 3 unmatchedRegion."""
+    first, last = stretch.find("("), stretch.rfind(")")
+    if first >= 0 and last > first:
+        return 0
+    if first >= 0:
+        return 1 if stretch.count("(") >= stretch.count(")") else 2
+    return 2 if last >= 0 else 3
+
+
+def host_prune(seq, structure, mirnas, pruned_length=15):
+    """The host's getPrunedPrecusor up to the fold, for the candidates the kernels leave (beyond 256 characters): the slice
+    (lo, hi) of the record with 0 <= lo <= hi <= len, or None where pairing_partner gives None."""
+    chosen = mirnas[0] if len(mirnas) == 1 or seq.find(mirnas[0]) == 20 else mirnas[1]
+    start = seq.find(chosen)
+    end = start + len(chosen)
+    pairs = _partners(structure)
+    if _arm(structure[start:end]) == 1:
+        at = structure.index("(", start, end)
+        cut = slice(start - pruned_length, min(at - start + pairs[at], len(seq) - 1) + 1 + pruned_length)
+    else:
+        if end - 1 >= len(structure):
+            raise ValueError("an absent miRNA longer than the sequence: the reference dies of an IndexError")
+        at = structure.rfind(")", 0, max(end, 0))
+        if at < 0:
+            return None
+        cut = slice(max(pairs[at] - (end - 1 - at), 0) - pruned_length, end + pruned_length)
+    lo, hi, _ = cut.indices(len(seq))
+    return lo, max(lo, hi)
+
+
+def host_screen_features(seq, structure, mirnas):
+    """The host's featuresInPrecusor / percentageOfPairedInMiRNA / bindingsInMiRNA for the candidates the kernels leave:
+    the 16 words of a feature row (state 1), or None for the all-None row.  Every position gets its element's letter and
+    the LAST character of the element's number, as the reference's to_element_string does: from ten stems (or hairpins) on
+    two elements share a key, their adjacent runs merge and stemLen takes one maximum for both."""
+    if "(" not in structure or ")" not in structure:
+        return None
+    pairs = _partners(structure)
+    n = len(structure)
+    label = [""] * n
+    n_hairpin = n_stem = interior = 0
+    for x in range(n):
+        if structure[x] != "(":
+            continue
+        y = pairs[x]
+        nxt = x + 1
+        while structure[nxt] == ".":
+            nxt += 1
+        if nxt == y:
+            if y - x - 1 < 3:
+                raise ValueError("a hairpin loop under 3")
+            for z in range(x + 1, y):
+                label[z] = "h" + str(n_hairpin)[-1]
+            n_hairpin += 1
+        else:
+            back = pairs[nxt] + 1
+            while structure[back] == ".":
+                back += 1
+            if back == y and (nxt > x + 1 or pairs[nxt] < y - 1):
+                interior += 1
+        if not (x and structure[x - 1] == "(" and pairs[x - 1] == y + 1):
+            z = 0
+            while structure[x + z] == "(" and pairs[x + z] == y - z:
+                label[x + z] = label[y - z] = "s" + str(n_stem)[-1]
+                z += 1
+            n_stem += 1
+    runs, order = {}, []
+    for x in range(n):
+        if label[x] and (x == 0 or label[x - 1] != label[x]):
+            if label[x] not in runs:
+                runs[label[x]] = []
+                order.append(label[x])
+            runs[label[x]].append([x, x])
+        elif label[x]:
+            runs[label[x]][-1][1] = x
+    loops = [r for key in order if key[0] == "h" for r in runs[key]]
+    row = [0] * 16
+    row[0], row[1], row[2], row[3] = 1, n_hairpin, max(structure.count("("), structure.count(")")), interior
+    row[5] = max(r[1] - r[0] + 1 for r in loops)
+    row[8] = -1
+    for t, mirna in enumerate(mirnas):
+        start = seq.find(mirna)
+        last = start + len(mirna) - 1
+        arm = _arm(structure[start:start + len(mirna)])
+        shared = [max(0, min(last, r[1]) - max(start, r[0]) + 1) for r in loops]
+        gap = [r[0] - 1 - last if arm == 1 else start - r[1] - 1 for r in loops]
+        most = max(shared)
+        at = (4, 6, 7) if t == 0 else (8, 9, 10)
+        row[at[0]], row[at[1]], row[at[2]] = arm, most, min(gap) if most == 0 else gap[shared.index(most)]
+    row[11] = sum(max(r[1] + 1 - r[0] for r in runs[key]) for key in order if key[0] == "s")
+    row[12] = int(any("UGU" in seq[r[0]:r[1]] for r in loops))
+    stretch = structure[seq.find(mirnas[0]):seq.find(mirnas[0]) + len(mirnas[0])]
+    row[13], row[14], row[15] = stretch.count("(") + stretch.count(")"), len(stretch), n_stem
+    return row
+
+
 _FEATURES_HEADER_HEAD = ("realMicRNA\trealMicRNAName\tchr\tstartPos\tendPos\tclusterName\tclusterSeq\tmajoritySeq\tstableClusterSeq\t"
                          "alignedClusterSeq\tadjustedClusterSeq\tclusterSecondSeq\ttemplateSeq\tseqCount\treadCountSum\texactMatchRatio\t"
                          "headUnstableLength\ttailUnstableLength\t")
@@ -695,7 +980,7 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False):
+                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False, screen=False, fold=None):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
     as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`)."""
     from .engine import STRATUM_ALL
@@ -705,6 +990,10 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
         raise ValueError("features needs remap: the feature table is built from the rows of the second mapping")
     if precursors and not features:
         raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
+    if screen and not precursors:
+        raise ValueError("screen needs precursors: the candidates it folds are the windows cut there")
+    if screen and fold is None:
+        raise ValueError("screen needs fold: a callable (fasta_path, str_path), or the path of RNAfold")
     keys, parts = genome_libraries(engine, genome_prefix)
     if trim is not None:
         repeats, cutoff = trim
@@ -740,6 +1029,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
                                               **({"keep_device": True} if precursors else {}))
             if precursors:
                 cl["precursors"] = cluster_precursors(engine, cl["features"], trimmed, parts, out_stem, parts_libs=keys)
+                if screen:
+                    cl["screen"] = screen_precursors(engine, cl["features"], cl["precursors"], fold, out_stem)
                 cl["features"].pop("device", None)
                 cl["features"].pop("index", None)
             cl["remap"].pop("device", None)
@@ -748,7 +1039,7 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None, trim=None, remap=False, features=False, precursors=False):
+                    timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
@@ -758,10 +1049,14 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     remap=True (needs trim) adds :566-601 (map_reads_to_clusters: `<out_stem>_vs_representative_seq_modified_selected_sorted.tsv`;
     the return value gains "remap").  features=True (needs remap) adds :604 (cluster_features: the table's `_features.tsv` and
     `_cluster.txt`; the return value gains "features").  precursors=True (needs features) adds :608 (cluster_precursors: the
-    table's `_features_precusor.fa`; the return value gains "precursors")."""
+    table's `_features_precusor.fa`; the return value gains "precursors").  screen=True (needs precursors and fold = a callable
+    (fasta_path, str_path) or RNAfold's path) adds :610-626 (screen_precursors: two folds and the table's
+    `_features_updated_stableClusterSeq_15.tsv`; the return value gains "screen")."""
     from .engine import ReadSet
     if precursors and not features:
         raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
+    if screen and not precursors:
+        raise ValueError("screen needs precursors: the candidates it folds are the windows cut there")
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
     if longest > bowtie.MAX_READ_LEN:
@@ -773,15 +1068,15 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, features=features, precursors=precursors)
+                              out_stem, sam, timings, trim, remap, features=features, precursors=precursors, screen=screen, fold=fold)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None, trim=None, remap=False, features=False, precursors=False):
+                          sam=True, timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
-    names; no FASTA is parsed and no Python string is made per read.  trim / remap / features / precursors: as
+    names; no FASTA is parsed and no Python string is made per read.  trim / remap / features / precursors / screen / fold: as
     map_and_cluster's."""
     import torch
     from .engine import ReadSet
@@ -814,7 +1109,8 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
             seqs = pack.unpack_blob(words.cpu().numpy().view(np.uint64), lens.cpu().numpy(),
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, numbers, features=features, precursors=precursors)
+                              out_stem, sam, timings, trim, remap, numbers, features=features, precursors=precursors, screen=screen,
+                              fold=fold)
 
 
 def sample_stem(sample):
@@ -924,7 +1220,20 @@ def clusters_main(argv):
     ap.add_argument("--remap", action="store_true", help="with --trim: also map the reads to the retained clusters (the sorted table)")
     ap.add_argument("--features", action="store_true", help="with --remap: also build the cluster feature table (_features.tsv, _cluster.txt)")
     ap.add_argument("--precursors", action="store_true", help="with --features: also cut the precursor candidates (_features_precusor.fa)")
+    ap.add_argument("--screen", action="store_true", help="with --precursors: also fold and screen the candidates "
+                    "(_features_updated_stableClusterSeq_15.tsv); needs -pr or --fold-cmd")
+    ap.add_argument("-pr", dest="rnafold_dir", metavar="DIR", help="the directory RNAfold is in")
+    ap.add_argument("--fold-cmd", metavar="EXECUTABLE", help="the fold command itself (started as `EXECUTABLE --noPS --noLP`); overrides -pr")
     a = ap.parse_args(argv)
+    if a.screen and not a.precursors:
+        ap.error("--screen needs --precursors")
+    fold = None
+    if a.screen:
+        try:
+            fold = resolve_fold_cmd(a.rnafold_dir, a.fold_cmd)
+        except ValueError as e:
+            sys.stderr.write("%s\n" % e)
+            return 1
     if a.precursors and not a.features:
         ap.error("--precursors needs --features")
     if a.remap and not a.trim:
@@ -937,7 +1246,7 @@ def clusters_main(argv):
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
                                  sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap,
-                                 features=a.features, precursors=a.precursors)
+                                 features=a.features, precursors=a.precursors, screen=a.screen, fold=fold)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -954,6 +1263,9 @@ def clusters_main(argv):
             cl["features"][k] for k in ("seen", "passed", "written", "lines", "host_groups")))
     if a.precursors:
         sys.stderr.write("# precursors: %d records, %d bytes\n" % (cl["precursors"]["records"], cl["precursors"]["bytes"]))
+    if a.screen:
+        sys.stderr.write("# screened: %d lines, %d candidates, %d folded again, %d worked out on the host, %d fold calls\n" % tuple(
+            cl["screen"][k] for k in ("lines", "candidates", "pruned", "host_candidates", "folds")))
     return 0
 
 
@@ -961,7 +1273,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
-                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features [--precursors]]]]\n")
+                         "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features [--precursors [--screen -pr DIR | "
+                         "--fold-cmd EXECUTABLE]]]]]\n")
         return 1
     return clusters_main(argv[1:])
 
