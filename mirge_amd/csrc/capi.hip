@@ -100,6 +100,62 @@ int fail(int code, const char* fmt, ...) {
                   __FILE__, __LINE__);                                             \
   } while (0)
 
+// ---- a stage's scratch: one buffer, carved in a fixed order into typed pieces ----
+// A piece of a layout: where it starts, and of what.  at(base) is the only way to a pointer.
+template <class T>
+struct Piece {
+  size_t off = 0;
+  T* at(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+};
+// Hands out the pieces of one layout in order.  A piece takes max(bytes, least) rounded up to `align` -- the one
+// rounding rule.  Carver(8): the predict stages (an empty piece takes nothing); Carver(256, 1): -trf, -tcf and the
+// candidate reads (every piece has a slot of its own).
+class Carver {
+ public:
+  explicit Carver(size_t align, size_t least = 0) : align_(align), least_(least) {}
+  template <class T>
+  Piece<T> take(uint64_t count) {
+    const Piece<T> p{used_};
+    used_ += (std::max((size_t)count * sizeof(T), least_) + align_ - 1) & ~(align_ - 1);
+    return p;
+  }
+  size_t total() const { return used_; }
+
+ private:
+  size_t align_, least_, used_ = 0;
+};
+// the layout of a call that uses the stat words alone (the first piece of its stage's 8-byte layouts)
+size_t stat_only_bytes(uint32_t words) {
+  Carver c(8);
+  c.take<uint32_t>(words);
+  return c.total();
+}
+
+// the size-and-alignment check of a call that takes caller scratch; `sizer` is the call that reports `need`
+int scratch_ok(const char* fn, const void* d_tmp, uint64_t tmp_bytes, uint64_t need, const char* sizer) {
+  if (tmp_bytes < need || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than %s, or unaligned", fn, sizer);
+  return MRG_OK;
+}
+
+// n stat words back to the host on the stream, and the stream synchronised (whatever else was queued rides along)
+int read_stat(const uint32_t* stat, uint32_t* h_stat, size_t n, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(h_stat, stat, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MRG_OK;
+}
+
+// a writer's body with what it throws mapped to a code: invalid_argument is the caller's data, anything else the file's
+template <class F>
+auto guarded(const char* fn, F&& body) -> decltype(body()) {
+  try {
+    return body();
+  } catch (const std::invalid_argument& e) {
+    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
+  } catch (const std::exception& e) {
+    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
+  }
+}
+
 struct DevLib {
   uint32_t *blocks = nullptr, *super = nullptr, *text = nullptr, *seg_start = nullptr,
            *seg_ref = nullptr, *seg_off = nullptr, *chunk_seg = nullptr;
@@ -3017,15 +3073,20 @@ int mrg_read_counts_from_names(uint64_t n_reads, const char* names, const uint64
 namespace {
 // mrg_predict_trim's scratch: the stat words, three uint32 arrays and one uint64 array of n + 1, the scans' own scratch
 struct TrimScratch {
-  size_t flag32, rank, keep_len, keep_off, scan, total;
+  Piece<uint32_t> stat, flag32, rank, keep_len;
+  Piece<uint64_t> keep_off;
+  Piece<char> scan;
+  size_t total;
   explicit TrimScratch(uint64_t n) {
-    const size_t words = (size_t)((n + 1 + 1) & ~1ull) * sizeof(uint32_t);  // (an even count: the uint64 array stays aligned)
-    flag32 = mrg::kTrimStatWords * sizeof(uint32_t);
-    rank = flag32 + words;
-    keep_len = rank + words;
-    keep_off = keep_len + words;
-    scan = keep_off + (size_t)(n + 1) * sizeof(uint64_t);
-    total = scan + ((mrg::prims::scan_temp_bytes(n + 1) + 7) & ~(size_t)7);
+    Carver c(8);
+    const uint64_t words = (n + 1 + 1) & ~1ull;  // (an even count: the uint64 array stays aligned)
+    stat = c.take<uint32_t>(mrg::kTrimStatWords);
+    flag32 = c.take<uint32_t>(words);
+    rank = c.take<uint32_t>(words);
+    keep_len = c.take<uint32_t>(words);
+    keep_off = c.take<uint64_t>(n + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(n + 1));
+    total = c.total();
   }
 };
 constexpr uint64_t kTrimMaxClusters = (1ull << 31) - 1, kTrimMaxBytes = (1ull << 38) - 1;
@@ -3057,16 +3118,12 @@ int mrg_predict_trim(mrg_ctx* ctx, uint64_t n_clusters, const uint32_t* d_entry,
   if (total_len && (!n_clusters || !d_seq || !d_orig || !d_kept_orig)) return fail(MRG_ERR_ARG, "%s: null sequence buffers", fn);
   if (n_elements && (!d_rep_start || !d_rep_end)) return fail(MRG_ERR_ARG, "%s: null repeat table", fn);
   const TrimScratch sc(n_clusters);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_trim_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_trim_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
-  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
-  uint32_t* keep_len = reinterpret_cast<uint32_t*>(base + sc.keep_len);
-  uint64_t* keep_off = reinterpret_cast<uint64_t*>(base + sc.keep_off);
-  void* scan_tmp = base + sc.scan;
+  uint32_t *stat = sc.stat.at(d_tmp), *flag32 = sc.flag32.at(d_tmp), *rank = sc.rank.at(d_tmp), *keep_len = sc.keep_len.at(d_tmp);
+  uint64_t* keep_off = sc.keep_off.at(d_tmp);
+  void* scan_tmp = sc.scan.at(d_tmp);
   const mrg::TrimClusters c{(uint32_t)n_clusters, d_entry, d_strand, d_start, d_end, d_seq_off, d_seq, total_len};
   const mrg::TrimRepeats r{n_entries, (uint32_t)n_elements, d_rep_off, d_rep_start, d_rep_end};
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kTrimStatWords * sizeof(uint32_t), st));
@@ -3078,10 +3135,9 @@ int mrg_predict_trim(mrg_ctx* ctx, uint64_t n_clusters, const uint32_t* d_entry,
   HIP_TRY(mrg::trim_gather_launch(c, d_orig, rank, keep_off, d_kept_orig, st));
   uint32_t h_stat[mrg::kTrimStatWords] = {0, 0, 0, 0}, h_kept = 0;
   uint64_t h_len = 0;
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&h_kept, rank + n_clusters, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&h_len, keep_off + n_clusters, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kTrimStatWords, st)) return rc;
   if (h_stat[mrg::kTrimStatBadSeqOff]) return fail(MRG_ERR_ARG, "%s: d_seq_off does not ascend from 0 to total_len", fn);
   if (h_stat[mrg::kTrimStatBadEntry]) return fail(MRG_ERR_ARG, "%s: a cluster on an entry beyond the %u of the repeat table", fn, n_entries);
   if (h_stat[mrg::kTrimStatBadTable]) return fail(MRG_ERR_ARG, "%s: d_rep_off does not ascend inside the %llu elements", fn, (unsigned long long)n_elements);
@@ -3106,49 +3162,54 @@ int mrg_write_trimmed_clusters(const char* tsv_path, const char* fa_path, const 
   std::vector<const mrg::FmIndex*> ix;
   int rc = index_list(fn, parts, n_parts, &ix);
   if (rc != MRG_OK) return rc;
-  try {
+  return guarded(fn, [&] {
     const mrg::TrimmedClustersArgs a{tsv_path, fa_path,   orig_fa_path, sample,  &ix,   n_clusters, entry, strand,     start,
                                      end,      seq_off,   seq,          count_sum, member_off, members, n_reads, names, names_off,
                                      flag,     rep,       orig,         n_elements, rep_name_id, n_rep_names, rep_names, rep_names_off};
     mrg::write_trimmed_clusters(a, rows, kept);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------------- predict mode: the second mapping (csrc/predict_remap.hip)
 namespace {
 constexpr uint64_t kRemapMaxReads = (1ull << 31) - 1, kRemapMaxRows = 0xfffffffeull;
-inline size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
 // mrg_predict_trim_reads' scratch: two uint32 arrays of n + 1 and the scan's own
 struct RemapTrimScratch {
-  size_t rank, scan, total;
+  Piece<uint32_t> flag32, rank;
+  Piece<char> scan;
+  size_t total;
   explicit RemapTrimScratch(uint64_t n) {
-    rank = up8((size_t)(n + 1) * sizeof(uint32_t));
-    scan = 2 * rank;
-    total = scan + up8(mrg::prims::scan_temp_bytes(n + 1));
+    Carver c(8);
+    flag32 = c.take<uint32_t>(n + 1);
+    rank = c.take<uint32_t>(n + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(n + 1));
+    total = c.total();
   }
 };
 // mrg_predict_remap_rows' scratch: the stat words, three uint64 and five uint32 arrays and two byte arrays of T, the sort's own
 struct RemapRowsScratch {
-  size_t key0, key1, ckey, vals0, vals1, read, cluster, offset, mm, pass, sort, total;
+  Piece<uint32_t> stat;
+  Piece<uint64_t> key0, key1, ckey;
+  Piece<uint32_t> vals0, vals1, read, cluster, offset;
+  Piece<uint8_t> mm, pass;
+  Piece<char> sort;
+  size_t total;
   explicit RemapRowsScratch(uint64_t rows) {
-    const size_t k8 = (size_t)rows * sizeof(uint64_t), k4 = up8((size_t)rows * sizeof(uint32_t)), k1 = up8((size_t)rows);
-    key0 = up8(mrg::kRemapStatWords * sizeof(uint32_t));
-    key1 = key0 + k8;
-    ckey = key1 + k8;
-    vals0 = ckey + k8;
-    vals1 = vals0 + k4;
-    read = vals1 + k4;
-    cluster = read + k4;
-    offset = cluster + k4;
-    mm = offset + k4;
-    pass = mm + k1;
-    sort = pass + k1;
-    total = sort + up8(mrg::prims::radix_temp_bytes(rows));
+    Carver c(8);
+    stat = c.take<uint32_t>(mrg::kRemapStatWords);
+    key0 = c.take<uint64_t>(rows);
+    key1 = c.take<uint64_t>(rows);
+    ckey = c.take<uint64_t>(rows);
+    vals0 = c.take<uint32_t>(rows);
+    vals1 = c.take<uint32_t>(rows);
+    read = c.take<uint32_t>(rows);
+    cluster = c.take<uint32_t>(rows);
+    offset = c.take<uint32_t>(rows);
+    mm = c.take<uint8_t>(rows);
+    pass = c.take<uint8_t>(rows);
+    sort = c.take<char>(mrg::prims::radix_temp_bytes(rows));
+    total = c.total();
   }
 };
 }  // namespace
@@ -3177,14 +3238,12 @@ int mrg_predict_trim_reads(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words
   if (n && (!d_reads || !d_lens || !d_counts || !d_sel || !d_out_reads || !d_out_lens || (d_nmask && !d_out_nmask)))
     return fail(MRG_ERR_ARG, "%s: null buffers", fn);
   const RemapTrimScratch sc(n);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_remap_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_remap_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base);
-  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  uint32_t *flag32 = sc.flag32.at(d_tmp), *rank = sc.rank.at(d_tmp);
   HIP_TRY(mrg::remap_mark_launch(d_counts, (uint32_t)n, flag32, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n + 1, sc.scan.at(d_tmp), st));
   HIP_TRY(mrg::remap_compact_launch((uint32_t)n, rank, d_sel, st));
   uint32_t k = 0;
   HIP_TRY(hipMemcpyAsync(&k, rank + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -3216,19 +3275,14 @@ int mrg_predict_remap_rows(mrg_ctx* ctx, uint64_t n_reads, const uint32_t* d_num
   if (T && (!n_clusters || !d_numbers || !d_kept || !d_read || !d_cluster || !d_offset || !d_mm || !d_pass))
     return fail(MRG_ERR_ARG, "%s: null row buffers", fn);
   const RemapRowsScratch sc(T);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_remap_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_remap_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint64_t* key0 = reinterpret_cast<uint64_t*>(base + sc.key0);
-  uint64_t* key1 = reinterpret_cast<uint64_t*>(base + sc.key1);
-  uint64_t* ckey = reinterpret_cast<uint64_t*>(base + sc.ckey);
-  uint32_t* vals0 = reinterpret_cast<uint32_t*>(base + sc.vals0);
-  uint32_t* vals1 = reinterpret_cast<uint32_t*>(base + sc.vals1);
-  const mrg::RemapRows listed{reinterpret_cast<uint32_t*>(base + sc.read), reinterpret_cast<uint32_t*>(base + sc.cluster),
-                              reinterpret_cast<uint32_t*>(base + sc.offset), reinterpret_cast<uint8_t*>(base + sc.mm),
-                              reinterpret_cast<uint8_t*>(base + sc.pass)};
+  uint32_t* stat = sc.stat.at(d_tmp);
+  uint64_t *key0 = sc.key0.at(d_tmp), *key1 = sc.key1.at(d_tmp), *ckey = sc.ckey.at(d_tmp);
+  uint32_t *vals0 = sc.vals0.at(d_tmp), *vals1 = sc.vals1.at(d_tmp);
+  void* sort_tmp = sc.sort.at(d_tmp);
+  const mrg::RemapRows listed{sc.read.at(d_tmp), sc.cluster.at(d_tmp), sc.offset.at(d_tmp), sc.mm.at(d_tmp), sc.pass.at(d_tmp)};
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kRemapStatWords * sizeof(uint32_t), st));
   // a listing without rows has no say: its offsets are not read
   const mrg::RemapListing p1{d_off1, rows1 ? (uint32_t)n_reads : 0u, d_ref1, d_pos1, d_mm1, (uint32_t)rows1};
@@ -3238,17 +3292,16 @@ int mrg_predict_remap_rows(mrg_ctx* ctx, uint64_t n_reads, const uint32_t* d_num
     HIP_TRY(mrg::remap_merge_launch(a, st));
     // by read name, then (stable) by cluster name: the order of `sort -k6,6 -k1,1` up to the rows equal in both
     bool second = false;
-    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, vals0, vals1, (uint32_t)T, mrg::kRemapKeyBits, base + sc.sort, st, &second));
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, vals0, vals1, (uint32_t)T, mrg::kRemapKeyBits, sort_tmp, st, &second));
     uint32_t* by_read = second ? vals1 : vals0;
     uint32_t* spare = second ? vals0 : vals1;
     HIP_TRY(mrg::remap_gather_keys_launch(ckey, by_read, (uint32_t)T, key0, st));
-    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, by_read, spare, (uint32_t)T, mrg::kRemapKeyBits, base + sc.sort, st, &second));
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(key0, key1, by_read, spare, (uint32_t)T, mrg::kRemapKeyBits, sort_tmp, st, &second));
     const mrg::RemapRows out{d_read, d_cluster, d_offset, d_mm, d_pass};
     HIP_TRY(mrg::remap_gather_rows_launch(listed, second ? spare : by_read, (uint32_t)T, out, st));
   }
   uint32_t h_stat[mrg::kRemapStatWords] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kRemapStatWords, st)) return rc;
   if (h_stat[mrg::kRemapStatBadOffsets]) return fail(MRG_ERR_ARG, "%s: a listing's offsets do not ascend from 0 to its rows", fn);
   if (h_stat[mrg::kRemapStatBadCluster]) return fail(MRG_ERR_ARG, "%s: a row on an entry beyond the %llu clusters, or at a negative offset", fn, (unsigned long long)n_clusters);
   if (h_stat[mrg::kRemapStatBadRead]) return fail(MRG_ERR_ARG, "%s: a pass-2 read beyond the %llu reads", fn, (unsigned long long)n_reads);
@@ -3267,17 +3320,13 @@ int mrg_write_remapped_rows(const char* path, const uint64_t* reads, uint32_t wo
   if (n_clusters && (!clusters || !kept_seq_off || !kept_orig)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
   if (n_rows && (!row_read || !row_cluster || !row_offset || !row_mm || !row_pass)) return fail(MRG_ERR_ARG, "%s: null row arrays", fn);
   if (words_per_read < 1 || words_per_read > 8 || stride < n_reads) return fail(MRG_ERR_ARG, "%s: words_per_read must be 1 .. 8 and the stride cover the reads", fn);
-  try {
-    const mrg::RemappedRowsArgs a{path,       reads,        words_per_read, stride,   lens,     nmask,       n_reads,    numbers,
+  return guarded(fn, [&] {
+    const mrg::RemappedRowsArgs a{path,      reads,        words_per_read, stride,   lens,     nmask,       n_reads,    numbers,
                                   counts,     clusters ? &clusters->ix : nullptr,     n_clusters, kept_seq_off, kept_orig, n_rows,
                                   row_read,   row_cluster,  row_offset,     row_mm,   row_pass, trim5,       trim3};
     *rows = mrg::write_remapped_rows(a);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------------- predict mode: the cluster feature table (csrc/predict_features.hip)
@@ -3285,29 +3334,37 @@ namespace {
 constexpr uint64_t kFeatMaxRows = 0xfffffffeull, kFeatMaxItems = (1ull << 31) - 1;
 // mrg_predict_feature_groups' scratch: the stat words, two uint32 arrays of n_rows + 1 and the scan's own
 struct FeatGroupScratch {
-  size_t flag32, rank, scan, total;
+  Piece<uint32_t> stat, flag32, rank;
+  Piece<char> scan;
+  size_t total;
   explicit FeatGroupScratch(uint64_t rows) {
-    const size_t k4 = up8((size_t)(rows + 1) * sizeof(uint32_t));
-    flag32 = up8(mrg::kFeatStatWords * sizeof(uint32_t));
-    rank = flag32 + k4;
-    scan = rank + k4;
-    total = scan + up8(mrg::prims::scan_temp_bytes(rows + 1));
+    Carver c(8);
+    stat = c.take<uint32_t>(mrg::kFeatStatWords);
+    flag32 = c.take<uint32_t>(rows + 1);
+    rank = c.take<uint32_t>(rows + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(rows + 1));
+    total = c.total();
   }
 };
 // mrg_predict_feature_neighbors' scratch: the stat words, five uint64 and two uint32 arrays of G, the sort's own
 struct FeatNeighborScratch {
-  size_t key_c, key_se, key_r, keys0, keys1, vals0, vals1, sort, total;
+  Piece<uint32_t> stat;
+  Piece<uint64_t> key_c, key_se, key_r, keys0, keys1;
+  Piece<uint32_t> vals0, vals1;
+  Piece<char> sort;
+  size_t total;
   explicit FeatNeighborScratch(uint64_t G) {
-    const size_t k8 = (size_t)G * sizeof(uint64_t), k4 = up8((size_t)G * sizeof(uint32_t));
-    key_c = up8(mrg::kFeatStatWords * sizeof(uint32_t));
-    key_se = key_c + k8;
-    key_r = key_se + k8;
-    keys0 = key_r + k8;
-    keys1 = keys0 + k8;
-    vals0 = keys1 + k8;
-    vals1 = vals0 + k4;
-    sort = vals1 + k4;
-    total = sort + up8(mrg::prims::radix_temp_bytes(G));
+    Carver c(8);
+    stat = c.take<uint32_t>(mrg::kFeatStatWords);
+    key_c = c.take<uint64_t>(G);
+    key_se = c.take<uint64_t>(G);
+    key_r = c.take<uint64_t>(G);
+    keys0 = c.take<uint64_t>(G);
+    keys1 = c.take<uint64_t>(G);
+    vals0 = c.take<uint32_t>(G);
+    vals1 = c.take<uint32_t>(G);
+    sort = c.take<char>(mrg::prims::radix_temp_bytes(G));
+    total = c.total();
   }
 };
 int feat_stat_error(const char* fn, const uint32_t* h_stat) {
@@ -3345,31 +3402,26 @@ int mrg_predict_feature_groups(mrg_ctx* ctx, uint64_t n_rows, const uint32_t* d_
     return fail(MRG_ERR_ARG, "%s: null arrays", fn);
   if (n_rows && (!n_reads || !n_clusters || !n_entries)) return fail(MRG_ERR_ARG, "%s: rows without reads, clusters or entries", fn);
   const FeatGroupScratch sc(n_rows);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_feature_temp_bytes")) return rc;
   if (n_rows == 0) return MRG_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
-  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
+  uint32_t *stat = sc.stat.at(d_tmp), *flag32 = sc.flag32.at(d_tmp), *rank = sc.rank.at(d_tmp);
   const mrg::FeatRows rows{(uint32_t)n_rows, d_row_read, d_row_cluster};
   const mrg::FeatReads reads{nullptr, nullptr, nullptr, d_counts, (uint32_t)n_reads};
   const mrg::FeatClusters cl{(uint32_t)n_clusters, d_cl_entry, nullptr, d_cl_start, d_cl_end, nullptr, d_kept_seq_off, nullptr, orig_len};
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kFeatStatWords * sizeof(uint32_t), st));
   HIP_TRY(mrg::feat_mark_launch(rows, (uint32_t)n_reads, (uint32_t)n_clusters, flag32, stat, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_rows + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_rows + 1, sc.scan.at(d_tmp), st));
   uint32_t h_stat[mrg::kFeatStatWords] = {0}, G = 0;
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&G, rank + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kFeatStatWords, st)) return rc;
   if (int rc = feat_stat_error(fn, h_stat)) return rc;   // (rows of no cluster: the groups would mean nothing)
   if (G == 0 || G > n_rows) return fail(MRG_ERR_HIP, "%s: %u groups of %llu rows", fn, G, (unsigned long long)n_rows);
   HIP_TRY(mrg::feat_starts_launch(rows, rank, d_row_group, d_group_off, d_group_cluster, st));
   HIP_TRY(mrg::feat_filter_launch(G, d_group_off, d_group_cluster, rows, reads, cl, (uint32_t)n_entries, d_entry_len, d_group_sum, d_group_pass,
                                   stat, st));
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kFeatStatWords, st)) return rc;
   if (int rc = feat_stat_error(fn, h_stat)) return rc;
   *n_groups = G;
   *n_passed = h_stat[mrg::kFeatStatPassed];
@@ -3387,7 +3439,7 @@ int mrg_predict_feature_align(mrg_ctx* ctx, uint64_t n_rows, const uint32_t* d_r
   if (n_rows > kFeatMaxRows || n_groups > n_rows) return fail(MRG_ERR_ARG, "%s: %llu groups of %llu rows (the limit is 2^32 - 2 rows)", fn,
                                                               (unsigned long long)n_groups, (unsigned long long)n_rows);
   if (n_reads > kFeatMaxItems || n_clusters > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: reads and clusters are limited to 2^31 - 1 each", fn);
-  if (!d_tmp || tmp_bytes < up8(mrg::kFeatStatWords * sizeof(uint32_t)) || ((uintptr_t)d_tmp & 7))
+  if (!d_tmp || tmp_bytes < stat_only_bytes(mrg::kFeatStatWords) || ((uintptr_t)d_tmp & 7))
     return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
   if (n_clusters && (!d_kept_seq_off || (orig_len && !d_kept_orig) || !d_cl_word || !d_cl_len)) return fail(MRG_ERR_ARG, "%s: null cluster arrays", fn);
   if (n_rows && (!n_groups || !n_reads || !n_clusters || !d_row_read || !d_row_cluster || !d_row_group || !d_group_pass || !d_reads || !d_lens ||
@@ -3417,8 +3469,7 @@ int mrg_predict_feature_align(mrg_ctx* ctx, uint64_t n_rows, const uint32_t* d_r
     HIP_TRY(mrg::feat_align_launch(a, st));
   }
   uint32_t h_stat[mrg::kFeatStatWords] = {0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kFeatStatWords, st)) return rc;
   return feat_stat_error(fn, h_stat);
 }
 
@@ -3472,17 +3523,14 @@ int mrg_predict_feature_neighbors(mrg_ctx* ctx, uint64_t n_groups, const uint32_
                    !d_cl_end || !d_kept || !d_entry_rank || !d_order || !d_nb_t || !d_nb_up || !d_nb_down || !d_nb_flags))
     return fail(MRG_ERR_ARG, "%s: null arrays", fn);
   const FeatNeighborScratch sc(n_groups);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_feature_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_feature_temp_bytes")) return rc;
   if (n_groups == 0) return MRG_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint64_t* key_c = reinterpret_cast<uint64_t*>(base + sc.key_c);
-  uint64_t* key_se = reinterpret_cast<uint64_t*>(base + sc.key_se);
-  uint64_t* key_r = reinterpret_cast<uint64_t*>(base + sc.key_r);
-  uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(base + sc.keys0), reinterpret_cast<uint64_t*>(base + sc.keys1)};
-  uint32_t* vals[2] = {reinterpret_cast<uint32_t*>(base + sc.vals0), reinterpret_cast<uint32_t*>(base + sc.vals1)};
+  uint32_t* stat = sc.stat.at(d_tmp);
+  uint64_t *key_c = sc.key_c.at(d_tmp), *key_se = sc.key_se.at(d_tmp), *key_r = sc.key_r.at(d_tmp);
+  uint64_t* keys[2] = {sc.keys0.at(d_tmp), sc.keys1.at(d_tmp)};
+  uint32_t* vals[2] = {sc.vals0.at(d_tmp), sc.vals1.at(d_tmp)};
   const uint32_t G = (uint32_t)n_groups;
   mrg::FeatNeighborArgs a;
   a.n_groups = G;
@@ -3502,15 +3550,14 @@ int mrg_predict_feature_neighbors(mrg_ctx* ctx, uint64_t n_groups, const uint32_
   for (uint32_t pass = 0; pass < 3; ++pass) {
     if (pass) HIP_TRY(mrg::feat_gather_keys_launch(later[pass - 1], vals[at], G, keys[0], st));
     bool second = false;
-    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[0], keys[1], vals[at], vals[at ^ 1u], G, bits[pass], base + sc.sort, st, &second));
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[0], keys[1], vals[at], vals[at ^ 1u], G, bits[pass], sc.sort.at(d_tmp), st, &second));
     if (second) at ^= 1u;
     if (pass == 2 && second) std::swap(keys[0], keys[1]);
   }
   HIP_TRY(hipMemcpyAsync(d_order, vals[at], (size_t)G * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   HIP_TRY(mrg::feat_neighbors_launch(a, keys[0], d_order, d_nb_t, d_nb_up, d_nb_down, d_nb_flags, stat, st));
   uint32_t h_stat[mrg::kFeatStatWords] = {0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kFeatStatWords, st)) return rc;
   if (int rc = feat_stat_error(fn, h_stat)) return rc;
   *n_sorted = h_stat[mrg::kFeatStatSorted];
   return MRG_OK;
@@ -3537,7 +3584,7 @@ int mrg_write_predict_features(const char* features_path, const char* cluster_pa
   std::vector<const mrg::FmIndex*> ix;
   int rc = index_list(fn, parts, n_parts, &ix);
   if (rc != MRG_OK) return rc;
-  try {
+  return guarded(fn, [&] {
     mrg::FeatWriteArgs a;
     a.features_path = features_path;
     a.cluster_path = cluster_path;
@@ -3576,11 +3623,7 @@ int mrg_write_predict_features(const char* features_path, const char* cluster_pa
     a.order = order;
     mrg::write_predict_features(a, written);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------------- predict mode: the precursor candidates (csrc/predict_precursors.hip)
@@ -3589,15 +3632,18 @@ constexpr uint64_t kPrecMaxGroups = (1ull << 30) - 1, kPrecMaxBytes = (1ull << 3
 // mrg_predict_precursors' scratch: the stat words, two uint32 arrays of S + 1, the windows [4 S], the lengths [2 S + 1] and
 // the scan's own; mrg_predict_precursor_bases reads the stat words alone
 struct PrecScratch {
-  size_t flag32, rank, win, len32, scan, total;
+  Piece<uint32_t> stat, flag32, rank, win, len32;
+  Piece<char> scan;
+  size_t total;
   explicit PrecScratch(uint64_t S) {
-    const size_t k4 = up8((size_t)(S + 1) * sizeof(uint32_t));
-    flag32 = up8(mrg::kPrecStatWords * sizeof(uint32_t));
-    rank = flag32 + k4;
-    win = rank + k4;
-    len32 = win + up8((size_t)(4 * S) * sizeof(uint32_t));
-    scan = len32 + up8((size_t)(2 * S + 1) * sizeof(uint32_t));
-    total = scan + up8(mrg::prims::scan_temp_bytes(2 * S + 1));
+    Carver c(8);
+    stat = c.take<uint32_t>(mrg::kPrecStatWords);
+    flag32 = c.take<uint32_t>(S + 1);
+    rank = c.take<uint32_t>(S + 1);
+    win = c.take<uint32_t>(4 * S);
+    len32 = c.take<uint32_t>(2 * S + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(2 * S + 1));
+    total = c.total();
   }
 };
 int prec_stat_error(const char* fn, const uint32_t* h_stat) {
@@ -3652,7 +3698,7 @@ int mrg_predict_precursors(mrg_ctx* ctx, uint64_t n_order, const uint32_t* d_ord
                   !d_written || !d_rec_group || !d_rec_lo || !d_rec_hi))
     return fail(MRG_ERR_ARG, "%s: null arrays", fn);
   const PrecScratch sc(n_order);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_precursor_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_precursor_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   if (n_order == 0) {
@@ -3660,25 +3706,20 @@ int mrg_predict_precursors(mrg_ctx* ctx, uint64_t n_order, const uint32_t* d_ord
     HIP_TRY(hipStreamSynchronize(st));
     return MRG_OK;
   }
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint32_t* flag32 = reinterpret_cast<uint32_t*>(base + sc.flag32);
-  uint32_t* rank = reinterpret_cast<uint32_t*>(base + sc.rank);
-  uint32_t* win = reinterpret_cast<uint32_t*>(base + sc.win);
-  uint32_t* len32 = reinterpret_cast<uint32_t*>(base + sc.len32);
+  uint32_t *stat = sc.stat.at(d_tmp), *flag32 = sc.flag32.at(d_tmp), *rank = sc.rank.at(d_tmp), *win = sc.win.at(d_tmp),
+           *len32 = sc.len32.at(d_tmp);
   const mrg::PrecGroups g{(uint32_t)n_order, d_order, (uint32_t)n_groups, d_group_cluster, d_frame, d_valid};
   const mrg::PrecClusters cl{(uint32_t)n_clusters, d_cl_entry, d_cl_strand, d_cl_start, d_cl_end, (uint32_t)n_entries, d_entry_len};
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPrecStatWords * sizeof(uint32_t), st));
   HIP_TRY(mrg::prec_windows_launch(g, cl, d_written, flag32, win, stat, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_order + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flag32, rank, n_order + 1, sc.scan.at(d_tmp), st));
   uint32_t h_stat[mrg::kPrecStatWords] = {0}, W = 0;
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&W, rank + n_order, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kPrecStatWords, st)) return rc;
   if (int rc = prec_stat_error(fn, h_stat)) return rc;
   if (W > n_order) return fail(MRG_ERR_HIP, "%s: %u groups written of %llu", fn, W, (unsigned long long)n_order);
   HIP_TRY(mrg::prec_compact_launch(g, rank, win, d_rec_group, d_rec_lo, d_rec_hi, len32, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_rec_off, 2ull * W + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_rec_off, 2ull * W + 1, sc.scan.at(d_tmp), st));
   uint64_t total = 0;
   HIP_TRY(hipMemcpyAsync(&total, d_rec_off + 2ull * W, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3698,7 +3739,7 @@ int mrg_predict_precursor_bases(mrg_ctx* ctx, uint64_t n_rec, const uint32_t* d_
   if (n_rec > 2 * kPrecMaxGroups || n_groups > kPrecMaxGroups) return fail(MRG_ERR_ARG, "%s: records and groups are limited to 2^31 - 2 and 2^30 - 1", fn);
   if (n_clusters > kFeatMaxItems || n_entries > kFeatMaxItems) return fail(MRG_ERR_ARG, "%s: clusters and entries are limited to 2^31 - 1 each", fn);
   if (seq_len > kPrecMaxBytes) return fail(MRG_ERR_ARG, "%s: %llu sequence bytes; the limit is 2^38 - 1", fn, (unsigned long long)seq_len);
-  if (!d_tmp || !d_rec_off || tmp_bytes < up8(mrg::kPrecStatWords * sizeof(uint32_t)) || ((uintptr_t)d_tmp & 7))
+  if (!d_tmp || !d_rec_off || tmp_bytes < stat_only_bytes(mrg::kPrecStatWords) || ((uintptr_t)d_tmp & 7))
     return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_precursor_temp_bytes, unaligned, or null offsets", fn);
   if (n_rec && (!d_rec_group || !d_rec_lo || !d_rec_hi || !d_group_cluster || !d_cl_entry || !d_cl_strand || !d_entry_len)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
   if (seq_len && (!n_rec || !d_seq)) return fail(MRG_ERR_ARG, "%s: sequence bytes without records or buffer", fn);
@@ -3726,8 +3767,7 @@ int mrg_predict_precursor_bases(mrg_ctx* ctx, uint64_t n_rec, const uint32_t* d_
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPrecStatWords * sizeof(uint32_t), st));
   HIP_TRY(mrg::prec_check_launch(r, g, cl, seq_len, stat, st));
   uint32_t h_stat[mrg::kPrecStatWords] = {0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kPrecStatWords, st)) return rc;
   if (int rc = prec_stat_error(fn, h_stat)) return rc;  // (before a byte is written: the bases kernel trusts the records)
   HIP_TRY(mrg::prec_bases_launch(r, g, cl, genome, seq_len, d_seq, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3748,16 +3788,12 @@ int mrg_write_precursors(const char* path, const mrg_index* const* parts, uint32
   std::vector<const mrg::FmIndex*> ix;
   int rc = index_list(fn, parts, n_parts, &ix);
   if (rc != MRG_OK) return rc;
-  try {
+  return guarded(fn, [&] {
     const mrg::PrecWriteArgs a{path, &ix, clusters ? &clusters->ix : nullptr, n_clusters, cl_entry, n_groups, group_cluster, n_rec, rec_group,
                                rec_lo, rec_hi, rec_off, seq, seq_len};
     mrg::write_precursors(a, written);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------- predict mode: screening the folded candidates (csrc/predict_screen.hip)
@@ -3765,11 +3801,15 @@ namespace {
 constexpr uint64_t kScreenMaxLines = (1ull << 28) - 1, kScreenMaxItems = (1ull << 31) - 1;
 // the screen calls' scratch: the stat words, the slices' lengths [n_cand + 1] and the scan's own
 struct ScreenScratch {
-  size_t len32, scan, total;
+  Piece<uint32_t> stat, len32;
+  Piece<char> scan;
+  size_t total;
   explicit ScreenScratch(uint64_t n_cand) {
-    len32 = up8(mrg::kScreenStatWords * sizeof(uint32_t));
-    scan = len32 + up8((size_t)(n_cand + 1) * sizeof(uint32_t));
-    total = scan + up8(mrg::prims::scan_temp_bytes(n_cand + 1));
+    Carver c(8);
+    stat = c.take<uint32_t>(mrg::kScreenStatWords);
+    len32 = c.take<uint32_t>(n_cand + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(n_cand + 1));
+    total = c.total();
   }
 };
 int screen_scratch_ok(const char* fn, void* d_tmp, uint64_t tmp_bytes, uint64_t n_cand) {
@@ -3790,11 +3830,7 @@ int screen_first_of(const uint8_t* d_state, size_t stride, uint64_t n, uint8_t w
     }
   return MRG_OK;
 }
-int screen_read_stat(uint32_t* stat, uint32_t* h_stat, hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, mrg::kScreenStatWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MRG_OK;
-}
+int screen_read_stat(const uint32_t* stat, uint32_t* h_stat, hipStream_t st) { return read_stat(stat, h_stat, mrg::kScreenStatWords, st); }
 }  // namespace
 
 int mrg_predict_screen_temp_bytes(uint64_t n_cand, uint64_t* bytes) {
@@ -3851,9 +3887,7 @@ int mrg_predict_screen_prune(mrg_ctx* ctx, uint64_t n_cand, const uint32_t* d_ca
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const ScreenScratch sc(n_cand);
-  char* base = static_cast<char*>(d_tmp);
-  uint32_t* stat = reinterpret_cast<uint32_t*>(base);
-  uint32_t* len32 = reinterpret_cast<uint32_t*>(base + sc.len32);
+  uint32_t *stat = sc.stat.at(d_tmp), *len32 = sc.len32.at(d_tmp);
   const mrg::ScreenBlob rec{(uint32_t)n_rec, d_rec_off, d_seq, d_str, seq_len}, mir{(uint32_t)n_mir, d_mir_off, d_mir, nullptr, mir_len};
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kScreenStatWords * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(len32 + n_cand, 0, sizeof(uint32_t), st));
@@ -3865,7 +3899,7 @@ int mrg_predict_screen_prune(mrg_ctx* ctx, uint64_t n_cand, const uint32_t* d_ca
   if (h_stat[mrg::kScreenStatBadOffsets]) return fail(MRG_ERR_ARG, "%s: offsets that do not ascend from 0 to the length of their text", fn);
   if (h_stat[mrg::kScreenStatBadCand]) return fail(MRG_ERR_ARG, "%s: a candidate names no record or no miRNA", fn);
   HIP_TRY(mrg::screen_prune_launch((uint32_t)n_cand, d_cand_rec, d_cand_mir, rec, mir, pruned_length, d_status, d_lo, d_hi, len32, stat, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_pruned_off, n_cand + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32_to_u64(len32, d_pruned_off, n_cand + 1, sc.scan.at(d_tmp), st));
   uint64_t total = 0;
   HIP_TRY(hipMemcpyAsync(&total, d_pruned_off + n_cand, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (int rc = screen_read_stat(stat, h_stat, st)) return rc;
@@ -3946,18 +3980,14 @@ int mrg_read_str_file(const char* path, uint64_t expected, uint64_t* n_rec, uint
   if (!path || !n_rec || !text_len || !handle) return fail(MRG_ERR_ARG, "%s: null argument", fn);
   *handle = nullptr;
   *n_rec = *text_len = 0;
-  try {
+  return guarded(fn, [&] {
     std::unique_ptr<mrg::StrRecords> r(new mrg::StrRecords);
     mrg::read_str_file(path, expected, r.get());
     *n_rec = r->mfe.size();
     *text_len = r->seq.size();
     *handle = r.release();
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 int mrg_str_file_copy(void* handle, uint64_t* off, char* seq, char* structure, double* mfe) {
@@ -3980,14 +4010,10 @@ int mrg_write_pruned_fasta(const char* path, uint64_t n, const uint64_t* off, co
   const char* fn = "mrg_write_pruned_fasta";
   if (!path || !off || !written || (n && !keep)) return fail(MRG_ERR_ARG, "%s: null argument", fn);
   *written = 0;
-  try {
+  return guarded(fn, [&] {
     *written = mrg::write_pruned_fasta(path, n, off, seq, keep);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 int mrg_write_screened_features(const char* features_path, const char* out_path, uint64_t n_lines, const int32_t* best, const int32_t* feat,
@@ -3996,15 +4022,11 @@ int mrg_write_screened_features(const char* features_path, const char* out_path,
   if (!features_path || !out_path || !written || !p_off) return fail(MRG_ERR_ARG, "%s: null argument", fn);
   *written = 0;
   if (n_lines && (!best || !feat || !p_mfe)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
-  try {
+  return guarded(fn, [&] {
     const mrg::ScreenWriteArgs a{features_path, out_path, n_lines, best, feat, p_off, p_seq, p_str, p_mfe};
     *written = mrg::write_screened_features(a);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ----------------------------------------------------- host convenience
@@ -4572,36 +4594,27 @@ int mrg_write_isomir_gff(const char* const* paths, const char* const* coldata, u
     return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: null buffers");
   if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
     return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: bad words_per_read / stride");
-  try {
+  return guarded("mrg_write_isomir_gff", [&] {
     mrg::write_isomir_gff(paths, coldata, n_samples, source, reads, words_per_read, stride, lens, nmask, n, quant, idx, rec, mask, k,
                           entry_names, pre_names, n_entries, rows);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "mrg_write_isomir_gff: %s", e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "mrg_write_isomir_gff: %s", e.what());
-  }
+  });
 }
 
 // ------------------------------------------------------------- -trf
 extern "C++" {
 namespace {
 
-struct TrfBuf {  // one device allocation, carved into 256-byte aligned pieces
+struct TrfBuf {  // the carver with a device allocation of its own: 256-byte aligned pieces, freed on return
+  Carver c{256, 1};
   char* p = nullptr;
-  uint64_t used = 0;
   ~TrfBuf() {
     if (p) (void)hipFree(p);
   }
-  static uint64_t up(uint64_t b) { return (b + 255) & ~255ull; }
-  uint64_t reserve(uint64_t bytes) {
-    const uint64_t at = used;
-    used += up(std::max<uint64_t>(bytes, 1));
-    return at;
-  }
-  hipError_t alloc() { return hipMalloc((void**)&p, std::max<uint64_t>(used, 256)); }
+  uint64_t reserve(uint64_t bytes) { return c.take<char>(bytes).off; }
+  hipError_t alloc() { return hipMalloc((void**)&p, std::max<size_t>(c.total(), 256)); }
   template <class T>
-  T* at(uint64_t off) const { return (T*)(p + off); }
+  T* at(uint64_t off) const { return Piece<T>{off}.at(p); }
 };
 
 uint32_t bits_for(uint64_t v) {  // the smallest b with v < 2^b
@@ -4841,16 +4854,12 @@ int mrg_write_trf_tables(const char* const* paths, const char* const* samples, u
   if ((h && !hits) || (n_clusters && !clusters) || (n_merged && !merged_names)) return fail(MRG_ERR_ARG, "mrg_write_trf_tables: null buffers");
   if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
     return fail(MRG_ERR_ARG, "mrg_write_trf_tables: bad words_per_read / stride");
-  try {
+  return guarded("mrg_write_trf_tables", [&] {
     const mrg::TrfWriteArgs a{paths, samples, n_samples, denom, reads, words_per_read, stride, lens, nmask, n, quant, rec, k, hits, h,
                               desc, entry_names, aa_types, anticodons, n_entries, clusters, n_clusters, merged_names, n_merged};
     mrg::write_trf_tables(a, rows);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "mrg_write_trf_tables: %s", e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "mrg_write_trf_tables: %s", e.what());
-  }
+  });
 }
 
 // ------------------------------------------------------------- -trf: the per-sample blocks (csrc/trf_groups.hip)
@@ -5118,16 +5127,12 @@ int mrg_write_trf_sample_reports(const char* const* paths, uint32_t n_samples, c
     return fail(MRG_ERR_ARG, "%s: null buffers", fn);
   if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
     return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
-  try {
+  return guarded(fn, [&] {
     const mrg::TrfSampleWriteArgs a{paths, n_samples, denom, reads, words_per_read, stride, lens, nmask, n, quant, rec, k, entries,
                                     entry_names, templates, aa_types, n_entries, n_names, blocks, block_sums, n_blocks, rows, n_rows};
     mrg::write_trf_sample_reports(a);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------------------------- -tcf (csrc/collapsed_order.hip)
@@ -5135,24 +5140,24 @@ extern "C++" {
 namespace {
 
 struct SeqScratch {  // the caller's scratch, carved into 256-byte aligned pieces
-  uint64_t k0, k1, v0, v1, flags, scan, sort, stat, total;
+  Piece<uint64_t> k0, k1;
+  Piece<uint32_t> v0, v1, flags, stat;
+  Piece<char> scan, sort;
+  size_t total;
   // with_flags: the flags of a sample column and their scan (mrg_collapsed_order)
   SeqScratch(uint64_t n, bool with_flags) {
-    uint64_t used = 0;
-    auto reserve = [&](uint64_t bytes) {
-      const uint64_t at = used;
-      used += (std::max<uint64_t>(bytes, 1) + 255) & ~255ull;
-      return at;
-    };
-    k0 = reserve(n * sizeof(uint64_t));
-    k1 = reserve(n * sizeof(uint64_t));
-    v0 = reserve(n * sizeof(uint32_t));
-    v1 = reserve(n * sizeof(uint32_t));
-    flags = with_flags ? reserve((n + 1) * sizeof(uint32_t)) : 0;
-    scan = with_flags ? reserve(mrg::prims::scan_temp_bytes(n + 1)) : 0;
-    sort = reserve(mrg::prims::radix_temp_bytes(n));
-    stat = reserve(mrg::kSeqStatWords * sizeof(uint32_t));
-    total = used;
+    Carver c(256, 1);
+    k0 = c.take<uint64_t>(n);
+    k1 = c.take<uint64_t>(n);
+    v0 = c.take<uint32_t>(n);
+    v1 = c.take<uint32_t>(n);
+    if (with_flags) {
+      flags = c.take<uint32_t>(n + 1);
+      scan = c.take<char>(mrg::prims::scan_temp_bytes(n + 1));
+    }
+    sort = c.take<char>(mrg::prims::radix_temp_bytes(n));
+    stat = c.take<uint32_t>(mrg::kSeqStatWords);
+    total = c.total();
   }
 };
 
@@ -5178,13 +5183,12 @@ int mrg_seq_rank(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read,
   if (max_len > 255 || max_len > 32 * words_per_read)
     return fail(MRG_ERR_ARG, "%s: max_len %u: at most 255 and what %u words hold", fn, max_len, words_per_read);
   const SeqScratch sc((uint64_t)n, false);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_collapsed_order_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_collapsed_order_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)d_tmp;
-  uint64_t* keys[2] = {(uint64_t*)(base + sc.k0), (uint64_t*)(base + sc.k1)};
-  uint32_t* vals[2] = {(uint32_t*)(base + sc.v0), (uint32_t*)(base + sc.v1)};
-  uint32_t* stat = (uint32_t*)(base + sc.stat);
+  uint64_t* keys[2] = {sc.k0.at(d_tmp), sc.k1.at(d_tmp)};
+  uint32_t* vals[2] = {sc.v0.at(d_tmp), sc.v1.at(d_tmp)};
+  uint32_t* stat = sc.stat.at(d_tmp);
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kSeqStatWords * sizeof(uint32_t), st));
   mrg::SeqRankParams p;
   p.reads = d_reads;
@@ -5202,13 +5206,12 @@ int mrg_seq_rank(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per_read,
     const uint32_t width = std::min(mrg::kSeqChunkBases, max_len - mrg::kSeqChunkBases * c);
     HIP_TRY(mrg::seq_chunk_keys_launch(p, vals[cur], c, keys[cur], stat, st));
     bool second = false;
-    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[cur], keys[cur ^ 1], vals[cur], vals[cur ^ 1], p.n, 3 * width, base + sc.sort, st, &second));
+    HIP_TRY(mrg::prims::radix_sort_pairs_u64(keys[cur], keys[cur ^ 1], vals[cur], vals[cur ^ 1], p.n, 3 * width, sc.sort.at(d_tmp), st, &second));
     if (second) cur ^= 1;
   }
   HIP_TRY(mrg::seq_rank_scatter_launch(vals[cur], p.n, d_rank, st));
   uint32_t h_stat[mrg::kSeqStatWords] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kSeqStatWords, st)) return rc;
   if (h_stat[mrg::kSeqStatTooLong]) return fail(MRG_ERR_ARG, "%s: a read is longer than max_len %u, or than its %u words hold", fn, max_len, words_per_read);
   return MRG_OK;
 }
@@ -5222,22 +5225,20 @@ int mrg_collapsed_order(mrg_ctx* ctx, const uint32_t* d_quant, uint64_t n, uint3
   if (n == 0 || n >= (1ull << 31)) return fail(MRG_ERR_ARG, "%s: 1 .. 2^31 - 1 reads", fn);
   if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
   const SeqScratch sc(n, true);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_collapsed_order_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_collapsed_order_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)d_tmp;
-  uint64_t *k0 = (uint64_t*)(base + sc.k0), *k1 = (uint64_t*)(base + sc.k1);
-  uint32_t *v0 = (uint32_t*)(base + sc.v0), *v1 = (uint32_t*)(base + sc.v1);
-  uint32_t *flags = (uint32_t*)(base + sc.flags), *stat = (uint32_t*)(base + sc.stat);
+  uint64_t *k0 = sc.k0.at(d_tmp), *k1 = sc.k1.at(d_tmp);
+  uint32_t *v0 = sc.v0.at(d_tmp), *v1 = sc.v1.at(d_tmp);
+  uint32_t *flags = sc.flags.at(d_tmp), *stat = sc.stat.at(d_tmp);
   const uint32_t N = (uint32_t)n;
   // ---- the reads of the sample: flag, exclusive sums, scatter
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kSeqStatWords * sizeof(uint32_t), st));
   HIP_TRY(mrg::collapsed_flags_launch(d_quant, N, n_samples, sample, flags, stat, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, sc.scan.at(d_tmp), st));
   uint32_t k = 0, h_stat[mrg::kSeqStatWords] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(&k, flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kSeqStatWords, st)) return rc;
   if (k > N) return fail(MRG_ERR_HIP, "%s: %u rows of %u reads", fn, k, N);
   *rows = k;
   if (cap < k) return fail(MRG_ERR_ARG, "%s: %u rows do not fit a buffer of %llu", fn, k, (unsigned long long)cap);
@@ -5246,7 +5247,7 @@ int mrg_collapsed_order(mrg_ctx* ctx, const uint32_t* d_quant, uint64_t n, uint3
   const uint32_t rank_bits = bits_for(n - 1), count_bits = bits_for(h_stat[mrg::kSeqStatMaxCount]);
   HIP_TRY(mrg::collapsed_keys_launch(flags, d_quant, N, n_samples, sample, d_rank, rank_bits, k0, v0, st));
   bool second = false;
-  HIP_TRY(mrg::prims::radix_sort_pairs_u64(k0, k1, v0, v1, k, rank_bits + count_bits, base + sc.sort, st, &second));
+  HIP_TRY(mrg::prims::radix_sort_pairs_u64(k0, k1, v0, v1, k, rank_bits + count_bits, sc.sort.at(d_tmp), st, &second));
   HIP_TRY(mrg::collapsed_reverse_launch(second ? v1 : v0, k, d_order, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MRG_OK;
@@ -5263,15 +5264,11 @@ int64_t mrg_write_collapsed_fasta(const char* path, const uint64_t* reads, uint3
   if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
     return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
   if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
-  try {
+  return guarded(fn, [&] {
     const mrg::CollapsedFaArgs a{path, reads, words_per_read, stride, lens, nmask, n, quant, n_samples, sample, order, k,
                                  extra_seqs, extra_counts, n_extra};
     return (int64_t)mrg::write_collapsed_fasta(a);
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 // ------------------------------------------------------------- predict mode's candidate reads (csrc/predict_reads.hip)
@@ -5279,19 +5276,16 @@ extern "C++" {
 namespace {
 
 struct PredictScratch {  // the caller's scratch, carved into 256-byte aligned pieces
-  uint64_t raw, sel, scan, stat, total;
+  Piece<uint32_t> raw, sel, stat;
+  Piece<char> scan;
+  size_t total;
   explicit PredictScratch(uint64_t n) {
-    uint64_t used = 0;
-    auto reserve = [&](uint64_t bytes) {
-      const uint64_t at = used;
-      used += (std::max<uint64_t>(bytes, 1) + 255) & ~255ull;
-      return at;
-    };
-    raw = reserve((n + 1) * sizeof(uint32_t));
-    sel = reserve((n + 1) * sizeof(uint32_t));
-    scan = reserve(mrg::prims::scan_temp_bytes(n + 1));
-    stat = reserve(mrg::kPredictStatWords * sizeof(uint32_t));
-    total = used;
+    Carver c(256, 1);
+    raw = c.take<uint32_t>(n + 1);
+    sel = c.take<uint32_t>(n + 1);
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(n + 1));
+    stat = c.take<uint32_t>(mrg::kPredictStatWords);
+    total = c.total();
   }
 };
 
@@ -5318,11 +5312,10 @@ int mrg_predict_select(mrg_ctx* ctx, const int8_t* d_pass_id, const uint8_t* d_l
   if (min_len > max_len) return fail(MRG_ERR_ARG, "%s: the length window %u .. %u is empty", fn, min_len, max_len);
   if (count_cutoff == 0) return fail(MRG_ERR_ARG, "%s: the count cutoff must be at least 1", fn);
   const PredictScratch sc(n);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_reads_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)d_tmp;
-  uint32_t *raw = (uint32_t*)(base + sc.raw), *sel = (uint32_t*)(base + sc.sel);
+  uint32_t *raw = sc.raw.at(d_tmp), *sel = sc.sel.at(d_tmp);
   mrg::PredictSelectParams p;
   p.pass_id = d_pass_id;
   p.lens = d_lens;
@@ -5333,8 +5326,8 @@ int mrg_predict_select(mrg_ctx* ctx, const int8_t* d_pass_id, const uint8_t* d_l
   p.max_len = max_len;
   p.cutoff = count_cutoff;
   HIP_TRY(mrg::predict_flags_launch(p, d_total, raw, sel, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(raw, raw, n + 1, base + sc.scan, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(sel, sel, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(raw, raw, n + 1, sc.scan.at(d_tmp), st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(sel, sel, n + 1, sc.scan.at(d_tmp), st));
   HIP_TRY(mrg::predict_numbers_launch(raw, sel, p.n, d_raw_no, d_sel_no, st));
   uint32_t k[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&k[0], raw + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -5358,15 +5351,14 @@ int mrg_predict_sample_reads(mrg_ctx* ctx, const uint32_t* d_quant, uint64_t n, 
   if (n_samples == 0 || sample >= n_samples) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
   if (threshold == 0) return fail(MRG_ERR_ARG, "%s: the threshold must be at least 1", fn);
   const PredictScratch sc(n);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_reads_temp_bytes")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)d_tmp;
-  uint32_t* flags = (uint32_t*)(base + sc.raw);
+  uint32_t* flags = sc.raw.at(d_tmp);
   const uint32_t N = (uint32_t)n;
   // ---- count: flag, exclusive sums
   HIP_TRY(mrg::predict_sample_flags_launch(d_quant, d_no, N, n_samples, sample, threshold, flags, st));
-  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, base + sc.scan, st));
+  HIP_TRY(mrg::prims::exclusive_sum_u32(flags, flags, n + 1, sc.scan.at(d_tmp), st));
   uint32_t k = 0;
   HIP_TRY(hipMemcpyAsync(&k, flags + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -5393,11 +5385,11 @@ int mrg_predict_gather(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per
   if (stride < n || n >= (1ull << 31) || k > n) return fail(MRG_ERR_ARG, "%s: bad stride / n / k", fn);
   if (n_samples == 0 || (sample >= n_samples && sample != mrg::kPredictTotalAll)) return fail(MRG_ERR_ARG, "%s: sample %u of %u", fn, sample, n_samples);
   const PredictScratch sc(n);
-  if (tmp_bytes < sc.total || ((uintptr_t)d_tmp & 7)) return fail(MRG_ERR_ARG, "%s: scratch smaller than mrg_predict_reads_temp_bytes, or unaligned", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_reads_temp_bytes")) return rc;
   if (k == 0) return MRG_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  uint32_t* stat = (uint32_t*)((char*)d_tmp + sc.stat);
+  uint32_t* stat = sc.stat.at(d_tmp);
   HIP_TRY(hipMemsetAsync(stat, 0, mrg::kPredictStatWords * sizeof(uint32_t), st));
   mrg::PredictGatherParams p;
   p.reads = d_reads;
@@ -5417,8 +5409,7 @@ int mrg_predict_gather(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_per
   p.out_counts = d_out_counts;
   HIP_TRY(mrg::predict_gather_launch(p, stat, st));
   uint32_t h_stat[mrg::kPredictStatWords] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = read_stat(stat, h_stat, mrg::kPredictStatWords, st)) return rc;
   if (h_stat[mrg::kPredictStatBadIndex]) return fail(MRG_ERR_ARG, "%s: an index is no read of %llu", fn, (unsigned long long)n);
   if (h_stat[mrg::kPredictStatTooLong]) return fail(MRG_ERR_ARG, "%s: a read is longer than its %u words hold", fn, words_per_read);
   if (h_stat[mrg::kPredictStatOverflow]) return fail(MRG_ERR_ARG, "%s: a read's total count does not fit 32 bits", fn);
@@ -5436,15 +5427,11 @@ int64_t mrg_write_predict_fasta(const char* path, const uint64_t* reads, uint32_
   if ((words_per_read != 1 && words_per_read != 2 && words_per_read != 4 && words_per_read != 8) || stride < n)
     return fail(MRG_ERR_ARG, "%s: bad words_per_read / stride", fn);
   if (count_bytes != 4 && count_bytes != 8) return fail(MRG_ERR_ARG, "%s: count_bytes must be 4 or 8", fn);
-  try {
+  return guarded(fn, [&] {
     const mrg::PredictFastaArgs a{path, reads, words_per_read, stride, lens, nmask, n, idx, num, counts, count_bytes, k,
                                   extra_seqs, extra_nums, extra_counts, n_extra};
     return (int64_t)mrg::write_predict_fasta(a);
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 int mrg_predict_read_names(const uint32_t* num, const void* counts, uint32_t count_bytes, uint64_t k, char* blob, uint64_t blob_cap,
@@ -5680,16 +5667,12 @@ int mrg_write_a2i_detail(const char* path, const uint64_t* reads, uint32_t words
     return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: bad words_per_read / stride");
   for (uint64_t g = 0; g < n_groups; ++g)
     if (!group_names[g] || !group_targets[g]) return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: null group name / target");
-  try {
+  return guarded("mrg_write_a2i_detail", [&] {
     const mrg::A2iDetailArgs a{path, reads, words_per_read, stride, lens, nmask, n, n_blocks, block_off, block_group, block_frame,
                                block_text, group_names, group_targets, n_groups, row_read, row_count, row_flags, row_d};
     mrg::write_a2i_detail(a, lines);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "mrg_write_a2i_detail: %s", e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "mrg_write_a2i_detail: %s", e.what());
-  }
+  });
 }
 
 // ------------------------------------------------------------- packing
@@ -6057,17 +6040,13 @@ int mrg_write_trf_cluster_reports(const char* const* paths, uint32_t n_samples, 
   if (off[n_groups] != n_rows) return fail(MRG_ERR_ARG, "%s: the offsets do not cover the rows", fn);
   if (n_groups && cen_off[n_groups] && (!centers || !tallies)) return fail(MRG_ERR_ARG, "%s: null centres / tallies", fn);
   status[0] = status[1] = 0;
-  try {
+  return guarded(fn, [&] {
     const mrg::TrfClusterWriteArgs a{paths, n_samples, codes, nmask, max_len, stride, span, rpm, rows, n_rows, off, n_groups,
                                      group_sample, group_len, group_names, group_keys, group_mature, group_trailer, labels, core,
                                      order, nclust, cen_off, centers, tallies, status};
     mrg::write_trf_cluster_reports(a);
     return MRG_OK;
-  } catch (const std::invalid_argument& e) {
-    return fail(MRG_ERR_ARG, "%s: %s", fn, e.what());
-  } catch (const std::exception& e) {
-    return fail(MRG_ERR_IO, "%s: %s", fn, e.what());
-  }
+  });
 }
 
 int mrg_py3_float_repr(double value, char* out, uint64_t cap) {

@@ -8,6 +8,7 @@ materialises the reference's dict shapes from these arrays for small inputs.
 torch is used only for device memory, streams and (in mirge_amd.dist)
 torch.distributed; every kernel is launched through libmirge_amd.so.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -44,6 +45,41 @@ ISOMIR_PASS = 8  # annot slot 9 "isomiR miRNA"
 def _torch():
     import torch
     return torch
+
+
+class _Marks:
+    """Device events in a row, for a call that reports the milliseconds between them.  mark() records the next one: on the
+    current stream of `device`, or, without a device, where Event.record() itself records (the current stream of the
+    current device).  ms(a, b) waits for the last mark.  With timings None, mark() does nothing."""
+
+    def __init__(self, timings, device=None):
+        self.on, self.device, self.ev = timings is not None, device, []
+
+    def mark(self):
+        if self.on:
+            torch = _torch()
+            e = torch.cuda.Event(enable_timing=True)
+            if self.device is None:
+                e.record()
+            else:
+                e.record(torch.cuda.current_stream(self.device))
+            self.ev.append(e)
+
+    def ms(self, a, b):
+        self.ev[-1].synchronize()
+        return self.ev[a].elapsed_time(self.ev[b])
+
+
+@contextlib.contextmanager
+def _timed(timings, key):
+    """timings[key] = the device milliseconds of the block, between two events of Event.record(); nothing when timings is
+    None, and no entry when the block raises."""
+    m = _Marks(timings)
+    m.mark()
+    yield
+    m.mark()
+    if timings is not None:
+        timings[key] = m.ms(0, 1)
 
 
 class ReadSet:
@@ -212,6 +248,46 @@ class Engine:
     def _stream_ptr(self):
         torch = _torch()
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _dev(self, x, np_dtype, view=None):
+        """None or a device tensor as it is; a host array as np_dtype (its bits seen as `view`) on the device."""
+        torch = _torch()
+        if x is None or torch.is_tensor(x):
+            return x
+        a = np.ascontiguousarray(x, dtype=np_dtype)
+        return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
+
+    def _dev_reads(self, words, lens, nmask):
+        """words [W, n] / lens / nmask (or None) of a read set, contiguous on the device."""
+        words = self._dev(words, np.uint64, np.int64).contiguous()
+        nmask = self._dev(nmask, np.uint64, np.int64)
+        if nmask is not None:
+            nmask = nmask.contiguous()
+        return words, self._dev(lens, np.uint8).contiguous(), nmask
+
+    def _tmp(self, sizer, *sizes, floor=0):
+        """A stage's scratch: the bytes `sizer` (a mrg_*_temp_bytes call of one output) reports for `sizes`, at least
+        `floor`, as a uint8 device tensor.  The one place where stage scratch is allocated."""
+        torch = _torch()
+        need = C.c_uint64()
+        check(sizer(*[int(s) for s in sizes], C.byref(need)))
+        return torch.empty(max(int(need.value), floor), dtype=torch.uint8, device=self.device)
+
+    def _predict_tmp(self, n):
+        return self._tmp(self._lib.mrg_predict_reads_temp_bytes, n)
+
+    def _remap_tmp(self, n_reads, n_rows):
+        return self._tmp(self._lib.mrg_predict_remap_temp_bytes, n_reads, n_rows, floor=8)
+
+    def _screen_tmp(self, n_cand):
+        return self._tmp(self._lib.mrg_predict_screen_temp_bytes, n_cand, floor=64)
+
+    def _order_sizer(self, which):
+        """mrg_collapsed_order_temp_bytes as a sizer of one output: 0 = mrg_seq_rank's scratch, 1 = mrg_collapsed_order's."""
+        def sizer(n, out):
+            other = C.byref(C.c_uint64())
+            return self._lib.mrg_collapsed_order_temp_bytes(n, *((out, other) if which == 0 else (other, out)))
+        return sizer
 
     def _workspace(self, n):
         torch = _torch()
@@ -549,18 +625,9 @@ class Engine:
         inside the call), and `classify_call_ms`, the whole filling call (selection, table uploads, kernel; events around it).
         The rows are counted by a first call and filled by a second: the selection (two launches and a scan) runs twice."""
         torch = _torch()
-
-        def dev(x, np_dtype, view=None):
-            if x is None or torch.is_tensor(x):
-                return x
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
-        words = dev(words, np.uint64, np.int64).contiguous()
-        nmask = dev(nmask, np.uint64, np.int64)
-        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
-        ref_id, pos = dev(ref_id, np.int32).contiguous(), dev(pos, np.int32).contiguous()
-        if nmask is not None:
-            nmask = nmask.contiguous()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        pass_id = self._dev(pass_id, np.int8).contiguous()
+        ref_id, pos = self._dev(ref_id, np.int32).contiguous(), self._dev(pos, np.int32).contiguous()
         W, n = int(words.shape[0]), int(words.shape[1])
         desc = np.ascontiguousarray(table.desc, dtype=np.int32)
         text = np.ascontiguousarray(table.words, dtype=np.uint64)
@@ -584,14 +651,9 @@ class Engine:
         rec = torch.empty((max(k, 1), 8), dtype=torch.int32, device=self.device)
         mask = torch.empty((max(k, 1), mw), dtype=torch.int64, device=self.device)
         if k:
+            with _timed(timings, "classify_call_ms"):
+                call(k, idx, rec, mask)
             if timings is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            call(k, idx, rec, mask)
-            if timings is not None:
-                e1.record()
-                e1.synchronize()
-                timings["classify_call_ms"] = e0.elapsed_time(e1)
                 timings["kernel_ms"] = float(kernel_ms.value)
         return (idx.cpu().numpy().view(np.uint32)[:k], rec.cpu().numpy()[:k], mask.cpu().numpy().view(np.uint64)[:k],
                 int(counts[0]), int(counts[1]))
@@ -610,20 +672,10 @@ class Engine:
         `settle_examined`, `settle_settled` and `settle_kernel_ms`."""
         torch = _torch()
         from .a2i import BASE_CODE
-
-        def dev(x, np_dtype, view=None):
-            if x is None or torch.is_tensor(x):
-                return x
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
-        words = dev(words, np.uint64, np.int64).contiguous()
-        nmask = dev(nmask, np.uint64, np.int64)
-        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
-        ref_id = dev(ref_id, np.int32).contiguous()
-        if nmask is not None:
-            nmask = nmask.contiguous()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        pass_id, ref_id = self._dev(pass_id, np.int8).contiguous(), self._dev(ref_id, np.int32).contiguous()
         if keep is not None:
-            keep = (keep.to(torch.uint8) if torch.is_tensor(keep) else dev(np.asarray(keep) != 0, np.uint8)).contiguous()
+            keep = (keep.to(torch.uint8) if torch.is_tensor(keep) else self._dev(np.asarray(keep) != 0, np.uint8)).contiguous()
         W, n = int(words.shape[0]), int(words.shape[1])
         canon_t = np.ascontiguousarray(table.by_pass[canon_pass], dtype=np.int32)
         iso_t = np.ascontiguousarray(table.by_pass[isomir_pass], dtype=np.int32)
@@ -645,14 +697,9 @@ class Engine:
         idx = torch.empty(max(k, 1), dtype=torch.int32, device=self.device)
         rec = torch.empty((max(k, 1), 4), dtype=torch.int32, device=self.device)
         if k:
+            with _timed(timings, "align_call_ms"):
+                call(k, idx, rec)
             if timings is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            call(k, idx, rec)
-            if timings is not None:
-                e1.record()
-                e1.synchronize()
-                timings["align_call_ms"] = e0.elapsed_time(e1)
                 timings["kernel_ms"] = float(kernel_ms.value)
         if settle:
             done = (C.c_uint64 * 2)()
@@ -680,17 +727,8 @@ class Engine:
         rows are counted by a first call; the filling call is repeated only if the read set has more than 4 kept
         alignments per read."""
         torch = _torch()
-
-        def dev(x, np_dtype, view=None):
-            if x is None or torch.is_tensor(x):
-                return x
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
-        words = dev(words, np.uint64, np.int64).contiguous()
-        nmask = dev(nmask, np.uint64, np.int64)
-        lens, pass_id = dev(lens, np.uint8).contiguous(), dev(pass_id, np.int8).contiguous()
-        if nmask is not None:
-            nmask = nmask.contiguous()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        pass_id = self._dev(pass_id, np.int8).contiguous()
         W, n = int(words.shape[0]), int(words.shape[1])
         desc = np.ascontiguousarray(et.desc, dtype=np.int32)
         clusters = np.ascontiguousarray(et.clusters, dtype=np.int32)
@@ -716,14 +754,9 @@ class Engine:
             cap = 4 * k + 64
             while True:
                 hits = torch.empty((cap, 4), dtype=torch.int32, device=self.device)
+                with _timed(timings, "classify_call_ms"):
+                    call(k, cap, rec, hits)
                 if timings is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                call(k, cap, rec, hits)
-                if timings is not None:
-                    e1.record()
-                    e1.synchronize()
-                    timings["classify_call_ms"] = e0.elapsed_time(e1)
                     timings["type_kernel_ms"], timings["assign_kernel_ms"] = float(kernel_ms[0]), float(kernel_ms[1])
                 h = int(counts[2])
                 if h <= cap:
@@ -740,19 +773,9 @@ class Engine:
         timings: a dict that receives `groups_count_ms` / `groups_fill_ms` (events around the two calls) and
         `items_kernel_ms`, `read_order_kernel_ms`, `row_order_kernel_ms`, `pack_kernel_ms` (events inside the filling call)."""
         torch = _torch()
-
-        def dev(x, np_dtype, view=None):
-            if x is None or torch.is_tensor(x):
-                return x
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
-        words = dev(words, np.uint64, np.int64).contiguous()
-        nmask = dev(nmask, np.uint64, np.int64)
-        if nmask is not None:
-            nmask = nmask.contiguous()
-        lens = dev(lens, np.uint8).contiguous()
-        quant = dev(quant, np.uint32, np.int32).contiguous()
-        rec = dev(np.asarray(rec).reshape(-1, 12) if not torch.is_tensor(rec) else rec, np.int32).contiguous()
+        words, lens, nmask = self._dev_reads(words, lens, nmask)
+        quant = self._dev(quant, np.uint32, np.int32).contiguous()
+        rec = self._dev(np.asarray(rec).reshape(-1, 12) if not torch.is_tensor(rec) else rec, np.int32).contiguous()
         W, n = int(words.shape[0]), int(words.shape[1])
         S = int(quant.shape[1]) if quant.dim() == 2 else 1
         k = int(rec.shape[0])
@@ -771,16 +794,8 @@ class Engine:
                 *[None if a is None else a.ctypes.data for a in host], *[ptr(t) for t in devs], counts,
                 None if timings is None else kernel_ms, self._stream_ptr()))
 
-        def timed(key, *a):
-            if timings is None:
-                return call(*a)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call(*a)
-            e1.record()
-            e1.synchronize()
-            timings[key] = e0.elapsed_time(e1)
-        timed("groups_count_ms", 0, 0, (None,) * 4, (None,) * 5)
+        with _timed(timings, "groups_count_ms"):
+            call(0, 0, (None,) * 4, (None,) * 5)
         g = TrfGroups()
         g.n_items, B, G, R = (int(counts[i]) for i in range(4))
         g.max_len, g.has_n = int(counts[4]), bool(counts[5])
@@ -798,8 +813,8 @@ class Engine:
         g.rpm_d = torch.zeros(max(R, 1), dtype=torch.float64, device=self.device)
         rows_d = torch.zeros((max(R, 1), 3), dtype=torch.int32, device=self.device)
         if B:
-            timed("groups_fill_ms", B, R, (g.blocks, g.block_sums, g.off, g.groups),
-                  (g.codes_d, g.nmask_d, g.span_d, g.rpm_d, rows_d))
+            with _timed(timings, "groups_fill_ms"):
+                call(B, R, (g.blocks, g.block_sums, g.off, g.groups), (g.codes_d, g.nmask_d, g.span_d, g.rpm_d, rows_d))
             if (int(counts[1]), int(counts[2]), int(counts[3])) != (B, G, R):
                 raise RuntimeError("trf_sample_groups: the counting and the filling call disagree")
             if timings is not None:
@@ -820,27 +835,11 @@ class Engine:
             raise ValueError("seq_rank: words [W, n], lens [n] and nmask [W, n] must match")
         if max_len is None:
             max_len = int(lens.max()) if n else 0
-        need = (C.c_uint64(), C.c_uint64())
-        check(self._lib.mrg_collapsed_order_temp_bytes(n, C.byref(need[0]), C.byref(need[1])))
-        tmp = torch.empty(int(need[0].value), dtype=torch.uint8, device=self.device)
+        tmp = self._tmp(self._order_sizer(0), n)
         rank = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
         check(self._lib.mrg_seq_rank(self._h, words.data_ptr(), W, n, lens.data_ptr(), None if nmask is None else nmask.data_ptr(),
                                      n, int(max_len), rank.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
         return rank[:n]
-
-    def _dev_reads(self, words, lens, nmask):
-        torch = _torch()
-
-        def dev(x, np_dtype, view=None):
-            if x is None or torch.is_tensor(x):
-                return x
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            return torch.from_numpy(a if view is None else a.view(view)).to(self.device)
-        words = dev(words, np.uint64, np.int64).contiguous()
-        nmask = dev(nmask, np.uint64, np.int64)
-        if nmask is not None:
-            nmask = nmask.contiguous()
-        return words, dev(lens, np.uint8).contiguous(), nmask
 
     def collapsed_order(self, words, lens, nmask, quant, timings=None):
         """The order of every sample's <sample>.trim.collapse.fa (mrg_seq_rank once, mrg_collapsed_order per sample column):
@@ -861,15 +860,11 @@ class Engine:
             timings.update(rank_ms=0.0, order_ms=0.0)
         if n == 0:
             return [np.zeros(0, dtype=np.uint32) for _ in range(S)]
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timings is not None else None
-        if ev:
-            ev[0].record()
+        marks = _Marks(timings)
+        marks.mark()
         rank = self.seq_rank(words, lens, nmask)
-        if ev:
-            ev[1].record()
-        need = (C.c_uint64(), C.c_uint64())
-        check(self._lib.mrg_collapsed_order_temp_bytes(n, C.byref(need[0]), C.byref(need[1])))
-        tmp = torch.empty(int(need[1].value), dtype=torch.uint8, device=self.device)
+        marks.mark()
+        tmp = self._tmp(self._order_sizer(1), n)
         order = torch.empty(n, dtype=torch.int32, device=self.device)
         rows = C.c_uint64(0)
         out = []
@@ -877,10 +872,9 @@ class Engine:
             check(self._lib.mrg_collapsed_order(self._h, quant.data_ptr(), n, S, s, rank.data_ptr(), order.data_ptr(), n,
                                                 C.byref(rows), tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
             out.append(order[:int(rows.value)].cpu().numpy().view(np.uint32))
-        if ev:
-            ev[2].record()
-            ev[2].synchronize()
-            timings.update(rank_ms=ev[0].elapsed_time(ev[1]), order_ms=ev[1].elapsed_time(ev[2]))
+        marks.mark()
+        if timings is not None:
+            timings.update(rank_ms=marks.ms(0, 1), order_ms=marks.ms(1, 2))
         return out
 
     def _dev_u32(self, x, what="the array"):
@@ -896,12 +890,6 @@ class Engine:
         if t.dtype != dtype:
             raise TypeError("%s must be a %s tensor, not %s" % (what, dtype, t.dtype))
         return t
-
-    def _predict_tmp(self, n):
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_reads_temp_bytes(n, C.byref(need)))
-        torch = _torch()
-        return torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
 
     def predict_select(self, pass_id, lens, quant, min_len=16, max_len=25, count_cutoff=2):
         """Predict mode's candidate reads (mrg_predict_select; the rules of convert2Fasta.py over unmapped.csv): of the
@@ -1204,13 +1192,10 @@ class Engine:
                                              tmp.data_ptr(), tmp_b.value, C.byref(second), st))
             return (k1, v1) if second.value else (k0, v0)
 
-        def event():
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(torch.cuda.current_stream(dev))
-            return e
-        ev = [event()]
+        marks = _Marks(timings, dev)
+        marks.mark()
         skeys, svals = sorted_pairs(0, keep_d.data_ptr() if keep_d is not None else None)
-        ev.append(event())
+        marks.mark()
         member = dev_empty(T, torch.int32)
         n_valid, n_clusters = C.c_uint64(), C.c_uint64()
         check(self._lib.mrg_cluster_scan(self._h, skeys.data_ptr(), svals.data_ptr(), T, owner.data_ptr(), reads.lens.data_ptr(),
@@ -1225,14 +1210,14 @@ class Engine:
                                            tmp.data_ptr(), tmp_b.value, c_entry.data_ptr(), c_strand.data_ptr(), c_start.data_ptr(),
                                            c_end.data_ptr(), c_moff.data_ptr(), c_len.data_ptr(), c_soff.data_ptr(),
                                            C.byref(total), st))
-        ev.append(event())
+        marks.mark()
         seq = dev_empty(total.value, torch.uint8)
         c_sum = dev_empty(K, torch.int64)
         check(self._lib.mrg_cluster_assemble(self._h, skeys.data_ptr(), T, V, K, pos_bits, work.data_ptr(), work_b.value,
                                              member.data_ptr(), reads.words.data_ptr(), reads.W, reads.lens.data_ptr(), nm, n,
                                              counts_d.data_ptr(), c_start.data_ptr(), c_soff.data_ptr(), seq.data_ptr(),
                                              c_sum.data_ptr(), st))
-        ev.append(event())
+        marks.mark()
         out.update(n_valid=V,
                    entry=c_entry.cpu().numpy()[:K].view(np.uint32), strand=c_strand.cpu().numpy()[:K],
                    start=c_start.cpu().numpy()[:K].view(np.uint32), end=c_end.cpu().numpy()[:K].view(np.uint32),
@@ -1243,9 +1228,8 @@ class Engine:
             out["device"] = dict(entry=c_entry, strand=c_strand, start=c_start, end=c_end, seq_off=c_soff, seq=seq, n_clusters=K,
                                  total_len=int(total.value))
         if timings is not None:
-            ev[-1].synchronize()
             for name, a, b in (("sort_ms", 0, 1), ("scan_ms", 1, 2), ("assemble_ms", 2, 3)):
-                timings[name] = ev[a].elapsed_time(ev[b])
+                timings[name] = marks.ms(a, b)
         if sorted_rows:
             del skeys, svals
             skeys, svals = sorted_pairs(1, None)
@@ -1300,41 +1284,30 @@ class Engine:
             cache[str(dev)] = tuple(self._dev_u32(pad(np.ascontiguousarray(repeats[k], dtype=np.uint32))) for k in ("rep_off", "start", "end"))
         r_off, r_start, r_end = cache[str(dev)]
         n_entries, n_elements = int(len(repeats["rep_off"])) - 1, int(len(repeats["start"]))
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_trim_temp_bytes(K, C.byref(need)))
         e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
-        tmp = e(need.value, torch.uint8)
+        tmp = self._tmp(self._lib.mrg_predict_trim_temp_bytes, K)
         flag, rep, orig = e(K, torch.uint8), e(K, torch.int32), e(total, torch.uint8)
         kept, kept_off, kept_orig = e(K, torch.int32), e(K + 1, torch.int64), e(total, torch.uint8)
         n_kept, kept_len = C.c_uint64(), C.c_uint64()
-        ev = None
-        if timings is not None:
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            ev[0].record(torch.cuda.current_stream(dev))
+        marks = _Marks(timings, dev)
+        marks.mark()
         check(self._lib.mrg_predict_trim(self._h, K, d["entry"].data_ptr(), d["strand"].data_ptr(), d["start"].data_ptr(),
                                          d["end"].data_ptr(), d["seq_off"].data_ptr(), d["seq"].data_ptr(), total, n_entries,
                                          r_off.data_ptr(), r_start.data_ptr(), r_end.data_ptr(), n_elements, int(cutoff),
                                          flag.data_ptr(), rep.data_ptr(), orig.data_ptr(), kept.data_ptr(), kept_off.data_ptr(),
-                                         kept_orig.data_ptr(), C.byref(n_kept), C.byref(kept_len), tmp.data_ptr(), need.value,
+                                         kept_orig.data_ptr(), C.byref(n_kept), C.byref(kept_len), tmp.data_ptr(), tmp.numel(),
                                          self._stream_ptr()))
         nk, kl = int(n_kept.value), int(kept_len.value)
-        if ev:
-            ev[1].record(torch.cuda.current_stream(dev))
+        marks.mark()
         out = dict(flag=flag.cpu().numpy()[:K], rep=rep.cpu().numpy()[:K], orig=orig.cpu().numpy()[:total].tobytes(),
                    kept=kept.cpu().numpy()[:nk].view(np.uint32), kept_seq_off=kept_off.cpu().numpy()[:nk + 1].view(np.uint64),
                    kept_orig=kept_orig.cpu().numpy()[:kl].tobytes(),
                    device=dict(flag=flag, rep=rep, orig=orig, kept=kept, kept_seq_off=kept_off, kept_orig=kept_orig, n_kept=nk,
                                kept_len=kl))
-        if ev:
-            ev[2].record(torch.cuda.current_stream(dev))
-            ev[2].synchronize()
-            timings.update(trim_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+        marks.mark()
+        if timings is not None:
+            timings.update(trim_ms=marks.ms(0, 1), download_ms=marks.ms(1, 2))
         return out
-
-    def _remap_tmp(self, n_reads, n_rows):
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_remap_temp_bytes(int(n_reads), int(n_rows), C.byref(need)))
-        return _torch().empty(max(int(need.value), 8), dtype=_torch().uint8, device=self.device)
 
     def predict_trim_reads(self, reads, counts, trim5=1, trim3=3):
         """The reads of a ReadSet that a listing left unaligned, cut for the next one (mrg_predict_trim_reads).  counts: the
@@ -1417,15 +1390,10 @@ class Engine:
         torch = _torch()
         dev = self.device
         n = reads.n
-        ev = []
-
-        def mark():
-            if timings is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record(torch.cuda.current_stream(dev))
-                ev.append(e)
+        marks = _Marks(timings, dev)
+        mark = marks.mark
         mark()
-        p1 = self._list_valid_device(reads, [lib], 1, STRATUM_ALL, 0, int(seed_len), 0, N_MODE_MAX_TOTAL)
+        p1 =self._list_valid_device(reads, [lib], 1, STRATUM_ALL, 0, int(seed_len), 0, N_MODE_MAX_TOTAL)
         sel, cut = self.predict_trim_reads(reads, p1["counts"][0], *trims)
         p2 = None
         if cut is not None:
@@ -1443,8 +1411,7 @@ class Engine:
         a1 = int(p1["aligned"].sum())
         a2 = 0 if p2 is None else int(p2["aligned"].sum())
         if timings is not None:
-            ev[-1].synchronize()
-            timings.update(list_ms=ev[0].elapsed_time(ev[1]), rows_ms=ev[1].elapsed_time(ev[2]), download_ms=ev[2].elapsed_time(ev[3]))
+            timings.update(list_ms=marks.ms(0, 1), rows_ms=marks.ms(1, 2), download_ms=marks.ms(2, 3))
         return dict(rows=host, n_rows=int(host[0].shape[0]), aligned1=a1, aligned2=a2, unaligned=n - a1 - a2, device=rows)
 
     def predict_features(self, reads, counts, rows, clusters, entry_len, entry_rank, host_groups=None, timings=None,
@@ -1493,19 +1460,12 @@ class Engine:
             raise ValueError("predict_features: rows without reads, clusters or entries")
         d_soff = torch.from_numpy(soff.view(np.int64)).to(dev)
         d_orig = torch.from_numpy(np.array(orig if orig.shape[0] else np.zeros(1, np.uint8))).to(dev)
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_feature_temp_bytes(T, C.byref(need)))
         e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
-        tmp = e(max(int(need.value), 64), torch.uint8)
+        tmp = self._tmp(self._lib.mrg_predict_feature_temp_bytes, T, floor=64)
         row_group, group_off, group_cluster = e(T, torch.int32), e(T + 1, torch.int32), e(T, torch.int32)
         group_sum, group_pass = e(T, torch.int64), e(T, torch.uint8)
-        ev = []
-
-        def mark():
-            if timings is not None:
-                x = torch.cuda.Event(enable_timing=True)
-                x.record(torch.cuda.current_stream(dev))
-                ev.append(x)
+        marks = _Marks(timings, dev)
+        mark = marks.mark
         ptr = lambda t: t.data_ptr()
         G, P, S = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         mark()
@@ -1568,8 +1528,7 @@ class Engine:
                                  strand=strand, start=cl["start"], end=cl["end"], entry_len=entry_len, n_sorted=S, n_groups=G,
                                  n_clusters=K)
         if timings is not None:
-            ev[-1].synchronize()
-            timings.update(device_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+            timings.update(device_ms=marks.ms(0, 1), download_ms=marks.ms(1, 2))
         return out
 
     def predict_precursors(self, features_device, clusters=None, entry_len=None, parts_libs=(), timings=None):
@@ -1604,19 +1563,12 @@ class Engine:
         E = int(entry_len.shape[0])
         lids = np.array([self.libs[k] for k in parts_libs], dtype=np.int32)
         ebase = np.cumsum([0] + [self.indexes[k].n_ref for k in parts_libs]).astype(np.uint32)
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_precursor_temp_bytes(S, C.byref(need)))
         e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=dev)
-        tmp = e(max(int(need.value), 64), torch.uint8)
+        tmp = self._tmp(self._lib.mrg_predict_precursor_temp_bytes, S, floor=64)
         written, rec_group, rec_lo, rec_hi = e(S, torch.uint8), e(2 * S, torch.int32), e(2 * S, torch.int32), e(2 * S, torch.int32)
         rec_off = e(2 * S + 1, torch.int64)
-        ev = []
-
-        def mark():
-            if timings is not None:
-                x = torch.cuda.Event(enable_timing=True)
-                x.record(torch.cuda.current_stream(dev))
-                ev.append(x)
+        marks = _Marks(timings, dev)
+        mark = marks.mark
         ptr = lambda t: t.data_ptr()
         W, total = C.c_uint64(0), C.c_uint64(0)
         mark()
@@ -1637,8 +1589,7 @@ class Engine:
                    device_ms=None, download_ms=None)
         mark()
         if timings is not None:
-            ev[-1].synchronize()
-            out.update(device_ms=ev[0].elapsed_time(ev[1]), download_ms=ev[1].elapsed_time(ev[2]))
+            out.update(device_ms=marks.ms(0, 1), download_ms=marks.ms(1, 2))
             timings.update(device_ms=out["device_ms"], download_ms=out["download_ms"])
         return out
 
@@ -1666,11 +1617,6 @@ class Engine:
         if len(texts) == 2 and texts[0].numel() != texts[1].numel():
             raise ValueError("%s: the sequences' and the structures' bytes must be equally many" % what)
         return off, texts, int(off.numel()) - 1, int(texts[0].numel())
-
-    def _screen_tmp(self, n_cand):
-        need = C.c_uint64()
-        check(self._lib.mrg_predict_screen_temp_bytes(int(n_cand), C.byref(need)))
-        return _torch().empty(max(int(need.value), 64), dtype=_torch().uint8, device=self.device)
 
     @staticmethod
     def _p(t):
