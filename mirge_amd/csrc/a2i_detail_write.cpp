@@ -18,39 +18,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "a2i_align.hpp"
+#include "host_write.hpp"
 
 namespace mrg {
 
 namespace {
-
-const char kBase[4] = {'A', 'C', 'G', 'T'};
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 [[noreturn]] void bad_block(uint64_t b, const char* what) { throw std::invalid_argument("block " + std::to_string(b) + ": " + what); }
 
@@ -83,11 +60,7 @@ void format_blocks(const A2iDetailArgs& a, uint64_t lo, uint64_t hi, std::string
       if (at < 0 || at + L > width) bad_block(b, "a read does not fit the frame");
       std::string& line = row_text[r - r0];
       line.assign((size_t)at, '-');
-      for (int64_t i = 0; i < L; ++i) {
-        const uint64_t w = (uint64_t)(i >> 5) * a.stride + read;
-        const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-        line.push_back(is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull]);
-      }
+      unpack_read(a.reads, a.nmask, a.stride, read, (uint32_t)L, line);
       line.append((size_t)(width - at - L), '-');
       const int len = std::snprintf(num, sizeof num, "\t%u\t", a.row_count[r]);
       line.append(num, (size_t)len);
@@ -117,48 +90,24 @@ void format_blocks(const A2iDetailArgs& a, uint64_t lo, uint64_t hi, std::string
 
 void write_a2i_detail(const A2iDetailArgs& a, uint64_t* lines) {
   File out(a.path);
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::min(16, std::atoi(e)));
-  uint64_t run = 256;   // blocks per worker and round
-  if (const char* e = std::getenv("MIRGE_AMD_A2I_RUN_BLOCKS")) run = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run = env_count("MIRGE_AMD_A2I_RUN_BLOCKS", 256);  // blocks per worker and round (tests lower it)
   const uint64_t n_runs = (a.n_blocks + run - 1) / run;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_runs, 1));
+  const unsigned n_threads = writer_threads(n_runs);
   std::vector<std::string> text(n_threads);
   std::vector<uint64_t> count(n_threads, 0);
-  std::vector<std::exception_ptr> failed(n_threads);
   uint64_t total = 0;
-  for (uint64_t b0 = 0; b0 < n_runs; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_runs - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        text[t].clear();
-        count[t] = 0;
-        const uint64_t lo = (b0 + t) * run;
-        format_blocks(a, lo, std::min(a.n_blocks, lo + run), text[t], count[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) {
-      out.write(text[t]);
-      total += count[t];
-    }
-  }
+  in_batches(n_runs, n_threads,
+             [&](unsigned t, uint64_t r) {
+               text[t].clear();
+               count[t] = 0;
+               format_blocks(a, r * run, std::min(a.n_blocks, (r + 1) * run), text[t], count[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) {
+                 out.write(text[t]);
+                 total += count[t];
+               }
+             });
   out.close();
   if (lines) *lines = total;
 }

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "fm_index.hpp"
+#include "host_write.hpp"
 #include "tables.hpp"
 
 namespace mrg {
@@ -69,7 +70,6 @@ struct Entries {
 
   // reference bases [off, off + len) of entry e as ACGT
   void bases(uint64_t e, uint32_t off, uint32_t len, std::string& out) const {
-    static const char kBase[4] = {'A', 'C', 'G', 'T'};
     uint32_t le;
     const Part& q = part_of(e, le);
     const FmIndex& ix = *q.ix;
@@ -87,7 +87,7 @@ struct Entries {
     out.resize(len);
     for (uint32_t i = 0; i < len; ++i) {
       const uint64_t p = p0 + i;
-      out[i] = kBase[(ix.text[p >> 4] >> ((p & 15) * 2)) & 3u];
+      out[i] = base_char(ix.text[p >> 4] >> ((p & 15) * 2));
     }
   }
 
@@ -281,12 +281,6 @@ struct OutFile {
     if (::close(f) != 0) throw std::runtime_error(std::string("cannot close ") + path);
   }
 };
-
-unsigned writer_threads(uint64_t n_blocks) {
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
-  return (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
-}
 
 // format(b, texts) for every block b < n_blocks on worker threads; texts[f] goes to files[f], every file in block order.
 // turn = the block whose texts go out next: a worker formats its block, waits for its turn, writes, passes the turn on
@@ -572,7 +566,6 @@ void write_trimmed_clusters(const TrimmedClustersArgs& a, uint64_t* rows, uint64
 // the read cut by trim5 / trim3).  The rows come ordered by (cluster name, read name); the rows of one read on one cluster are
 // put into the byte order of their lines here, which is `sort`'s last resort.
 uint64_t write_remapped_rows(const RemappedRowsArgs& a) {
-  static const char kBase[4] = {'A', 'C', 'G', 'T'};
   if (a.n_clusters && (!a.clusters || a.clusters->names.size() != a.n_clusters))
     throw std::invalid_argument("the cluster library does not hold the clusters given");
   for (uint64_t c = 0; c < a.n_clusters; ++c)
@@ -589,8 +582,7 @@ uint64_t write_remapped_rows(const RemappedRowsArgs& a) {
       throw std::invalid_argument("row " + std::to_string(k) + " runs past the end of its cluster");
   }
   OutFile file(a.path);
-  uint64_t block = 1u << 12;
-  if (const char* e = std::getenv("MIRGE_AMD_PREDICT_BLOCK_ROWS")) block = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t block = env_count("MIRGE_AMD_PREDICT_BLOCK_ROWS", 1u << 12);  // (tests lower it)
   // a block starts at the first row at or after its nominal start that continues no (cluster, read) run
   auto run_start = [&](uint64_t k) {
     k = std::min(k, a.n_rows);
@@ -600,12 +592,8 @@ uint64_t write_remapped_rows(const RemappedRowsArgs& a) {
   auto format_row = [&](uint64_t k, std::string& out, LineScratch& t, std::string& whole) {
     const uint64_t r = a.row_read[k], c = a.row_cluster[k];
     const uint32_t full = a.lens[r];
-    whole.resize(full);
-    for (uint32_t i = 0; i < full; ++i) {
-      const uint64_t w = (uint64_t)(i >> 5) * a.stride + r;
-      const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-      whole[i] = is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull];
-    }
+    whole.clear();
+    unpack_read(a.reads, a.nmask, a.stride, r, full, whole);
     const uint32_t t5 = a.row_pass[k] ? a.trim5 : 0u, t3 = a.row_pass[k] ? a.trim3 : 0u;
     const uint32_t L = full - t5 - t3;
     const char* orig = a.kept_orig + a.kept_seq_off[c];

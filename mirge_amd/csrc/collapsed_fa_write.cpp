@@ -12,43 +12,11 @@
 #include <string>
 
 #include "collapsed_order.hpp"
+#include "host_write.hpp"
 
 namespace mrg {
 
 namespace {
-
-const char kBase[4] = {'A', 'C', 'G', 'T'};
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
-
-// the bases of read u into buf (at least 256 bytes); returns the length
-uint32_t unpack(const CollapsedFaArgs& a, uint64_t u, char* buf) {
-  const uint32_t L = a.lens[u];
-  for (uint32_t i = 0; i < L; ++i) {
-    const uint64_t w = (uint64_t)(i >> 5) * a.stride + u;
-    const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-    buf[i] = is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull];
-  }
-  return L;
-}
 
 // Python's str comparison of two ASCII strings: < 0, 0, > 0
 int compare(const char* x, size_t nx, const char* y, size_t ny) {
@@ -95,7 +63,8 @@ uint64_t write_collapsed_fasta(const CollapsedFaArgs& a) {
     if (j < a.k) {
       const uint64_t u = a.order[j];
       count = a.quant[u * a.S + a.sample];
-      L = unpack(a, u, seq);
+      L = a.lens[u];
+      unpack_read(a.reads, a.nmask, a.stride, u, L, seq);
       if (e < a.n_extra)
         take_extra = a.extra_counts[e] != count ? a.extra_counts[e] > count
                                                 : compare(a.extra_seqs[e], std::strlen(a.extra_seqs[e]), seq, L) > 0;

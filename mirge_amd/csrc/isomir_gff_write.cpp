@@ -7,17 +7,14 @@
 // A row's text is formatted once and copied to every sample that saw the read, with that sample's count.  Blocks of rows
 // are formatted by worker threads and written in block order: the files do not depend on the thread count.
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <exception>
+#include <memory>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "isomir_gff.hpp"
 
 namespace mrg {
@@ -26,7 +23,6 @@ namespace {
 
 // 3-mer -> UID character (mirGFF3 / mirtop read-UID alphabet), codons in ACGT order
 const char kUidChars[] = "@fcoladsmkhwgebpvtDnx#yiCEGSrjqHT84FVXZ6KM$AWY35LNJzU9P07IuBQOR%";
-const char kBase[4] = {'A', 'C', 'G', 'T'};
 const char* const kSnpClass[6] = {"", "", "_seed", "_central_offset", "_central", "central_supp"};
 
 struct GffArgs {
@@ -48,12 +44,6 @@ struct GffArgs {
   uint64_t n_entries;
 };
 
-void append_int(std::string& out, long long v) {
-  char num[24];
-  const int len = std::snprintf(num, sizeof num, "%lld", v);
-  out.append(num, (size_t)len);
-}
-
 void append_signed(std::string& out, int32_t v) {  // "+3" / "-2"
   if (v > 0) out.push_back('+');
   append_int(out, v);
@@ -67,7 +57,8 @@ void flush_run(std::string& out, uint32_t& run) {
 
 // rows [lo, hi): their lines appended to text[s] for every sample s that holds the read; counts[s] += lines
 void format_rows(const GffArgs& a, uint64_t lo, uint64_t hi, std::vector<std::string>& text, std::vector<uint64_t>& counts) {
-  std::string head, seq, codes;
+  std::string head, seq;
+  auto code = [](char c) { return ((c >> 1) ^ (c >> 2)) & 3; };  // A, C, G, T -> 0, 1, 2, 3 (0x41, 0x43, 0x47, 0x54)
   for (uint64_t r = lo; r < hi; ++r) {
     const int32_t* rec = a.rec + r * kIsoRecInts;
     const uint32_t flags = (uint32_t)rec[kIsoRecFlags];
@@ -88,18 +79,8 @@ void format_rows(const GffArgs& a, uint64_t lo, uint64_t hi, std::vector<std::st
     const char* name = a.entry_names[entry];
     const char* parent = a.pre_names[entry];
     if (!name || !parent) throw std::invalid_argument("row " + std::to_string(r) + ": entry without a name");
-    // the read: its text and, for the UID, its codes (4 = N)
     seq.clear();
-    codes.clear();
-    bool has_n = false;
-    for (uint32_t i = 0; i < L; ++i) {
-      const uint64_t at = (uint64_t)(i >> 5) * a.stride + read;
-      const bool is_n = a.nmask && ((a.nmask[at] >> ((i & 31) * 2)) & 1ull);
-      const uint32_t c = (uint32_t)((a.reads[at] >> ((i & 31) * 2)) & 3ull);
-      has_n |= is_n;
-      seq.push_back(is_n ? 'N' : kBase[c]);
-      codes.push_back((char)c);
-    }
+    unpack_read(a.reads, a.nmask, a.stride, read, L, seq);
     head.clear();
     head += name;
     head.push_back('\t');
@@ -111,13 +92,13 @@ void format_rows(const GffArgs& a, uint64_t lo, uint64_t hi, std::vector<std::st
     head += "\t.\t+\t.\tRead ";
     head += seq;
     head += "; UID ";
-    if (has_n) {
+    if (seq.find('N') != std::string::npos) {
       head.push_back('.');  // make_id: a 3-mer with a non-ACGT character has no code
     } else {
       const uint32_t full = L / 3, rest = L - 3 * full;
-      for (uint32_t t = 0; t < full; ++t) head.push_back(kUidChars[16 * codes[3 * t] + 4 * codes[3 * t + 1] + codes[3 * t + 2]]);
+      for (uint32_t t = 0; t < full; ++t) head.push_back(kUidChars[16 * code(seq[3 * t]) + 4 * code(seq[3 * t + 1]) + code(seq[3 * t + 2])]);
       if (rest) {  // padded with A, followed by the pad length
-        head.push_back(kUidChars[16 * codes[3 * full] + (rest == 2 ? 4 * codes[3 * full + 1] : 0)]);
+        head.push_back(kUidChars[16 * code(seq[3 * full]) + (rest == 2 ? 4 * code(seq[3 * full + 1]) : 0)]);
         head.push_back(rest == 2 ? '1' : '2');
       }
     }
@@ -187,74 +168,37 @@ void write_isomir_gff(const char* const* paths, const char* const* coldata, uint
                       const uint32_t* idx, const int32_t* rec, const uint64_t* mask, uint64_t k, const char* const* entry_names,
                       const char* const* pre_names, uint64_t n_entries, uint64_t* rows) {
   const GffArgs a{S, source, reads, W, stride, lens, nmask, n, quant, idx, rec, mask, (W + 1) / 2, entry_names, pre_names, n_entries};
-  struct Files {
-    std::vector<FILE*> f;
-    ~Files() {
-      for (FILE* x : f)
-        if (x) std::fclose(x);
-    }
-  } files;
-  files.f.assign(S, nullptr);
+  std::vector<std::unique_ptr<File>> files;
   for (uint32_t s = 0; s < S; ++s) {
-    files.f[s] = std::fopen(paths[s], "wb");
-    if (!files.f[s]) throw std::runtime_error(std::string("cannot open ") + paths[s]);
+    files.emplace_back(new File(paths[s]));
     std::string header = "# GFF3 adapted for miRNA sequencing data\n## VERSION 0.0.1\n## source-ontology: ";
     header += source;
     header += "\n## COLDATA: ";
     header += coldata[s];
     header += "\n";
-    if (std::fwrite(header.data(), 1, header.size(), files.f[s]) != header.size())
-      throw std::runtime_error(std::string("short write to ") + paths[s]);
+    files[s]->write(header);
   }
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
-  uint64_t block_rows = 1u << 15;
-  if (const char* e = std::getenv("MIRGE_AMD_GFF_BLOCK_ROWS")) block_rows = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t block_rows = env_count("MIRGE_AMD_GFF_BLOCK_ROWS", 1u << 15);  // (tests lower it)
   const uint64_t n_blocks = (k + block_rows - 1) / block_rows;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
-  std::vector<uint64_t> total(S, 0);
-  // rounds of n_threads blocks: each worker formats one block into its own S strings, then the blocks are written in order
+  const unsigned n_threads = writer_threads(n_blocks);
+  // each worker formats one block into its own S strings, then the blocks are written in order
   std::vector<std::vector<std::string>> text(n_threads, std::vector<std::string>(S));
   std::vector<std::vector<uint64_t>> counts(n_threads, std::vector<uint64_t>(S, 0));
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t b0 = 0; b0 < n_blocks; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_blocks - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        for (auto& x : text[t]) x.clear();
-        const uint64_t lo = (b0 + t) * block_rows;
-        format_rows(a, lo, std::min(k, lo + block_rows), text[t], counts[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t)
-      for (uint32_t s = 0; s < S; ++s)
-        if (!text[t][s].empty() && std::fwrite(text[t][s].data(), 1, text[t][s].size(), files.f[s]) != text[t][s].size())
-          throw std::runtime_error(std::string("short write to ") + paths[s]);
-  }
-  for (unsigned t = 0; t < n_threads; ++t)
-    for (uint32_t s = 0; s < S; ++s) total[s] += counts[t][s];
+  in_batches(n_blocks, n_threads,
+             [&](unsigned t, uint64_t b) {
+               for (auto& x : text[t]) x.clear();
+               format_rows(a, b * block_rows, std::min(k, (b + 1) * block_rows), text[t], counts[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t)
+                 for (uint32_t s = 0; s < S; ++s) files[s]->write(text[t][s]);
+             });
   for (uint32_t s = 0; s < S; ++s) {
-    FILE* f = files.f[s];
-    files.f[s] = nullptr;
-    if (std::fclose(f) != 0) throw std::runtime_error(std::string("cannot close ") + paths[s]);
-    if (rows) rows[s] = total[s];
+    files[s]->close();
+    if (rows) {
+      rows[s] = 0;
+      for (unsigned t = 0; t < n_threads; ++t) rows[s] += counts[t][s];
+    }
   }
 }
 

@@ -13,13 +13,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "fm_index.hpp"
+#include "host_write.hpp"
 #include "predict_features.hpp"
 #include "tables.hpp"
 
@@ -27,31 +26,10 @@ namespace mrg {
 
 namespace {
 
-const char kBase[4] = {'A', 'C', 'G', 'T'};
 const char kOrder[4] = {'A', 'T', 'C', 'G'};  // the reference's column order
 const char* const kHeaderHead =
     "realMicRNA\trealMicRNAName\tchr\tstartPos\tendPos\tclusterName\tclusterSeq\tmajoritySeq\tstableClusterSeq\talignedClusterSeq\t"
     "adjustedClusterSeq\tclusterSecondSeq\ttemplateSeq\tseqCount\treadCountSum\texactMatchRatio\theadUnstableLength\ttailUnstableLength\t";
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 // global entry -> (part, local entry) and the entry's bases with N where the index holds none
 struct Genome {
@@ -109,7 +87,7 @@ struct Genome {
         const uint64_t in = p - ix.seg_off[s];
         if (in < (uint64_t)ix.seg_start[s + 1] - ix.seg_start[s]) {
           const uint64_t t = (uint64_t)ix.seg_start[s] + in;
-          ch = kBase[(ix.text[t >> 4] >> ((t & 15) * 2)) & 3u];
+          ch = base_char(ix.text[t >> 4] >> ((t & 15) * 2));
         }
       }
       out.push_back(ch);
@@ -173,11 +151,7 @@ void build_frame(const FeatWriteArgs& a, uint64_t g, Frame& fr) {
     if (at < 0 || at + L > width) bad_group(g, "a read does not fit the frame");
     std::string& row = fr.rows[1 + (r - r0)];
     row.assign((size_t)at, '-');
-    for (int64_t i = 0; i < L; ++i) {
-      const uint64_t w = (uint64_t)(i >> 5) * a.stride + read;
-      const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-      row.push_back(is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull]);
-    }
+    unpack_read(a.reads, a.nmask, a.stride, read, (uint32_t)L, row);
     row.append((size_t)(width - at - L), '-');
   }
 }
@@ -389,50 +363,26 @@ void write_predict_features(const FeatWriteArgs& a, uint64_t* written) {
     header += "neighborState\tupstreamDistance\tdownstreamDistance\n";
   }
   feats.write(header);
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::min(16, std::atoi(e)));
-  uint64_t run = 64;  // groups per worker and round
-  if (const char* e = std::getenv("MIRGE_AMD_FEATURE_BLOCK_GROUPS")) run = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run = env_count("MIRGE_AMD_FEATURE_BLOCK_GROUPS", 64);  // groups per worker and round (tests lower it)
   const uint64_t n_runs = (a.n_order + run - 1) / run;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_runs, 1));
+  const unsigned n_threads = writer_threads(n_runs);
   std::vector<std::string> ftext(n_threads), ctext(n_threads);
   std::vector<uint64_t> count(n_threads, 0);
-  std::vector<std::exception_ptr> failed(n_threads);
   uint64_t lines = 0;
-  for (uint64_t b0 = 0; b0 < n_runs; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_runs - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        ftext[t].clear();
-        ctext[t].clear();
-        count[t] = 0;
-        const uint64_t lo = (b0 + t) * run;
-        for (uint64_t j = lo; j < std::min(a.n_order, lo + run); ++j) format_group(a, genome, j, ftext[t], ctext[t], count[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) {
-      feats.write(ftext[t]);
-      clus.write(ctext[t]);
-      lines += count[t];
-    }
-  }
+  in_batches(n_runs, n_threads,
+             [&](unsigned t, uint64_t r) {
+               ftext[t].clear();
+               ctext[t].clear();
+               count[t] = 0;
+               for (uint64_t j = r * run; j < std::min(a.n_order, (r + 1) * run); ++j) format_group(a, genome, j, ftext[t], ctext[t], count[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) {
+                 feats.write(ftext[t]);
+                 clus.write(ctext[t]);
+                 lines += count[t];
+               }
+             });
   feats.close();
   clus.close();
   if (written) {

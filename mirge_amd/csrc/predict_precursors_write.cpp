@@ -7,40 +7,17 @@
 // the bytes depend on neither the thread count nor the block length.
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "fm_index.hpp"
+#include "host_write.hpp"
 #include "predict_precursors.hpp"
 
 namespace mrg {
 
 namespace {
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 [[noreturn]] void bad_record(uint64_t r, const std::string& what) { throw std::invalid_argument("record " + std::to_string(r) + ": " + what); }
 
@@ -85,46 +62,22 @@ void format_record(const PrecWriteArgs& a, uint64_t r, std::string& out) {
 void write_precursors(const PrecWriteArgs& a, uint64_t* written) {
   check_all(a);
   File fa(a.path);
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::min(16, std::atoi(e)));
-  uint64_t run = 4096;  // records per worker and round
-  if (const char* e = std::getenv("MIRGE_AMD_PRECURSOR_BLOCK_RECORDS")) run = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run = env_count("MIRGE_AMD_PRECURSOR_BLOCK_RECORDS", 4096);  // records per worker and round (tests lower it)
   const uint64_t n_runs = (a.n_rec + run - 1) / run;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_runs, 1));
+  const unsigned n_threads = writer_threads(n_runs);
   std::vector<std::string> text(n_threads);
-  std::vector<std::exception_ptr> failed(n_threads);
   uint64_t bytes = 0;
-  for (uint64_t b0 = 0; b0 < n_runs; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_runs - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        text[t].clear();
-        const uint64_t lo = (b0 + t) * run;
-        for (uint64_t r = lo; r < std::min(a.n_rec, lo + run); ++r) format_record(a, r, text[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) {
-      fa.write(text[t]);
-      bytes += text[t].size();
-    }
-  }
+  in_batches(n_runs, n_threads,
+             [&](unsigned t, uint64_t b) {
+               text[t].clear();
+               for (uint64_t r = b * run; r < std::min(a.n_rec, (b + 1) * run); ++r) format_record(a, r, text[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) {
+                 fa.write(text[t]);
+                 bytes += text[t].size();
+               }
+             });
   fa.close();
   if (written) {
     written[0] = a.n_rec;

@@ -6,46 +6,21 @@
 // as extra rows whose numbers continue after the packed ones.  The whole list is checked before the file is opened: an index
 // that is no read, a number of 0 or numbers that do not increase write nothing (that holds for these list checks only: the
 // file is open while the rows are formatted, so an I/O error met later can leave a truncated file).  Runs of rows are
-// formatted by worker threads (MIRGE_AMD_TABLE_THREADS, at most 16; MIRGE_AMD_PREDICT_BLOCK_ROWS = rows per run, lowered by
-// tests) and written in order; the bytes depend on neither setting.
+// formatted by worker threads (host_write.hpp; MIRGE_AMD_PREDICT_BLOCK_ROWS = rows per run, lowered by tests) and written in
+// order; the bytes depend on neither setting.
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "predict_reads.hpp"
 
 namespace mrg {
 
 namespace {
-
-const char kBase[4] = {'A', 'C', 'G', 'T'};
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 inline uint64_t count_at(const void* counts, uint32_t count_bytes, uint64_t j) {
   return count_bytes == 8 ? ((const uint64_t*)counts)[j] : ((const uint32_t*)counts)[j];
@@ -76,11 +51,7 @@ void format_rows(const PredictFastaArgs& a, uint64_t lo, uint64_t hi, std::strin
   for (uint64_t j = lo; j < hi; ++j) {
     const uint64_t u = a.idx[j];
     const uint32_t L = a.lens[u];
-    for (uint32_t i = 0; i < L; ++i) {
-      const uint64_t w = (uint64_t)(i >> 5) * a.stride + u;
-      const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-      seq[i] = is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull];
-    }
+    unpack_read(a.reads, a.nmask, a.stride, u, L, seq);
     text.push_back('>');
     text.append(head, put_name(head, a.num[j], count_at(a.counts, a.count_bytes, j)));
     text.push_back('\n');
@@ -109,42 +80,18 @@ uint64_t write_predict_fasta(const PredictFastaArgs& a) {
     last = a.extra_nums[e];
   }
   File out(a.path);
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::min(16, std::atoi(e)));
-  uint64_t run = 65536;  // rows per worker and round
-  if (const char* e = std::getenv("MIRGE_AMD_PREDICT_BLOCK_ROWS")) run = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run = env_count("MIRGE_AMD_PREDICT_BLOCK_ROWS", 65536);  // rows per worker and round
   const uint64_t n_runs = (a.k + run - 1) / run;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_runs, 1));
+  const unsigned n_threads = writer_threads(n_runs);
   std::vector<std::string> text(n_threads);
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t b0 = 0; b0 < n_runs; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_runs - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        text[t].clear();
-        const uint64_t lo = (b0 + t) * run;
-        format_rows(a, lo, std::min(a.k, lo + run), text[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) out.write(text[t]);
-  }
+  in_batches(n_runs, n_threads,
+             [&](unsigned t, uint64_t r) {
+               text[t].clear();
+               format_rows(a, r * run, std::min(a.k, (r + 1) * run), text[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) out.write(text[t]);
+             });
   std::string tail;
   char head[48];
   for (uint64_t e = 0; e < a.n_extra; ++e) {

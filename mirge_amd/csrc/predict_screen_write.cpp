@@ -8,45 +8,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "predict_screen.hpp"
 
 namespace mrg {
 
 namespace {
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  File(const char* p, const char* mode) : path(p) {
-    f = std::fopen(p, mode);
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-  std::string read_all() {
-    std::string out;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, got);
-    if (std::ferror(f)) throw std::runtime_error("cannot read " + path);
-    return out;
-  }
-};
 
 // what Python's str.strip() and str.split() take for white space in ASCII text
 inline bool is_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= '\x1c' && c <= '\x1f'); }
@@ -212,42 +183,18 @@ uint64_t write_screened_features(const ScreenWriteArgs& a) {
     const Span h = strip(lines[0]);
     out.write(std::string(h.p, h.n) + "\t" + kHeaderTail);
   }
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::min(16, std::atoi(e)));
-  uint64_t run = 4096;  // lines per worker and round
-  if (const char* e = std::getenv("MIRGE_AMD_SCREEN_BLOCK_LINES")) run = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run = env_count("MIRGE_AMD_SCREEN_BLOCK_LINES", 4096);  // lines per worker and round (tests lower it)
   const uint64_t n_runs = (a.n_lines + run - 1) / run;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_runs, 1));
+  const unsigned n_threads = writer_threads(n_runs);
   std::vector<std::string> block(n_threads);
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t b0 = 0; b0 < n_runs; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_runs - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        block[t].clear();
-        const uint64_t lo = (b0 + t) * run;
-        for (uint64_t i = lo; i < std::min(a.n_lines, lo + run); ++i) format_line(a, lines[i + 1], i, block[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) out.write(block[t]);
-  }
+  in_batches(n_runs, n_threads,
+             [&](unsigned t, uint64_t r) {
+               block[t].clear();
+               for (uint64_t i = r * run; i < std::min(a.n_lines, (r + 1) * run); ++i) format_line(a, lines[i + 1], i, block[t]);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) out.write(block[t]);
+             });
   out.close();
   return a.n_lines;
 }

@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "tables.hpp"
 
 namespace mrg {
@@ -48,18 +49,13 @@ struct TableArgs {
 
 // rows [lo, hi) of the table as text, appended to `out`; returns the rows written, ~0 = an entry index out of range
 uint64_t format_rows(const TableArgs& a, uint64_t lo, uint64_t hi, std::string& out) {
-  static const char kBase[4] = {'A', 'C', 'G', 'T'};
   char num[24];
   uint64_t rows = 0;
   for (uint64_t r = lo; r < hi; ++r) {
     const int pass = a.pass_id[r];
     if (a.mapped != (pass >= 0)) continue;
     const uint32_t L = a.lens[r];
-    for (uint32_t i = 0; i < L; ++i) {
-      const uint64_t w = a.reads[(uint64_t)(i >> 5) * a.stride + r];
-      const bool is_n = a.nmask && ((a.nmask[(uint64_t)(i >> 5) * a.stride + r] >> ((i & 31) * 2)) & 1ull);
-      out.push_back(is_n ? 'N' : kBase[(w >> ((i & 31) * 2)) & 3ull]);
-    }
+    unpack_read(a.reads, a.nmask, a.stride, r, L, out);
     out.push_back(',');
     out.push_back(a.mapped ? '1' : '0');
     for (uint32_t s = 0; s < a.n_slots; ++s) {
@@ -88,7 +84,7 @@ uint64_t format_rows(const TableArgs& a, uint64_t lo, uint64_t hi, std::string& 
 // cache); round 6: a worker formats its block, learns where the block starts from the worker of the block in front (a
 // chain of SIZES only: it is passed on as soon as a block is formatted, not when it is written), and writes it there itself
 // with pwrite -- formatting and the writes of up to 16 blocks overlap.  Same bytes for every thread count
-// (tests/test_report_tables.py; MIRGE_AMD_TABLE_THREADS overrides the count: hardware threads, at most 16).
+// (tests/test_report_tables.py; the count is writer_threads' of host_write.hpp).
 uint64_t write_read_table(const char* path, bool mapped, const char* header, bool append, const uint64_t* reads,
                           uint32_t W, uint64_t stride, const uint8_t* lens, const uint64_t* nmask, uint64_t n,
                           const int8_t* pass_id, const int32_t* ref_id, const uint32_t* quant, uint32_t n_samples,
@@ -123,12 +119,9 @@ uint64_t write_read_table(const char* path, bool mapped, const char* header, boo
     start = std::strlen(header);
   }
   const TableArgs a{mapped, reads, W, stride, lens, nmask, pass_id, ref_id, quant, n_samples, n_slots, names, names_off};
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
   constexpr uint64_t kBlockRows = 1u << 18;
   const uint64_t n_blocks = (n + kBlockRows - 1) / kBlockRows;
-  if (n_blocks <= 1) n_threads = 1;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
+  const unsigned n_threads = writer_threads(n_blocks);
   // begin[b] = file offset of block b, known once block b - 1 is formatted (begin[0] = start)
   std::vector<std::atomic<uint64_t>> begin(n_blocks + 1);
   for (auto& x : begin) x.store(~0ull, std::memory_order_relaxed);
@@ -234,7 +227,6 @@ uint64_t write_isomir_tables(const char* isomirs_path, const char* samples_path,
                              uint64_t n, const int8_t* pass_id, const int32_t* ref_id, const uint32_t* quant, uint32_t S,
                              int32_t canon_pass, int32_t isomir_pass, const int32_t* group_of_entry, uint64_t n_entries,
                              const char* const* group_names, uint32_t n_groups, const double* filtered) {
-  static const char kBase[4] = {'A', 'C', 'G', 'T'};
   // groups in the order their first read (exact-miRNA or isomiR pass) appears; the isomiR reads of each, in read order
   std::vector<uint32_t> order;
   std::vector<uint8_t> seen(n_groups, 0);
@@ -280,11 +272,7 @@ uint64_t write_isomir_tables(const char* isomirs_path, const char* samples_path,
       out1 += name;
       out1.push_back(',');
       const uint32_t L = lens[r];
-      for (uint32_t i = 0; i < L; ++i) {
-        const uint64_t w = reads[(uint64_t)(i >> 5) * stride + r];
-        const bool is_n = nmask && ((nmask[(uint64_t)(i >> 5) * stride + r] >> ((i & 31) * 2)) & 1ull);
-        out1.push_back(is_n ? 'N' : kBase[(w >> ((i & 31) * 2)) & 3ull]);
-      }
+      unpack_read(reads, nmask, stride, r, L, out1);
       for (uint32_t s = 0; s < S; ++s) {
         counts[s] = quant[r * S + s];
         out1.push_back(',');

@@ -13,15 +13,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <memory>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
+#include "host_write.hpp"
 #include "trf_labels.hpp"
 
 namespace mrg {
@@ -76,29 +75,7 @@ std::string py3_float_repr(double v) {
 
 namespace {
 
-const char kBase[4] = {'A', 'C', 'G', 'T'};
 const char* const kTypeName[7] = {"tRF-1", "tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF"};
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  File(const File&) = delete;
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 [[noreturn]] void bad(const char* what, uint64_t at) { throw std::invalid_argument(std::string(what) + " " + std::to_string(at)); }
 
@@ -118,39 +95,6 @@ struct Group {
   uint64_t sum_count = 0;
   double sum_rpm = 0.0;
 };
-
-// tasks [0, n) on up to n_threads workers, `width` at a time; after each batch `flush(first, live)` runs on the caller
-template <class Work, class Flush>
-void in_batches(uint64_t n, unsigned n_threads, Work work, Flush flush) {
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n, 1));
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t t0 = 0; t0 < n; t0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n - t0);
-    auto run = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        work(t, t0 + t);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      run(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(run, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    flush(t0, live);
-  }
-}
 
 struct Writer {
   const TrfClusterWriteArgs& a;
@@ -226,11 +170,9 @@ struct Writer {
   void append_seq(std::string& out, uint64_t r, uint32_t L, bool dashes) const {
     const uint32_t first = a.span[r] & 0xffu, last = a.span[r] >> 8;
     if (dashes) out.append(first - 1, '-');
-    for (uint32_t p = first - 1; p < last; ++p) {
-      const uint64_t w = (uint64_t)(p >> 5) * a.stride + r;
-      const bool is_n = a.nmask && ((a.nmask[w] >> ((p & 31) * 2)) & 1ull);
-      out.push_back(is_n ? 'N' : kBase[(a.codes[w] >> ((p & 31) * 2)) & 3ull]);
-    }
+    const size_t at = out.size();
+    out.resize(at + (last - first + 1));
+    unpack_read(a.codes, a.nmask, a.stride, r, first - 1, last, &out[at]);
     if (dashes) out.append(L - last, '-');
   }
 
@@ -374,10 +316,7 @@ struct Writer {
 }  // namespace
 
 void write_trf_cluster_reports(const TrfClusterWriteArgs& a) {
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::min(16, std::max(1, std::atoi(e)));
-  uint64_t run_rows = 1u << 14;
-  if (const char* e = std::getenv("MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS")) run_rows = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run_rows = env_count("MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS", 1u << 14);  // (tests lower it)
   for (uint32_t g = 0; g < a.G; ++g)
     if (a.group_sample[g] < 0 || (uint32_t)a.group_sample[g] >= a.S || (g && a.group_sample[g] < a.group_sample[g - 1]))
       bad("groups are not in sample order at group", g);
@@ -399,6 +338,7 @@ void write_trf_cluster_reports(const TrfClusterWriteArgs& a) {
     runs.push_back(Run{g, e, s});
     g = e;
   }
+  const unsigned n_threads = writer_threads(runs.size());
   Writer w(a);
   in_batches(runs.size(), n_threads,
              [&](unsigned, uint64_t r) {

@@ -12,13 +12,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <memory>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "trf_groups.hpp"
 #include "trf_tables.hpp"
 
@@ -26,29 +25,7 @@ namespace mrg {
 
 namespace {
 
-const char kBase[4] = {'A', 'C', 'G', 'T'};
 const char* const kTypeName[7] = {"tRF-1", "tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF"};
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  File(const File&) = delete;
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 [[noreturn]] void bad(const char* what, uint64_t at) { throw std::invalid_argument(std::string(what) + " " + std::to_string(at)); }
 
@@ -98,11 +75,7 @@ void format_blocks(const TrfSampleWriteArgs& a, const std::vector<double>& rpm_s
     for (uint64_t at = (uint32_t)blk[2]; at < (uint64_t)(uint32_t)blk[2] + (uint32_t)blk[3]; ++at) {
       const Row r = row_of(a, at, s, rep);
       text.append(r.start, '-');
-      for (uint32_t i = 0; i < r.len; ++i) {
-        const uint64_t w = (uint64_t)(i >> 5) * a.stride + r.read;
-        const bool is_n = a.nmask && ((a.nmask[w] >> ((i & 31) * 2)) & 1ull);
-        text.push_back(is_n ? 'N' : kBase[(a.reads[w] >> ((i & 31) * 2)) & 3ull]);
-      }
+      unpack_read(a.reads, a.nmask, a.stride, r.read, r.len, text);
       text.append(tlen - r.start - r.len, '-');
       text.push_back('\t');
       text += kTypeName[r.type];
@@ -171,10 +144,7 @@ void write_trf_sample_reports(const TrfSampleWriteArgs& a) {
     if (read_sum[b] != a.block_sums[b]) bad("read count sum does not match the items of block", b);
 
   // ---- the reports: runs of blocks of one sample
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
-  uint64_t run_rows = 1u << 14;
-  if (const char* e = std::getenv("MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS")) run_rows = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t run_rows = env_count("MIRGE_AMD_TRF_SAMPLE_BLOCK_ROWS", 1u << 14);  // (tests lower it)
   struct Run {
     uint64_t lo, hi;
     uint32_t s;
@@ -189,36 +159,16 @@ void write_trf_sample_reports(const TrfSampleWriteArgs& a) {
   }
   std::vector<std::unique_ptr<File>> report;
   for (uint32_t s = 0; s < S; ++s) report.emplace_back(new File(a.paths[2 * s]));
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(runs.size(), 1));
+  const unsigned n_threads = writer_threads(runs.size());
   std::vector<std::string> text(n_threads);
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t r0 = 0; r0 < runs.size(); r0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, runs.size() - r0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        text[t].clear();
-        format_blocks(a, rpm_sum, runs[r0 + t].lo, runs[r0 + t].hi, text[t]);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) report[runs[r0 + t].s]->write(text[t]);
-  }
+  in_batches(runs.size(), n_threads,
+             [&](unsigned t, uint64_t r) {
+               text[t].clear();
+               format_blocks(a, rpm_sum, runs[r].lo, runs[r].hi, text[t]);
+             },
+             [&](uint64_t r0, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) report[runs[r0 + t].s]->write(text[t]);
+             });
   for (auto& f : report) f->close();
 
   // ---- the summaries: keys in order of first appearance over the blocks, sums in print order

@@ -13,12 +13,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "host_write.hpp"
 #include "trf_tables.hpp"
 
 namespace mrg {
@@ -27,34 +26,7 @@ namespace {
 
 // 3-mer -> UID character (make_id, as isomir_gff_write.cpp), codons in ACGT order
 const char kUidChars[] = "@fcoladsmkhwgebpvtDnx#yiCEGSrjqHT84FVXZ6KM$AWY35LNJzU9P07IuBQOR%";
-const char kBase[4] = {'A', 'C', 'G', 'T'};
 const char* const kTypeName[7] = {"tRF-1", "tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF"};
-
-void append_int(std::string& out, long long v) {
-  char num[24];
-  const int len = std::snprintf(num, sizeof num, "%lld", v);
-  out.append(num, (size_t)len);
-}
-
-struct File {
-  FILE* f = nullptr;
-  std::string path;
-  explicit File(const char* p) : path(p) {
-    f = std::fopen(p, "wb");
-    if (!f) throw std::runtime_error("cannot open " + path);
-  }
-  ~File() {
-    if (f) std::fclose(f);
-  }
-  void write(const std::string& s) {
-    if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw std::runtime_error("short write to " + path);
-  }
-  void close() {
-    FILE* x = f;
-    f = nullptr;
-    if (std::fclose(x) != 0) throw std::runtime_error("cannot close " + path);
-  }
-};
 
 [[noreturn]] void bad_row(uint64_t r, const char* what) { throw std::invalid_argument("row " + std::to_string(r) + ": " + what); }
 
@@ -72,7 +44,8 @@ void join(std::string& out, const std::vector<std::string>& items) {
 // rows [lo, hi): their lines appended to text; written[r] = 1 and rp[r * S + s] = float("%.3f" % RP100K) for a written row
 void format_rows(const TrfWriteArgs& a, uint64_t lo, uint64_t hi, std::string& text, std::vector<uint8_t>& written,
                  std::vector<double>& rp) {
-  std::string seq, codes;
+  std::string seq;
+  auto code = [](char c) { return ((c >> 1) ^ (c >> 2)) & 3; };  // A, C, G, T -> 0, 1, 2, 3 (0x41, 0x43, 0x47, 0x54)
   std::vector<std::string> aa_types, aa_pairs, infos, d_types, d_pairs, d_infos;
   std::vector<int32_t> reps;
   char num[400];
@@ -108,25 +81,16 @@ void format_rows(const TrfWriteArgs& a, uint64_t lo, uint64_t hi, std::string& t
       if (!a.entry_names[hit[0]] || !a.aa_types[hit[0]] || !a.anticodons[hit[0]]) bad_row(r, "an entry without amino acid");
     }
     seq.clear();
-    codes.clear();
-    bool has_n = false;
-    for (uint32_t i = 0; i < L; ++i) {
-      const uint64_t at = (uint64_t)(i >> 5) * a.stride + read;
-      const bool is_n = a.nmask && ((a.nmask[at] >> ((i & 31) * 2)) & 1ull);
-      const uint32_t c = (uint32_t)((a.reads[at] >> ((i & 31) * 2)) & 3ull);
-      has_n |= is_n;
-      seq.push_back(is_n ? 'N' : kBase[c]);
-      codes.push_back((char)c);
-    }
+    unpack_read(a.reads, a.nmask, a.stride, read, L, seq);
     text += seq;
     text.push_back('\t');
-    if (has_n) {
+    if (seq.find('N') != std::string::npos) {
       text.push_back('.');  // make_id: a 3-mer with a non-ACGT character has no code
     } else {
       const uint32_t full = L / 3, rest = L - 3 * full;
-      for (uint32_t t = 0; t < full; ++t) text.push_back(kUidChars[16 * codes[3 * t] + 4 * codes[3 * t + 1] + codes[3 * t + 2]]);
+      for (uint32_t t = 0; t < full; ++t) text.push_back(kUidChars[16 * code(seq[3 * t]) + 4 * code(seq[3 * t + 1]) + code(seq[3 * t + 2])]);
       if (rest) {  // padded with A, followed by the pad length
-        text.push_back(kUidChars[16 * codes[3 * full] + (rest == 2 ? 4 * codes[3 * full + 1] : 0)]);
+        text.push_back(kUidChars[16 * code(seq[3 * full]) + (rest == 2 ? 4 * code(seq[3 * full + 1]) : 0)]);
         text.push_back(rest == 2 ? '1' : '2');
       }
     }
@@ -214,45 +178,21 @@ void write_trf_tables(const TrfWriteArgs& a, uint64_t* rows) {
             ")\tamino acid all hits\tamino acid-anticodon all hits\ttRF information all hits\tamino acid all deduplicated "
             "hits\tamino acid-anticodon all deduplicated hits\ttRF information all deduplicated hits\tamino acid one hit\tamino "
             "acid-anticodon one hit\ttRF information one hit\n");
-  unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* e = std::getenv("MIRGE_AMD_TABLE_THREADS")) n_threads = (unsigned)std::max(1, std::atoi(e));
-  uint64_t block_rows = 1u << 14;
-  if (const char* e = std::getenv("MIRGE_AMD_TRF_BLOCK_ROWS")) block_rows = (uint64_t)std::max(1, std::atoi(e));  // (tests)
+  const uint64_t block_rows = env_count("MIRGE_AMD_TRF_BLOCK_ROWS", 1u << 14);  // (tests lower it)
   const uint64_t n_blocks = (a.k + block_rows - 1) / block_rows;
-  n_threads = (unsigned)std::min<uint64_t>(n_threads, std::max<uint64_t>(n_blocks, 1));
+  const unsigned n_threads = writer_threads(n_blocks);
   std::vector<uint8_t> written(a.k, 0);
   std::vector<double> rp(a.k * S, 0.0);
-  // rounds of n_threads blocks: each worker formats one block into its own string, then the blocks are written in order
+  // each worker formats one block into its own string, then the blocks are written in order
   std::vector<std::string> text(n_threads);
-  std::vector<std::exception_ptr> failed(n_threads);
-  for (uint64_t b0 = 0; b0 < n_blocks; b0 += n_threads) {
-    const unsigned live = (unsigned)std::min<uint64_t>(n_threads, n_blocks - b0);
-    auto work = [&](unsigned t) {
-      try {
-        failed[t] = nullptr;
-        text[t].clear();
-        const uint64_t lo = (b0 + t) * block_rows;
-        format_rows(a, lo, std::min(a.k, lo + block_rows), text[t], written, rp);
-      } catch (...) {
-        failed[t] = std::current_exception();
-      }
-    };
-    if (live == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      try {
-        for (unsigned t = 0; t < live; ++t) pool.emplace_back(work, t);
-      } catch (...) {
-        for (auto& th : pool) th.join();
-        throw;
-      }
-      for (auto& th : pool) th.join();
-    }
-    for (unsigned t = 0; t < live; ++t)
-      if (failed[t]) std::rethrow_exception(failed[t]);
-    for (unsigned t = 0; t < live; ++t) tsv.write(text[t]);
-  }
+  in_batches(n_blocks, n_threads,
+             [&](unsigned t, uint64_t b) {
+               text[t].clear();
+               format_rows(a, b * block_rows, std::min(a.k, (b + 1) * block_rows), text[t], written, rp);
+             },
+             [&](uint64_t, unsigned live) {
+               for (unsigned t = 0; t < live; ++t) tsv.write(text[t]);
+             });
   tsv.close();
 
   // W2C:749-800: counts per predefined tRF entity, in row order
