@@ -1204,6 +1204,47 @@ int mrg_write_screened_features(const char *features_path, const char *out_path,
                                 const int32_t *feat, const uint64_t *p_off, const char *p_seq, const char *p_str,
                                 const double *p_mfe, uint64_t *written);
 
+/* Predict mode's classification (reference miRge2.0.py:647-648: utils/preprocess_featureFiles.py and utils/model_predict.py;
+ * csrc/predict_svm.hip, csrc/predict_model_write.cpp; the rule: tests/predict_model_model.py).  The model's
+ * arrays are the caller's (mirge_amd/svm_model.py reads them from the user's model file); everything is float64.
+ *
+ *   mrg_predict_model_filter  HOST: the screened table into the reference's three filter files, byte for byte -- dataset_path
+ *       (`<tmp>.csv`: columns [0, 1, 5] + [10..]; rows with readCountSum >= 10, seqCount >= 3 and no cell from seqCount on
+ *       that equals N), refined_tmp_path (rows whose pruned_precusor_str is not None) and refined_path (the columns `namelist`
+ *       names, one a line) -- and into *handle: the refined rows' three leading cells and their raw feature rows [n][nf] for
+ *       `features` (the model's selected names in its order, one a line; nf of them).  A selected name is a column in which
+ *       every retained cell is a number; else `<column>_<value>` of a column that is not (1 where the cell equals the value);
+ *       else 0 for every row.  counts [4]: the table's rows, the first filter's, the second's, and the selected names whose
+ *       own column holds a cell that is no number (0 for every row, as pandas' get_dummies makes them).  A table without a
+ *       header line, without the columns the filters name, or with a count that is no whole number is MRG_ERR_ARG; nothing is
+ *       written then.  A table without retained rows gives header-only files (the reference raises there).
+ *   mrg_predict_model_rows  copies the feature rows [n][nf] out of the handle.
+ *   mrg_predict_svm  DEVICE, asynchronous on `stream`, no scratch: one lane per row of d_x [n_rows][nf] (raw rows).  The row is
+ *       standardised ((x - d_mean) / d_scale, [nf]); the decision value is the sum of d_coef[i] exp(-gamma |z - d_sv[i]|^2)
+ *       over the support vectors d_sv [n_sv][nf] IN THEIR STORED ORDER, each distance in the (z - sv)^2 form, plus intercept
+ *       (sklearn's decision_function).  d_pred [n_rows] int8 = -1 where it is negative, else 1; d_dec [n_rows]; d_prob
+ *       [n_rows][2] = libsvm's svm_predict_probability for the classes (-1, 1): sigmoid_predict with prob_a / prob_b, the clip
+ *       to [1e-7, 1 - 1e-7] and multiclass_probability (eps 0.005 / 2, at most 100 rounds) per row.  No atomics: a row's
+ *       results depend on the row and the model alone.  1 <= nf <= 64, n_sv >= 1, n_rows < 2^31; n_rows = 0 launches nothing.
+ *   mrg_predict_model_write  HOST: detailed_path (`predictedValue,probability,` and the three leading columns: 1 or -1, the
+ *       larger of the row's two probabilities as Python's repr prints it, the cells as text) and novel_path (the rows
+ *       predicted 1 with a probability of at least 0.8, by (probability, line) descending).  pred [n], prob [n][2] on the
+ *       host.  *predicted = rows predicted 1, *kept = rows of the novel list.  Worker threads: MIRGE_AMD_TABLE_THREADS.
+ *   mrg_predict_model_free  releases the handle.
+ *   mrg_format_repr  Python's repr of a double (the shortest digits that read back) into buf [cap], NUL-terminated.
+ */
+int mrg_predict_model_filter(const char *table_path, const char *dataset_path, const char *refined_tmp_path,
+                             const char *refined_path, const char *namelist, const char *features, uint32_t nf,
+                             uint64_t *counts, void **handle);
+int mrg_predict_model_rows(void *handle, double *x);
+int mrg_predict_svm(mrg_ctx *ctx, uint64_t n_rows, const double *d_x, uint32_t nf, const double *d_mean, const double *d_scale,
+                    const double *d_sv, const double *d_coef, uint64_t n_sv, double intercept, double gamma, double prob_a,
+                    double prob_b, int8_t *d_pred, double *d_dec, double *d_prob, void *stream);
+int mrg_predict_model_write(void *handle, const int8_t *pred, const double *prob, const char *detailed_path,
+                            const char *novel_path, uint64_t *predicted, uint64_t *kept);
+void mrg_predict_model_free(void *handle);
+int mrg_format_repr(double v, char *buf, uint32_t cap);
+
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are

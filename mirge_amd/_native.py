@@ -254,6 +254,16 @@ SIGNATURES = {
     "mrg_write_pruned_fasta": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "mrg_write_screened_features": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mrg_predict_model_filter": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]),
+    "mrg_predict_model_rows": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mrg_predict_svm": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "mrg_predict_model_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]),
+    "mrg_predict_model_free": (None, [C.c_void_p]),
+    "mrg_format_repr": (C.c_int, [C.c_double, C.c_char_p, C.c_uint32]),
     "mrg_annotate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.POINTER(PassCfg), C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PassStats),

@@ -33,7 +33,11 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     resident genome on the GPU: `..._sorted_features_precusor.fa`, the file the reference feeds to RNAfold;
     `--novel-screen` (implies `--novel-precursors`; needs `-pr <dir>` holding RNAfold, or `--fold-cmd <executable>`) folds
     that file once, picks and prunes the candidates on the GPU, folds the pruned ones once, and writes
-    `..._sorted_features_updated_stableClusterSeq_15.tsv`, the table the reference's SVM reads.
+    `..._sorted_features_updated_stableClusterSeq_15.tsv`, the table the reference's SVM reads;
+    `--novel-predict` (implies `--novel-screen`; needs `--models <dir>` holding miRge2.0's `<species>_svc_model.pkl` and
+    `total_features_namelist.txt`; the species is `-sp`) filters that table as preprocess_featureFiles does, classifies the rows
+    with the model's SVM on the GPU and writes `predicted_<sample>_detailed.csv` and `<sample>_novel_miRNAs_miRge2.0.csv`, as
+    the reference's model_predict does.  The report of write_novel_report (PDFs) is not written.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -51,7 +55,8 @@ def novel_stages(args):
     """(reads, clusters, trim, map): which of predict mode's stages the `--novel-*` options ask for; each implies the ones
     before it."""
     novel_map = bool(getattr(args, "novel_map", False)) or bool(getattr(args, "novel_features", False)) or \
-        bool(getattr(args, "novel_precursors", False)) or bool(getattr(args, "novel_screen", False))
+        bool(getattr(args, "novel_precursors", False)) or bool(getattr(args, "novel_screen", False)) or \
+        bool(getattr(args, "novel_predict", False))
     novel_trim = novel_map or bool(getattr(args, "novel_trim", False))
     novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
     novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
@@ -112,6 +117,12 @@ def build_parser():
                         "RNAfold over the pruned ones, and their features and the choice on the GPU "
                         "(<table>_features_updated_stableClusterSeq_15.tsv, as the reference's screen_precusor_candidates writes it); "
                         "needs -pr or --fold-cmd")
+    p.add_argument("--novel-predict", dest="novel_predict", action="store_true",
+                   help="extension: --novel-screen, then the reference's preprocess_featureFiles and model_predict: the three filter "
+                        "files, the SVM of the species' model on the GPU, predicted_<sample>_detailed.csv and "
+                        "<sample>_novel_miRNAs_miRge2.0.csv; needs --models")
+    p.add_argument("--models", default=None, dest="models", metavar="<dir>",
+                   help="extension: the directory of miRge2.0's model files (<species>_svc_model.pkl, total_features_namelist.txt)")
     p.add_argument("-pr", default=None, dest="rnafoldBinary", metavar="<dir>", help="the directory RNAfold is in (--novel-screen)")
     p.add_argument("--fold-cmd", default=None, dest="fold_cmd", metavar="<executable>",
                    help="extension: the fold command itself, started as `<executable> --noPS --noLP` with the FASTA on its "
@@ -242,13 +253,19 @@ def annotate_main(args, engine_factory=None, materialize=False):
         if rank == 0:
             print(msg, file=out)
         sys.exit(1)
-    novel_fold = None
-    if bool(getattr(args, "novel_screen", False)):   # before any GPU work: MAIN's check of -pr
+    novel_fold = novel_classifier = None
+    novel_predict = bool(getattr(args, "novel_predict", False))
+    if bool(getattr(args, "novel_screen", False)) or novel_predict:   # before any GPU work: MAIN's check of -pr
         from . import predict as _predict
         try:
             novel_fold = _predict.fold_command(_predict.resolve_fold_cmd(getattr(args, "rnafoldBinary", None), getattr(args, "fold_cmd", None)))
         except ValueError as e:
             novel_die(str(e))
+    if novel_predict:   # ... and the model file and the namelist, opened and validated
+        try:
+            novel_classifier = _predict.classifier_files(getattr(args, "models", None), sp)
+        except (OSError, ValueError) as e:
+            novel_die("--novel-predict: %s" % e)
     if novel_reads:
         try:
             novel_min, novel_max, novel_cc = int(args.minLength), int(args.maxLength), int(args.countCutoff)
@@ -598,7 +615,7 @@ def annotate_main(args, engine_factory=None, materialize=False):
                 predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
                                               seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
                                               remap=novel_map, features=novel_features, precursors=novel_precursors,
-                                              screen=novel_screen, fold=novel_fold)
+                                              screen=novel_screen, fold=novel_fold, classifier=novel_classifier)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

@@ -33,6 +33,7 @@
 #include "predict_precursors.hpp"
 #include "predict_reads.hpp"
 #include "predict_screen.hpp"
+#include "predict_svm.hpp"
 #include "prims.hpp"
 #include "sa_build.hpp"
 #include "tables.hpp"
@@ -4027,6 +4028,80 @@ int mrg_write_screened_features(const char* features_path, const char* out_path,
     *written = mrg::write_screened_features(a);
     return MRG_OK;
   });
+}
+
+// ------------------------------------------- predict mode: the SVM (csrc/predict_svm.hip, csrc/predict_model_write.cpp)
+int mrg_predict_model_filter(const char* table_path, const char* dataset_path, const char* refined_tmp_path, const char* refined_path,
+                             const char* namelist, const char* features, uint32_t nf, uint64_t* counts, void** handle) {
+  const char* fn = "mrg_predict_model_filter";
+  if (!table_path || !dataset_path || !refined_tmp_path || !refined_path || !namelist || !features || !counts || !handle)
+    return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *handle = nullptr;
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  return guarded(fn, [&] {
+    std::unique_ptr<mrg::ModelTable> t(new mrg::ModelTable);
+    const mrg::ModelFilterArgs a{table_path, dataset_path, refined_tmp_path, refined_path, namelist, features};
+    mrg::filter_model_table(a, t.get());
+    if (t->nf != nf) return fail(MRG_ERR_ARG, "%s: %u selected names for nf = %u", fn, t->nf, nf);
+    counts[0] = t->n_table;
+    counts[1] = t->n_dataset;
+    counts[2] = t->n_refined;
+    counts[3] = t->n_stray;
+    *handle = t.release();
+    return MRG_OK;
+  });
+}
+
+int mrg_predict_model_rows(void* handle, double* x) {
+  const char* fn = "mrg_predict_model_rows";
+  if (!handle) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  const mrg::ModelTable* t = static_cast<const mrg::ModelTable*>(handle);
+  if (t->x.size() && !x) return fail(MRG_ERR_ARG, "%s: null buffer", fn);
+  if (t->x.size()) std::memcpy(x, t->x.data(), t->x.size() * sizeof(double));
+  return MRG_OK;
+}
+
+int mrg_predict_svm(mrg_ctx* ctx, uint64_t n_rows, const double* d_x, uint32_t nf, const double* d_mean, const double* d_scale,
+                    const double* d_sv, const double* d_coef, uint64_t n_sv, double intercept, double gamma, double prob_a, double prob_b,
+                    int8_t* d_pred, double* d_dec, double* d_prob, void* stream) {
+  const char* fn = "mrg_predict_svm";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (nf < 1 || nf > mrg::kSvmMaxFeatures) return fail(MRG_ERR_ARG, "%s: nf = %u; 1 to %u features are taken", fn, nf, mrg::kSvmMaxFeatures);
+  if (n_sv < 1 || n_sv > 0x7fffffffull / nf) return fail(MRG_ERR_ARG, "%s: n_sv = %llu; at least one, and n_sv nf below 2^31", fn, (unsigned long long)n_sv);
+  if (n_rows > 0x7fffffffull / nf) return fail(MRG_ERR_ARG, "%s: n_rows = %llu; n_rows nf must stay below 2^31", fn, (unsigned long long)n_rows);
+  if (!(gamma > 0.0) || !std::isfinite(gamma) || !std::isfinite(intercept) || !std::isfinite(prob_a) || !std::isfinite(prob_b))
+    return fail(MRG_ERR_ARG, "%s: gamma must be positive, and gamma, intercept, prob_a and prob_b finite", fn);
+  if (n_rows == 0) return MRG_OK;
+  if (!d_x || !d_mean || !d_scale || !d_sv || !d_coef || !d_pred || !d_dec || !d_prob) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const mrg::SvmModelDev m{nf, (uint32_t)n_sv, d_mean, d_scale, d_sv, d_coef, intercept, gamma, prob_a, prob_b};
+  HIP_TRY(mrg::predict_svm_launch(n_rows, d_x, m, d_pred, d_dec, d_prob, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_predict_model_write(void* handle, const int8_t* pred, const double* prob, const char* detailed_path, const char* novel_path,
+                            uint64_t* predicted, uint64_t* kept) {
+  const char* fn = "mrg_predict_model_write";
+  if (!handle || !detailed_path || !novel_path || !predicted || !kept) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  const mrg::ModelTable* t = static_cast<const mrg::ModelTable*>(handle);
+  *predicted = *kept = 0;
+  if (t->n_refined && (!pred || !prob)) return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  return guarded(fn, [&] {
+    mrg::write_model_results(*t, pred, prob, detailed_path, novel_path, predicted, kept);
+    return MRG_OK;
+  });
+}
+
+void mrg_predict_model_free(void* handle) { delete static_cast<mrg::ModelTable*>(handle); }
+
+int mrg_format_repr(double v, char* buf, uint32_t cap) {
+  const char* fn = "mrg_format_repr";
+  if (!buf) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  std::string s;
+  mrg::append_repr(s, v);
+  if (s.size() + 1 > cap) return fail(MRG_ERR_ARG, "%s: %zu characters do not fit", fn, s.size());
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return MRG_OK;
 }
 
 // ----------------------------------------------------- host convenience

@@ -1707,6 +1707,30 @@ class Engine:
                                                   tmp.data_ptr(), tmp.numel(), self._stream_ptr()))
         return best.cpu().numpy()
 
+    # ---- predict mode: the SVM of the model file (csrc/predict_svm.hip)
+    def predict_svm(self, x, model):
+        """mrg_predict_svm: sklearn's predict, decision_function and predict_proba of the model file's scaler and SVC for raw
+        feature rows x [n, nf] (float64; a host array or a device tensor).  model: svm_model.SvmModel.  Returns host arrays:
+        pred (int8 [n], 1 or -1), dec (float64 [n]) and prob (float64 [n, 2]: class -1, class 1)."""
+        torch = _torch()
+        nf, n_sv = int(model.sv.shape[1]), int(model.sv.shape[0])
+        xd = self._screen_dev(x.reshape(-1) if torch.is_tensor(x) else np.asarray(x, dtype=np.float64).reshape(-1), np.float64,
+                              torch.float64, "predict_svm: x")
+        if xd.numel() % nf:
+            raise ValueError("predict_svm: x must hold rows of the model's %d features" % nf)
+        if model.mean.shape != (nf,) or model.scale.shape != (nf,) or model.coef.shape != (n_sv,):
+            raise ValueError("predict_svm: the model's mean and scale [nf], sv [n_sv, nf] and coef [n_sv] must match")
+        n = int(xd.numel()) // nf
+        up = lambda a, what: self._screen_dev(np.asarray(a).reshape(-1), np.float64, torch.float64, "predict_svm: " + what)
+        mean, scale, sv, coef = up(model.mean, "mean"), up(model.scale, "scale"), up(model.sv, "sv"), up(model.coef, "coef")
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        pred, dec, prob = e(n, torch.int8), e(n, torch.float64), e(2 * n, torch.float64)
+        p = self._p
+        check(self._lib.mrg_predict_svm(self._h, n, p(xd), nf, p(mean), p(scale), p(sv), p(coef), n_sv, float(model.intercept),
+                                        float(model.gamma), float(model.probA), float(model.probB), p(pred), p(dec), p(prob),
+                                        self._stream_ptr()))
+        return dict(pred=pred.cpu().numpy(), dec=dec.cpu().numpy(), prob=prob.cpu().numpy().reshape(n, 2))
+
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
         mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask

@@ -36,6 +36,17 @@ _neighbors; mrg_write_predict_features) and adds
     <out_stem>_vs_representative_seq_modified_selected_sorted_features.tsv    one line per cluster with a stable stretch
     <out_stem>_vs_representative_seq_modified_selected_sorted_cluster.txt     the aligned members of every cluster that got that far
 
+With `classify=True, models=<dir>, species=...` / `--classify --models DIR [-sp SPECIES]` (needs the screening: `screen=True,
+fold=...` / `--screen`) the last two calls before the report (miRge2.0.py:647-648, preprocess_featureFiles and model_predict) run
+over the screened table (classify_candidates: the native reader and writers of ScreenedTable, Engine.predict_svm =
+mrg_predict_svm; the model file read by mirge_amd/svm_model.py, before any device work) and add, next to the table,
+
+    <tmp>.csv, <tmp>_refined_tmp.csv, <tmp>_refined_features.csv    the three filter files, <tmp> = ..._vs_dataset_15
+    predicted_<sample>_detailed.csv                                   label and probability of every refined row
+    <sample>_novel_miRNAs_miRge2.0.csv                                the rows predicted 1 with a probability of 0.8 or more
+
+The report of write_novel_report (PDFs through matplotlib and forgi) is not built.
+
 The device is $MIRGE_AMD_GPU (default 0).  Limits: reads up to 255 nt, fewer than 2^32 - 1 alignment rows, positions
 below 2^31; beyond them the call fails naming the limit and writes nothing.
 """
@@ -822,6 +833,100 @@ def write_screened_features(features_path, out_path, best, feat, p_off, p_seq, p
     return int(written.value)
 
 
+def classifier_files(model_dir, species):
+    """The model file of `species` and the namelist from `model_dir`, opened and validated: (svm_model.SvmModel, names).
+    No GPU is touched: the callers run this before any device work, as they check RNAfold.  OSError or ValueError."""
+    from . import svm_model
+    if not model_dir:
+        raise ValueError("the classification needs the directory of the model files (miRge2.0's models/)")
+    return svm_model.load_model(model_dir, species), svm_model.read_namelist(model_dir)
+
+
+def classified_paths(screened_path):
+    """The five files preprocess_featureFiles and model_predict write next to the screened table, by the reference's names."""
+    d, base = os.path.dirname(screened_path), os.path.basename(screened_path)
+    tmp = "_".join(base.split("_")[:-9]) + "_dataset_" + base.split("_")[-1].split(".")[0]
+    sample = "_".join((tmp + "_refined_features.csv").split("_")[2:-5])
+    return dict(dataset=os.path.join(d, tmp + ".csv"), refined_tmp=os.path.join(d, tmp + "_refined_tmp.csv"),
+                refined=os.path.join(d, tmp + "_refined_features.csv"), detailed=os.path.join(d, "predicted_" + sample + "_detailed.csv"),
+                novel=os.path.join(d, sample + "_novel_miRNAs_miRge2.0.csv"))
+
+
+class ScreenedTable:
+    """mrg_predict_model_filter: a screened table read by the native reader, which writes the reference's three filter files
+    (paths["dataset"], ["refined_tmp"], ["refined"]) on the way.  rows: the table's, the first filter's and the second's row
+    counts; stray: the selected names whose column holds a cell that is no number (0 for every row); x: the raw feature rows
+    [refined, nf] for the model's selected names.  write() is mrg_predict_model_write.  A context manager: the native side is
+    released on exit."""
+
+    def __init__(self, screened_path, model, namelist):
+        from . import _native
+        self._lib = _native.load()
+        self.paths = classified_paths(screened_path)
+        counts, self._h = (C.c_uint64 * 4)(), C.c_void_p()
+        enc = lambda names: "\n".join(names).encode("utf-8")
+        nf = len(model.feature_names)
+        _native.check(self._lib.mrg_predict_model_filter(
+            os.fsencode(screened_path), os.fsencode(self.paths["dataset"]), os.fsencode(self.paths["refined_tmp"]),
+            os.fsencode(self.paths["refined"]), enc(namelist), enc(model.feature_names), nf, counts, C.byref(self._h)))
+        self.rows, self.stray = tuple(int(c) for c in counts[:3]), int(counts[3])
+        self.x = np.zeros((self.rows[2], nf), np.float64)
+        try:
+            _native.check(self._lib.mrg_predict_model_rows(self._h, _ptr(self.x.reshape(-1))))
+        except Exception:
+            self.close()
+            raise
+
+    def write(self, pred, prob, threads=None):
+        """`predicted_<sample>_detailed.csv` and `<sample>_novel_miRNAs_miRge2.0.csv` from pred [n] (1 or -1) and prob [n, 2]
+        (class -1, class 1).  Returns (rows predicted 1, rows of the novel list)."""
+        from . import _native
+        pred = np.ascontiguousarray(pred, dtype=np.int8)
+        prob = np.ascontiguousarray(prob, dtype=np.float64).reshape(-1)
+        if pred.shape != (self.rows[2],) or prob.shape != (2 * self.rows[2],):
+            raise ValueError("ScreenedTable.write: pred [n] and prob [n, 2] for the table's %d refined rows" % self.rows[2])
+        predicted, kept = C.c_uint64(), C.c_uint64()
+        with _writer_threads(threads):
+            _native.check(self._lib.mrg_predict_model_write(self._h, _ptr(pred), _ptr(prob), os.fsencode(self.paths["detailed"]),
+                                                            os.fsencode(self.paths["novel"]), C.byref(predicted), C.byref(kept)))
+        return int(predicted.value), int(kept.value)
+
+    def close(self):
+        if self._h:
+            self._lib.mrg_predict_model_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def classify_candidates(engine, screened_path, model_dir, species, threads=None, timings=None, classifier=None):
+    """The reference's miRge2.0.py:647-648 (preprocess_featureFiles, model_predict) for one screened table
+    `*_features_updated_stableClusterSeq_15.tsv`: the three filter files by the native reader (ScreenedTable), the SVM on the
+    device (Engine.predict_svm) and `predicted_<sample>_detailed.csv` / `<sample>_novel_miRNAs_miRge2.0.csv` by the native
+    writer.  classifier: what classifier_files returned (None: read from model_dir now).  Returns a dict: table, dataset,
+    refined (rows per filter), stray (selected names whose column holds a cell that is no number: 0 for every row),
+    predicted (rows predicted 1), kept (rows of the novel list), paths, and the device's pred, dec and prob.  timings gets
+    read_s, device_s and write_s."""
+    import time
+    model, namelist = classifier if classifier is not None else classifier_files(model_dir, species)
+    clock = time.perf_counter
+    t0 = clock()
+    with ScreenedTable(screened_path, model, namelist) as table:
+        t1 = clock()
+        res = engine.predict_svm(table.x, model)
+        t2 = clock()
+        predicted, kept = table.write(res["pred"], res["prob"], threads)
+        t3 = clock()
+        if timings is not None:
+            timings.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2)
+        return dict(table=table.rows[0], dataset=table.rows[1], refined=table.rows[2], stray=table.stray, predicted=predicted, kept=kept,
+                    paths=table.paths, pred=res["pred"], dec=res["dec"], prob=res["prob"])
+
+
 def _partners(structure):
     """{position: partner} of a dot-bracket structure; ValueError where the brackets do not balance."""
     open_at, pairs = [], {}
@@ -980,9 +1085,10 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False, screen=False, fold=None):
+                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False, screen=False, fold=None, classifier=None):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
-    as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`)."""
+    as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`); classifier: what
+    classifier_files returned (None: no classification)."""
     from .engine import STRATUM_ALL
     if remap and trim is None:
         raise ValueError("remap needs trim: the reads are mapped to the clusters the trim retains")
@@ -994,6 +1100,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
         raise ValueError("screen needs precursors: the candidates it folds are the windows cut there")
     if screen and fold is None:
         raise ValueError("screen needs fold: a callable (fasta_path, str_path), or the path of RNAfold")
+    if classifier is not None and not screen:
+        raise ValueError("classify needs screen: the SVM reads the screened table")
     keys, parts = genome_libraries(engine, genome_prefix)
     if trim is not None:
         repeats, cutoff = trim
@@ -1031,6 +1139,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
                 cl["precursors"] = cluster_precursors(engine, cl["features"], trimmed, parts, out_stem, parts_libs=keys)
                 if screen:
                     cl["screen"] = screen_precursors(engine, cl["features"], cl["precursors"], fold, out_stem)
+                    if classifier is not None:
+                        cl["classify"] = classify_candidates(engine, cl["screen"]["path"], None, None, classifier=classifier)
                 cl["features"].pop("device", None)
                 cl["features"].pop("index", None)
             cl["remap"].pop("device", None)
@@ -1039,7 +1149,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
 
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
-                    timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None):
+                    timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None, classify=False,
+                    models=None, species=None):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
@@ -1051,12 +1162,19 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     `_cluster.txt`; the return value gains "features").  precursors=True (needs features) adds :608 (cluster_precursors: the
     table's `_features_precusor.fa`; the return value gains "precursors").  screen=True (needs precursors and fold = a callable
     (fasta_path, str_path) or RNAfold's path) adds :610-626 (screen_precursors: two folds and the table's
-    `_features_updated_stableClusterSeq_15.tsv`; the return value gains "screen")."""
+    `_features_updated_stableClusterSeq_15.tsv`; the return value gains "screen").  classify=True (needs screen, models = the
+    directory of miRge2.0's model files and species: human and mouse have a model of their own, every other name takes
+    `others`) adds :647-648 (classify_candidates: the three filter files, `predicted_<sample>_detailed.csv` and
+    `<sample>_novel_miRNAs_miRge2.0.csv`; the return value gains "classify").  The model file and the namelist are opened and
+    validated before any device work."""
     from .engine import ReadSet
     if precursors and not features:
         raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
     if screen and not precursors:
         raise ValueError("screen needs precursors: the candidates it folds are the windows cut there")
+    if classify and not screen:
+        raise ValueError("classify needs screen: the SVM reads the screened table")
+    classifier = classifier_files(models, species) if classify else None
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
     if longest > bowtie.MAX_READ_LEN:
@@ -1068,16 +1186,18 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
-                              out_stem, sam, timings, trim, remap, features=features, precursors=precursors, screen=screen, fold=fold)
+                              out_stem, sam, timings, trim, remap, features=features, precursors=precursors, screen=screen, fold=fold,
+                              classifier=classifier)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                          sam=True, timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None):
+                          sam=True, timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None,
+                          classifier=None):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
     names; no FASTA is parsed and no Python string is made per read.  trim / remap / features / precursors / screen / fold: as
-    map_and_cluster's."""
+    map_and_cluster's; classifier: what classifier_files returned (None: no classification)."""
     import torch
     from .engine import ReadSet
     if precursors and not features:
@@ -1110,7 +1230,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
                               out_stem, sam, timings, trim, remap, numbers, features=features, precursors=precursors, screen=screen,
-                              fold=fold)
+                              fold=fold, classifier=classifier)
 
 
 def sample_stem(sample):
@@ -1224,9 +1344,24 @@ def clusters_main(argv):
                     "(_features_updated_stableClusterSeq_15.tsv); needs -pr or --fold-cmd")
     ap.add_argument("-pr", dest="rnafold_dir", metavar="DIR", help="the directory RNAfold is in")
     ap.add_argument("--fold-cmd", metavar="EXECUTABLE", help="the fold command itself (started as `EXECUTABLE --noPS --noLP`); overrides -pr")
+    ap.add_argument("--classify", action="store_true", help="with --screen: also classify the screened candidates with the SVM "
+                    "(predicted_<sample>_detailed.csv, <sample>_novel_miRNAs_miRge2.0.csv); needs --models")
+    ap.add_argument("--models", metavar="DIR", help="the directory of miRge2.0's model files (<species>_svc_model.pkl, total_features_namelist.txt)")
+    ap.add_argument("-sp", dest="species", default="human", help="the species: human and mouse have a model of their own, every other takes `others`")
     a = ap.parse_args(argv)
     if a.screen and not a.precursors:
         ap.error("--screen needs --precursors")
+    if a.classify and not a.screen:
+        ap.error("--classify needs --screen")
+    if a.classify and not a.models:
+        ap.error("--classify needs --models")
+    classifier = None
+    if a.classify:   # (before any device work, as -pr is checked)
+        try:
+            classifier = classifier_files(a.models, a.species)
+        except (OSError, ValueError) as e:
+            sys.stderr.write("predict clusters: %s\n" % e)
+            return 1
     fold = None
     if a.screen:
         try:
@@ -1246,7 +1381,8 @@ def clusters_main(argv):
         try:
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
                                  sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap,
-                                 features=a.features, precursors=a.precursors, screen=a.screen, fold=fold)
+                                 features=a.features, precursors=a.precursors, screen=a.screen, fold=fold, classify=a.classify,
+                                 models=a.models, species=a.species)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -1266,6 +1402,9 @@ def clusters_main(argv):
     if a.screen:
         sys.stderr.write("# screened: %d lines, %d candidates, %d folded again, %d worked out on the host, %d fold calls\n" % tuple(
             cl["screen"][k] for k in ("lines", "candidates", "pruned", "host_candidates", "folds")))
+    if a.classify:
+        sys.stderr.write("# classified: %d rows, %d after the count filter, %d with a structure, %d predicted 1, %d kept\n" % tuple(
+            cl["classify"][k] for k in ("table", "dataset", "refined", "predicted", "kept")))
     return 0
 
 
@@ -1274,7 +1413,7 @@ def main(argv=None):
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
                          "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features [--precursors [--screen -pr DIR | "
-                         "--fold-cmd EXECUTABLE]]]]]\n")
+                         "--fold-cmd EXECUTABLE [--classify --models DIR [-sp SPECIES]]]]]]]\n")
         return 1
     return clusters_main(argv[1:])
 
