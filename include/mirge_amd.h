@@ -1245,6 +1245,78 @@ int mrg_predict_model_write(void *handle, const int8_t *pred, const double *prob
 void mrg_predict_model_free(void *handle);
 int mrg_format_repr(double v, char *buf, uint32_t cap);
 
+/* Predict mode's report (reference miRge2.0.py:652, utils/write_novel_report.py, without its drawing; csrc/predict_report.hip,
+ * csrc/predict_report_write.cpp; the rule: tests/predict_report_model.py).
+ *
+ *   mrg_predict_report_read  HOST: the novel list (columns probability and clusterName; a name's first line counts), the
+ *       screened table and the cluster file into *handle.  counts [3]: table lines, listed names, read rows.  Headers without
+ *       the columns the report names, a line with fewer cells than the header, a clusterName that is not
+ *       `<sample>:<cluster>:<chr>:<start>_<end><+|->` or repeated, a count that is no whole number and a listed name the table
+ *       lacks are MRG_ERR_ARG.
+ *   mrg_predict_report_array  a pointer into the handle (valid until mrg_predict_report_free) and its bytes, `which` one of
+ *       MRG_REPORT_*: per line flags uint8 (1 listed, 2 pair_state Yes, 4 precursor None, arm code << 3: 0 arm5, 1 arm3, 2 loop,
+ *       3 other; 32 minus strand), rank uint32 (in the novel list, 0xffffffff none), up / down int64 (INT64_MIN = None,
+ *       INT64_MIN + 1 = no whole number), pos int64 [n][2] (start, end of the name), adj int32 [n][4] (head and tail dashes of
+ *       alignedClusterSeq, headUnstableLength, tailUnstableLength), reads int64 (readCountSum), gid3 uint32 [n][3] (the interned
+ *       group (precursor of line j - 1 / j / j + 1, chr, strand)), t_off uint64 [4 n + 1] into text (precursor, structure,
+ *       clusterSeq, stableClusterSeq of every line); per block blk uint8 (0 missing, 1 read, 2 malformed), r_off uint64 [n + 1];
+ *       per read row start / end / count int64, s_off uint64 [rows + 1] into the rows' text (RNA, dashes removed).
+ *   mrg_predict_report_correct  DEVICE, synchronised on return, no scratch: one wave per line.  d_src [n] = the line whose
+ *       precursor and structure the line ends up with (itself or a neighbour); d_state [n] = 1 touched by an offer | 2 re-typed
+ *       to loop | 4 left to the host (a precursor or structure beyond 256 characters, a clusterSeq or stableClusterSeq beyond
+ *       255: re-type and stable index are the caller's) | 8 precursor None | new arm code << 4; d_err [n] = where the reference
+ *       raises (1 upstreamDistance no number, 2 downstreamDistance None behind an upstreamDistance above 44, 3 the last line
+ *       offers downstream, 4 listed with precursor None, 8 offsets that do not ascend inside the text); d_pos_adj [n][2];
+ *       d_stable_idx [n] = where the corrected precursor holds stableClusterSeq (T as U), -1 absent; d_gid [n] (0xffffffff none).
+ *   mrg_predict_report_entries  DEVICE, synchronised on return: the project's radix sort over d_gid (file order inside a
+ *       group), a group's chunks of two keyed by its first listed member's rank, a second sort, the three-way mature rule, the
+ *       entry numbers by the project's prefix sum.  d_ent_m / d_ent_p [n] (entry e = novel_miRNA_<e + 1>: mature line,
+ *       passenger line or -1), d_chunk_err / d_chunk_line [n] per visited chunk in visiting order (5 the chosen mature is not
+ *       listed and not loop, 6 a stable sequence absent, 7 no block), d_row_off / d_prof_off [n + 1] (the entries' read rows and
+ *       precursor lengths summed).  totals [3]: entries, rows, profile words.  Scratch: mrg_predict_report_temp_bytes(n_lines).
+ *   mrg_predict_report_profile  DEVICE, synchronised on return, no scratch: one wave per entry; d_lead / d_trail [rows] (the
+ *       dashes on either side of every padded row, never negative), d_prof [profile words] (per precursor position the summed
+ *       count of the rows whose padded character there equals the precursor's; uint64), d_total [entries], d_flag [entries]
+ *       (1 ragged: a padded row's length is not the precursor's; 2 left to the host: a precursor beyond 256, a read beyond 255
+ *       or more than 65535 dashes on one side; 4 arrays that contradict each other).
+ *   mrg_predict_report_write  HOST: `_corrected.tsv` and `_novel_miRNAs_report.csv` byte for byte as the reference writes
+ *       them, and `_novel_miRNAs_report_profiles.tsv` (per entry `>novel_miRNA_<i>\t<L>\t<total>\t<rows>\t<ragged>`, the
+ *       precursor, the structure, L sums, then `<padded row>\t<count>` for the mature's and the passenger's rows).  Worker
+ *       threads: MIRGE_AMD_TABLE_THREADS.  Nothing is written when the arrays contradict the handle.
+ *   mrg_predict_report_free  releases the handle.
+ */
+enum {
+  MRG_REPORT_FLAGS = 0, MRG_REPORT_RANK, MRG_REPORT_UP, MRG_REPORT_DOWN, MRG_REPORT_POS, MRG_REPORT_ADJ, MRG_REPORT_READS,
+  MRG_REPORT_GID3, MRG_REPORT_T_OFF, MRG_REPORT_TEXT, MRG_REPORT_BLK, MRG_REPORT_R_OFF, MRG_REPORT_ROW_START, MRG_REPORT_ROW_END,
+  MRG_REPORT_ROW_COUNT, MRG_REPORT_ROW_SOFF, MRG_REPORT_ROW_TEXT
+};
+int mrg_predict_report_read(const char *novel_path, const char *table_path, const char *cluster_path, uint64_t *counts,
+                            void **handle);
+int mrg_predict_report_array(void *handle, uint32_t which, const void **data, uint64_t *bytes);
+int mrg_predict_report_temp_bytes(uint64_t n_lines, uint64_t *bytes);
+int mrg_predict_report_correct(mrg_ctx *ctx, uint64_t n_lines, const uint8_t *d_flags, const int64_t *d_up, const int64_t *d_down,
+                               const int64_t *d_pos, const int32_t *d_adj, const uint32_t *d_gid3, const uint64_t *d_t_off,
+                               const char *d_text, uint64_t text_len, uint32_t *d_src, uint8_t *d_state, uint8_t *d_err,
+                               int64_t *d_pos_adj, int32_t *d_stable_idx, uint32_t *d_gid, void *stream);
+int mrg_predict_report_entries(mrg_ctx *ctx, uint64_t n_lines, const uint8_t *d_flags, const uint32_t *d_rank,
+                               const int64_t *d_reads, const uint64_t *d_t_off, const uint32_t *d_src, const uint8_t *d_state,
+                               const int32_t *d_stable_idx, const uint32_t *d_gid, const uint8_t *d_blk, const uint64_t *d_r_off,
+                               uint32_t *d_ent_m, int32_t *d_ent_p, uint8_t *d_chunk_err, uint32_t *d_chunk_line,
+                               uint64_t *d_row_off, uint64_t *d_prof_off, uint64_t *totals, void *d_tmp, uint64_t tmp_bytes,
+                               void *stream);
+int mrg_predict_report_profile(mrg_ctx *ctx, uint64_t n_lines, const uint8_t *d_flags, const uint64_t *d_t_off, const char *d_text,
+                               uint64_t text_len, const uint32_t *d_src, const int64_t *d_pos_adj, const int32_t *d_stable_idx,
+                               const uint64_t *d_r_off, uint64_t n_rows, const int64_t *d_row_start, const int64_t *d_row_end,
+                               const int64_t *d_row_count, const uint64_t *d_row_soff, const char *d_row_text,
+                               uint64_t row_text_len, uint64_t n_entries, const uint32_t *d_ent_m, const int32_t *d_ent_p,
+                               const uint64_t *d_row_off, const uint64_t *d_prof_off, int32_t *d_lead, int32_t *d_trail,
+                               uint64_t *d_prof, uint64_t *d_total, uint8_t *d_flag, void *stream);
+int mrg_predict_report_write(void *handle, const uint32_t *src, const uint8_t *state, const int64_t *pos_adj, uint64_t n_entries,
+                             const uint32_t *ent_m, const int32_t *ent_p, const uint64_t *row_off, const int32_t *lead,
+                             const int32_t *trail, const uint64_t *prof_off, const uint64_t *prof, const uint64_t *total,
+                             const uint8_t *flag, const char *corrected_path, const char *report_path, const char *profiles_path);
+void mrg_predict_report_free(void *handle);
+
 /*
  * isomirs.csv and isomirs.samples.csv (utils/writeDataToCSV.py:1090-1170, over the grouping of :588-606) from the same
  * arrays (round 6): the reads claimed by canon_pass ("exact miRNA", slot 1) and isomir_pass ("isomiR miRNA", slot 9) are

@@ -264,6 +264,18 @@ SIGNATURES = {
                                           C.POINTER(C.c_uint64)]),
     "mrg_predict_model_free": (None, [C.c_void_p]),
     "mrg_format_repr": (C.c_int, [C.c_double, C.c_char_p, C.c_uint32]),
+    "mrg_predict_report_read": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]),
+    "mrg_predict_report_array": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "mrg_predict_report_temp_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mrg_predict_report_correct": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 + [C.c_uint64] + [C.c_void_p] * 7),
+    "mrg_predict_report_entries": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 16 + [C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64,
+                                                                                           C.c_void_p]),
+    "mrg_predict_report_profile": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_uint64, C.c_uint64] + [C.c_void_p] * 10),
+    "mrg_predict_report_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9 +
+                                 [C.c_char_p, C.c_char_p, C.c_char_p]),
+    "mrg_predict_report_free": (None, [C.c_void_p]),
     "mrg_annotate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.POINTER(PassCfg), C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PassStats),

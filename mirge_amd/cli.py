@@ -37,7 +37,11 @@ Same flags, library directory layout (MAIN:108-112, :262-281) and output tables
     `--novel-predict` (implies `--novel-screen`; needs `--models <dir>` holding miRge2.0's `<species>_svc_model.pkl` and
     `total_features_namelist.txt`; the species is `-sp`) filters that table as preprocess_featureFiles does, classifies the rows
     with the model's SVM on the GPU and writes `predicted_<sample>_detailed.csv` and `<sample>_novel_miRNAs_miRge2.0.csv`, as
-    the reference's model_predict does.  The report of write_novel_report (PDFs) is not written.
+    the reference's model_predict does;
+    `--novel-report` (implies `--novel-predict`) builds the report of write_novel_report from the novel list, that table and
+    `_cluster.txt` on the GPU: the table's `_corrected.tsv` and `<sample>_novel_miRNAs_report.csv` as the reference writes them,
+    and `<sample>_novel_miRNAs_report_profiles.tsv`, which holds what the reference's PDFs plot (the padded read rows and the
+    per-position coverage); the two are copied to `<outputdir>/<sample>_novel_miRNAs/`.  The PDFs are not drawn.
 Call order follows MAIN:346-389.
 """
 import argparse
@@ -56,7 +60,7 @@ def novel_stages(args):
     before it."""
     novel_map = bool(getattr(args, "novel_map", False)) or bool(getattr(args, "novel_features", False)) or \
         bool(getattr(args, "novel_precursors", False)) or bool(getattr(args, "novel_screen", False)) or \
-        bool(getattr(args, "novel_predict", False))
+        bool(getattr(args, "novel_predict", False)) or bool(getattr(args, "novel_report", False))
     novel_trim = novel_map or bool(getattr(args, "novel_trim", False))
     novel_clusters = novel_trim or bool(getattr(args, "novel_clusters", False))
     novel_reads = novel_clusters or bool(getattr(args, "novel_reads", False))
@@ -121,6 +125,10 @@ def build_parser():
                    help="extension: --novel-screen, then the reference's preprocess_featureFiles and model_predict: the three filter "
                         "files, the SVM of the species' model on the GPU, predicted_<sample>_detailed.csv and "
                         "<sample>_novel_miRNAs_miRge2.0.csv; needs --models")
+    p.add_argument("--novel-report", dest="novel_report", action="store_true",
+                   help="extension: --novel-predict, then the reference's write_novel_report without its drawing: the table's "
+                        "_corrected.tsv, <sample>_novel_miRNAs_report.csv and <sample>_novel_miRNAs_report_profiles.tsv (what the PDFs "
+                        "plot), copied to <outputdir>/<sample>_novel_miRNAs/; the PDFs are not drawn")
     p.add_argument("--models", default=None, dest="models", metavar="<dir>",
                    help="extension: the directory of miRge2.0's model files (<species>_svc_model.pkl, total_features_namelist.txt)")
     p.add_argument("-pr", default=None, dest="rnafoldBinary", metavar="<dir>", help="the directory RNAfold is in (--novel-screen)")
@@ -254,7 +262,8 @@ def annotate_main(args, engine_factory=None, materialize=False):
             print(msg, file=out)
         sys.exit(1)
     novel_fold = novel_classifier = None
-    novel_predict = bool(getattr(args, "novel_predict", False))
+    novel_report = bool(getattr(args, "novel_report", False))
+    novel_predict = bool(getattr(args, "novel_predict", False)) or novel_report
     if bool(getattr(args, "novel_screen", False)) or novel_predict:   # before any GPU work: MAIN's check of -pr
         from . import predict as _predict
         try:
@@ -265,7 +274,7 @@ def annotate_main(args, engine_factory=None, materialize=False):
         try:
             novel_classifier = _predict.classifier_files(getattr(args, "models", None), sp)
         except (OSError, ValueError) as e:
-            novel_die("--novel-predict: %s" % e)
+            novel_die("%s: %s" % ("--novel-report" if novel_report else "--novel-predict", e))
     if novel_reads:
         try:
             novel_min, novel_max, novel_cc = int(args.minLength), int(args.maxLength), int(args.countCutoff)
@@ -612,10 +621,17 @@ def annotate_main(args, engine_factory=None, materialize=False):
                     os.replace(os.path.join(tmp_dir, fn), os.path.join(sub, fn))
                 idx, num, _cnt = lists["sample_sel"][s]
                 g_words, g_lens, g_nmask, g_counts = engine.predict_gather(*a_reads, a_quant, idx, sample=s)
-                predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
-                                              seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
-                                              remap=novel_map, features=novel_features, precursors=novel_precursors,
-                                              screen=novel_screen, fold=novel_fold, classifier=novel_classifier)
+                cl = predict.map_and_cluster_reads(engine, (g_words, g_lens, g_nmask), num, g_counts, novel_genome, mapping_loc,
+                                                   seed_len, overlap, os.path.join(sub, "unmapped_mirna_" + stem), trim=trim,
+                                                   remap=novel_map, features=novel_features, precursors=novel_precursors,
+                                                   screen=novel_screen, fold=novel_fold, classifier=novel_classifier,
+                                                   report=novel_report)
+                if novel_report:   # MAIN:644-654: the sample's directory, and the report copied there
+                    import shutil
+                    novel_dir = os.path.join(outdir, stem + "_novel_miRNAs")
+                    os.makedirs(novel_dir, exist_ok=True)
+                    for key in ("report", "profiles"):
+                        shutil.copy(cl["report"]["paths"][key], novel_dir)
     # the reads the remaining consumers look at: dict records only when the GFF, the tRF tables or the -ai report want them
     # (round 6: the isomiR tables alone come straight from the arrays, columnar.write_isomir_tables)
     want = {CANON_PASS, ISOMIR_PASS} | ({2, 3} if args.trf_output else set())

@@ -32,6 +32,7 @@
 #include "predict_features.hpp"
 #include "predict_precursors.hpp"
 #include "predict_reads.hpp"
+#include "predict_report.hpp"
 #include "predict_screen.hpp"
 #include "predict_svm.hpp"
 #include "prims.hpp"
@@ -4103,6 +4104,183 @@ int mrg_format_repr(double v, char* buf, uint32_t cap) {
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return MRG_OK;
 }
+
+// ------------------------------------------- predict mode: the report (csrc/predict_report.hip, csrc/predict_report_write.cpp)
+namespace {
+constexpr uint64_t kReportMaxLines = (1ull << 28) - 1;
+// the entry pass's scratch: the entry count, two sorts' buffer pairs, the chunks' columns, the sizes the offsets are summed from
+struct ReportScratch {
+  Piece<uint32_t> stat, key0, key1, val0, val1, ckey0, ckey1, cval0, cval1, cm, emit, num, rows32, len32;
+  Piece<int32_t> cp;
+  Piece<char> sort, scan;
+  size_t total;
+  explicit ReportScratch(uint64_t n) {
+    Carver c(8);
+    stat = c.take<uint32_t>(2);
+    for (Piece<uint32_t>* p : {&key0, &key1, &val0, &val1, &ckey0, &ckey1, &cval0, &cval1, &cm, &emit, &num}) *p = c.take<uint32_t>(n);
+    rows32 = c.take<uint32_t>(n + 1);
+    len32 = c.take<uint32_t>(n + 1);
+    cp = c.take<int32_t>(n);
+    sort = c.take<char>(mrg::prims::radix_temp_bytes(n));
+    scan = c.take<char>(mrg::prims::scan_temp_bytes(n + 1));
+    total = c.total();
+  }
+};
+}  // namespace
+
+int mrg_predict_report_read(const char* novel_path, const char* table_path, const char* cluster_path, uint64_t* counts, void** handle) {
+  const char* fn = "mrg_predict_report_read";
+  if (!novel_path || !table_path || !cluster_path || !counts || !handle) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  *handle = nullptr;
+  counts[0] = counts[1] = counts[2] = 0;
+  return guarded(fn, [&] {
+    std::unique_ptr<mrg::ReportTable> t(new mrg::ReportTable);
+    mrg::read_report_inputs(novel_path, table_path, cluster_path, t.get());
+    counts[0] = t->n;
+    counts[1] = t->n_listed;
+    counts[2] = t->n_rows;
+    *handle = t.release();
+    return MRG_OK;
+  });
+}
+
+int mrg_predict_report_array(void* handle, uint32_t which, const void** data, uint64_t* bytes) {
+  const char* fn = "mrg_predict_report_array";
+  if (!handle || !data || !bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  const mrg::ReportTable* t = static_cast<const mrg::ReportTable*>(handle);
+  auto give = [&](const auto& v) {
+    *data = v.data();
+    *bytes = v.size() * sizeof(v[0]);
+    return MRG_OK;
+  };
+  switch (which) {
+    case MRG_REPORT_FLAGS: return give(t->flags);
+    case MRG_REPORT_RANK: return give(t->rank);
+    case MRG_REPORT_UP: return give(t->up);
+    case MRG_REPORT_DOWN: return give(t->down);
+    case MRG_REPORT_POS: return give(t->pos);
+    case MRG_REPORT_ADJ: return give(t->adj);
+    case MRG_REPORT_READS: return give(t->reads);
+    case MRG_REPORT_GID3: return give(t->gid3);
+    case MRG_REPORT_T_OFF: return give(t->t_off);
+    case MRG_REPORT_TEXT: return give(t->text);
+    case MRG_REPORT_BLK: return give(t->blk);
+    case MRG_REPORT_R_OFF: return give(t->r_off);
+    case MRG_REPORT_ROW_START: return give(t->row_start);
+    case MRG_REPORT_ROW_END: return give(t->row_end);
+    case MRG_REPORT_ROW_COUNT: return give(t->row_count);
+    case MRG_REPORT_ROW_SOFF: return give(t->row_soff);
+    case MRG_REPORT_ROW_TEXT: return give(t->row_text);
+  }
+  return fail(MRG_ERR_ARG, "%s: no array %u", fn, which);
+}
+
+int mrg_predict_report_temp_bytes(uint64_t n_lines, uint64_t* bytes) {
+  const char* fn = "mrg_predict_report_temp_bytes";
+  if (!bytes) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_lines > kReportMaxLines) return fail(MRG_ERR_ARG, "%s: %llu lines; the limit is 2^28 - 1", fn, (unsigned long long)n_lines);
+  *bytes = ReportScratch(n_lines).total;
+  return MRG_OK;
+}
+
+int mrg_predict_report_correct(mrg_ctx* ctx, uint64_t n_lines, const uint8_t* d_flags, const int64_t* d_up, const int64_t* d_down,
+                               const int64_t* d_pos, const int32_t* d_adj, const uint32_t* d_gid3, const uint64_t* d_t_off, const char* d_text,
+                               uint64_t text_len, uint32_t* d_src, uint8_t* d_state, uint8_t* d_err, int64_t* d_pos_adj, int32_t* d_stable_idx,
+                               uint32_t* d_gid, void* stream) {
+  const char* fn = "mrg_predict_report_correct";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_lines > kReportMaxLines) return fail(MRG_ERR_ARG, "%s: %llu lines; the limit is 2^28 - 1", fn, (unsigned long long)n_lines);
+  if (n_lines == 0) return MRG_OK;
+  if (!d_flags || !d_up || !d_down || !d_pos || !d_adj || !d_gid3 || !d_t_off || (text_len && !d_text) || !d_src || !d_state || !d_err ||
+      !d_pos_adj || !d_stable_idx || !d_gid)
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const mrg::ReportLines in{(uint32_t)n_lines, d_flags, nullptr, d_up, d_down, d_pos, d_adj, nullptr, d_gid3, d_t_off, d_text, text_len};
+  const mrg::ReportLineOut out{d_src, d_state, d_err, d_pos_adj, d_stable_idx, d_gid};
+  HIP_TRY(mrg::report_correct_launch(in, out, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_predict_report_entries(mrg_ctx* ctx, uint64_t n_lines, const uint8_t* d_flags, const uint32_t* d_rank, const int64_t* d_reads,
+                               const uint64_t* d_t_off, const uint32_t* d_src, const uint8_t* d_state, const int32_t* d_stable_idx,
+                               const uint32_t* d_gid, const uint8_t* d_blk, const uint64_t* d_r_off, uint32_t* d_ent_m, int32_t* d_ent_p,
+                               uint8_t* d_chunk_err, uint32_t* d_chunk_line, uint64_t* d_row_off, uint64_t* d_prof_off, uint64_t* totals,
+                               void* d_tmp, uint64_t tmp_bytes, void* stream) {
+  const char* fn = "mrg_predict_report_entries";
+  if (!ctx || !totals) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  totals[0] = totals[1] = totals[2] = 0;
+  if (n_lines > kReportMaxLines) return fail(MRG_ERR_ARG, "%s: %llu lines; the limit is 2^28 - 1", fn, (unsigned long long)n_lines);
+  const ReportScratch sc(n_lines);
+  if (!d_tmp) return fail(MRG_ERR_ARG, "%s: null scratch", fn);
+  if (int rc = scratch_ok(fn, d_tmp, tmp_bytes, sc.total, "mrg_predict_report_temp_bytes")) return rc;
+  if (!d_row_off || !d_prof_off || !d_r_off) return fail(MRG_ERR_ARG, "%s: null offsets", fn);
+  if (n_lines && (!d_flags || !d_rank || !d_reads || !d_t_off || !d_src || !d_state || !d_stable_idx || !d_gid || !d_blk || !d_ent_m || !d_ent_p ||
+                  !d_chunk_err || !d_chunk_line))
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const mrg::ReportLines in{(uint32_t)n_lines, d_flags, d_rank, nullptr, nullptr, nullptr, nullptr, d_reads, nullptr, d_t_off, nullptr, 0};
+  const mrg::ReportLineOut lines{const_cast<uint32_t*>(d_src), const_cast<uint8_t*>(d_state), nullptr, nullptr, const_cast<int32_t*>(d_stable_idx),
+                                 const_cast<uint32_t*>(d_gid)};
+  const mrg::ReportEntryScratch es{sc.key0.at(d_tmp), sc.key1.at(d_tmp), sc.val0.at(d_tmp), sc.val1.at(d_tmp), sc.ckey0.at(d_tmp), sc.ckey1.at(d_tmp),
+                                   sc.cval0.at(d_tmp), sc.cval1.at(d_tmp), sc.cm.at(d_tmp), sc.emit.at(d_tmp), sc.num.at(d_tmp), sc.rows32.at(d_tmp),
+                                   sc.len32.at(d_tmp), sc.cp.at(d_tmp), sc.sort.at(d_tmp), sc.scan.at(d_tmp)};
+  const mrg::ReportEntryOut out{d_ent_m, d_ent_p, d_chunk_err, d_chunk_line, d_row_off, d_prof_off, sc.stat.at(d_tmp)};
+  HIP_TRY(mrg::report_entries_launch(in, lines, d_blk, d_r_off, es, out, st));
+  uint32_t n_entries = 0;
+  uint64_t sums[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&n_entries, sc.stat.at(d_tmp), sizeof n_entries, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&sums[0], d_row_off + n_lines, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&sums[1], d_prof_off + n_lines, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  totals[0] = n_entries;
+  totals[1] = sums[0];
+  totals[2] = sums[1];
+  return MRG_OK;
+}
+
+int mrg_predict_report_profile(mrg_ctx* ctx, uint64_t n_lines, const uint8_t* d_flags, const uint64_t* d_t_off, const char* d_text, uint64_t text_len,
+                               const uint32_t* d_src, const int64_t* d_pos_adj, const int32_t* d_stable_idx, const uint64_t* d_r_off,
+                               uint64_t n_rows, const int64_t* d_row_start, const int64_t* d_row_end, const int64_t* d_row_count,
+                               const uint64_t* d_row_soff, const char* d_row_text, uint64_t row_text_len, uint64_t n_entries,
+                               const uint32_t* d_ent_m, const int32_t* d_ent_p, const uint64_t* d_row_off, const uint64_t* d_prof_off,
+                               int32_t* d_lead, int32_t* d_trail, uint64_t* d_prof, uint64_t* d_total, uint8_t* d_flag, void* stream) {
+  const char* fn = "mrg_predict_report_profile";
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  if (n_lines > kReportMaxLines || n_entries > n_lines) return fail(MRG_ERR_ARG, "%s: lines are limited to 2^28 - 1, entries to the lines", fn);
+  if (n_entries == 0) return MRG_OK;
+  if (!d_flags || !d_t_off || (text_len && !d_text) || !d_src || !d_pos_adj || !d_stable_idx || !d_r_off || !d_row_soff || !d_ent_m || !d_ent_p ||
+      !d_row_off || !d_prof_off || !d_total || !d_flag)
+    return fail(MRG_ERR_ARG, "%s: null arrays", fn);
+  if (n_rows && (!d_row_start || !d_row_end || !d_row_count || !d_lead || !d_trail || (row_text_len && !d_row_text)))
+    return fail(MRG_ERR_ARG, "%s: null row arrays", fn);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const mrg::ReportLines in{(uint32_t)n_lines, d_flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_t_off, d_text, text_len};
+  const mrg::ReportLineOut lines{const_cast<uint32_t*>(d_src), nullptr, nullptr, const_cast<int64_t*>(d_pos_adj), const_cast<int32_t*>(d_stable_idx), nullptr};
+  const mrg::ReportRows rows{nullptr, d_r_off, n_rows, d_row_start, d_row_end, d_row_count, d_row_soff, d_row_text, row_text_len};
+  const mrg::ReportProfileOut out{d_lead, d_trail, d_prof, d_total, d_flag};
+  HIP_TRY(mrg::report_profile_launch(in, lines, rows, (uint32_t)n_entries, d_ent_m, d_ent_p, d_row_off, d_prof_off, out, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_predict_report_write(void* handle, const uint32_t* src, const uint8_t* state, const int64_t* pos_adj, uint64_t n_entries,
+                             const uint32_t* ent_m, const int32_t* ent_p, const uint64_t* row_off, const int32_t* lead, const int32_t* trail,
+                             const uint64_t* prof_off, const uint64_t* prof, const uint64_t* total, const uint8_t* flag, const char* corrected_path,
+                             const char* report_path, const char* profiles_path) {
+  const char* fn = "mrg_predict_report_write";
+  if (!handle || !corrected_path || !report_path || !profiles_path) return fail(MRG_ERR_ARG, "%s: null argument", fn);
+  const mrg::ReportTable* t = static_cast<const mrg::ReportTable*>(handle);
+  return guarded(fn, [&] {
+    const mrg::ReportWriteArgs a{src, state, pos_adj, n_entries, ent_m, ent_p, row_off, lead, trail, prof_off, prof, total, flag,
+                                 corrected_path, report_path, profiles_path};
+    mrg::write_report(*t, a);
+    return MRG_OK;
+  });
+}
+
+void mrg_predict_report_free(void* handle) { delete static_cast<mrg::ReportTable*>(handle); }
 
 // ----------------------------------------------------- host convenience
 int mrg_annotate_host(mrg_ctx* ctx, const uint64_t* reads, uint32_t words_per_read,

@@ -1731,6 +1731,148 @@ class Engine:
                                         self._stream_ptr()))
         return dict(pred=pred.cpu().numpy(), dec=dec.cpu().numpy(), prob=prob.cpu().numpy().reshape(n, 2))
 
+    # ---- predict mode: the report (csrc/predict_report.hip)
+    _REPORT_LINE_ARRAYS = (("flags", np.uint8, "uint8"), ("rank", np.uint32, "int32"), ("up", np.int64, "int64"), ("down", np.int64, "int64"),
+                           ("pos", np.int64, "int64"), ("adj", np.int32, "int32"), ("reads", np.int64, "int64"), ("gid3", np.uint32, "int32"),
+                           ("t_off", np.uint64, "int64"), ("text", np.uint8, "uint8"), ("blk", np.uint8, "uint8"), ("r_off", np.uint64, "int64"),
+                           ("row_start", np.int64, "int64"), ("row_end", np.int64, "int64"), ("row_count", np.int64, "int64"),
+                           ("row_soff", np.uint64, "int64"), ("row_text", np.uint8, "uint8"))
+
+    def _report_tmp(self, n):
+        return self._tmp(self._lib.mrg_predict_report_temp_bytes, n, floor=64)
+
+    def predict_report_upload(self, arrays):
+        """The native reader's arrays (predict.ReportInputs.arrays, or tests/predict_report_model.arrays) as device tensors."""
+        torch = _torch()
+        d = {k: self._screen_dev(np.asarray(arrays[k]).reshape(-1) if not isinstance(arrays[k], (bytes, bytearray)) else arrays[k], np_dt,
+                                 getattr(torch, t_dt), "predict_report: " + k) for k, np_dt, t_dt in self._REPORT_LINE_ARRAYS}
+        n = int(d["flags"].numel())
+        sizes = dict(rank=n, up=n, down=n, pos=2 * n, adj=4 * n, reads=n, gid3=3 * n, t_off=4 * n + 1, blk=n, r_off=n + 1)
+        R = int(d["row_start"].numel())
+        sizes.update(row_end=R, row_count=R, row_soff=R + 1)
+        for k, want in sizes.items():
+            if int(d[k].numel()) != want:
+                raise ValueError("predict_report: %s must hold %d entries, not %d" % (k, want, int(d[k].numel())))
+        d["n"], d["n_rows"] = n, R
+        return d
+
+    def predict_report_correct(self, d):
+        """mrg_predict_report_correct over predict_report_upload's tensors: device tensors src, state, err, pos_adj, stable_idx, gid."""
+        torch = _torch()
+        n = d["n"]
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        out = dict(src=e(n, torch.int32), state=e(n, torch.uint8), err=e(n, torch.uint8), pos_adj=e(2 * n, torch.int64),
+                   stable_idx=e(n, torch.int32), gid=e(n, torch.int32))
+        p = self._p
+        check(self._lib.mrg_predict_report_correct(self._h, n, p(d["flags"]), p(d["up"]), p(d["down"]), p(d["pos"]), p(d["adj"]), p(d["gid3"]),
+                                                   p(d["t_off"]), p(d["text"]), int(d["text"].numel()), p(out["src"]), p(out["state"]),
+                                                   p(out["err"]), p(out["pos_adj"]), p(out["stable_idx"]), p(out["gid"]), self._stream_ptr()))
+        return out
+
+    def predict_report_entries(self, d, lines):
+        """mrg_predict_report_entries: device tensors ent_m, ent_p, chunk_err, chunk_line [n], row_off, prof_off [n + 1] and the
+        totals n_entries, rows, words."""
+        torch = _torch()
+        n = d["n"]
+        e = lambda count, dtype: torch.empty(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        out = dict(ent_m=e(n, torch.int32), ent_p=e(n, torch.int32), chunk_err=e(n, torch.uint8), chunk_line=e(n, torch.int32),
+                   row_off=e(n + 1, torch.int64), prof_off=e(n + 1, torch.int64))
+        totals = (C.c_uint64 * 3)()
+        tmp = self._report_tmp(n)
+        p = self._p
+        check(self._lib.mrg_predict_report_entries(self._h, n, p(d["flags"]), p(d["rank"]), p(d["reads"]), p(d["t_off"]), p(lines["src"]),
+                                                   p(lines["state"]), p(lines["stable_idx"]), p(lines["gid"]), p(d["blk"]), p(d["r_off"]),
+                                                   p(out["ent_m"]), p(out["ent_p"]), p(out["chunk_err"]), p(out["chunk_line"]),
+                                                   p(out["row_off"]), p(out["prof_off"]), totals, tmp.data_ptr(), tmp.numel(),
+                                                   self._stream_ptr()))
+        out.update(n_entries=int(totals[0]), rows=int(totals[1]), words=int(totals[2]))
+        return out
+
+    def predict_report_profile(self, d, lines, ents):
+        """mrg_predict_report_profile: device tensors lead, trail [rows], prof [words], total, flag [n_entries]."""
+        torch = _torch()
+        n, E = d["n"], ents["n_entries"]
+        e = lambda count, dtype: torch.zeros(max(int(count), 1), dtype=dtype, device=self.device)[:int(count)]
+        out = dict(lead=e(ents["rows"], torch.int32), trail=e(ents["rows"], torch.int32), prof=e(ents["words"], torch.int64),
+                   total=e(E, torch.int64), flag=e(E, torch.uint8))
+        p = self._p
+        check(self._lib.mrg_predict_report_profile(self._h, n, p(d["flags"]), p(d["t_off"]), p(d["text"]), int(d["text"].numel()),
+                                                   p(lines["src"]), p(lines["pos_adj"]), p(lines["stable_idx"]), p(d["r_off"]), d["n_rows"],
+                                                   p(d["row_start"]), p(d["row_end"]), p(d["row_count"]), p(d["row_soff"]), p(d["row_text"]),
+                                                   int(d["row_text"].numel()), E, p(ents["ent_m"]), p(ents["ent_p"]), p(ents["row_off"]),
+                                                   p(ents["prof_off"]), p(out["lead"]), p(out["trail"]), p(out["prof"]), p(out["total"]),
+                                                   p(out["flag"]), self._stream_ptr()))
+        return out
+
+    REPORT_ERRORS = {1: "upstreamDistance is no whole number", 2: "upstreamDistance exceeds 44 and downstreamDistance is None or no whole number",
+                     3: "the last line offers its precursor to a line that does not exist",
+                     4: "the name is in the novel list and its precursor is None",
+                     5: "the line is the mature one of its pair, is not loop and is not in the novel list",
+                     6: "a stable sequence of its pair is not in the precursor", 7: "the cluster file holds no (or a malformed) block of its pair",
+                     8: "offsets that do not ascend inside their text"}
+
+    def predict_report(self, arrays, host_line=None, host_entry=None, timings=None):
+        """The report's three device calls over the native reader's arrays (mrg_predict_report_correct / _entries / _profile).
+        host_line(j, src) -> (re-typed, stable index) answers for the lines the correction leaves to the host (state & 4), and
+        host_entry(e, m, p, src, pos_adj, stable_idx) -> (lead, trail, sums, total, ragged) for the entries the profile leaves
+        (flag & 2); without them such a line or entry is an error.  Returns host arrays: src, state, pos_adj, stable_idx, gid,
+        ent_m, ent_p, row_off, prof_off, lead, trail, prof, total, flag, and n_entries, host_lines, host_entries.  ValueError
+        naming the line and the reason where the reference raises."""
+        torch = _torch()
+        d = self.predict_report_upload(arrays)
+        n = d["n"]
+        lines = self.predict_report_correct(d)
+
+        def refuse(code, line):
+            raise ValueError("line %d of the table: %s" % (int(line) + 2, self.REPORT_ERRORS.get(int(code), "error %d" % int(code))))
+        err = lines["err"].cpu().numpy()
+        if err.any():
+            j = int(np.flatnonzero(err)[0])
+            refuse(err[j], j)
+        state = lines["state"].cpu().numpy()
+        src = lines["src"].cpu().numpy().view(np.uint32)
+        left = np.flatnonzero(state & 4)
+        if left.size:
+            if host_line is None:
+                raise ValueError("line %d of the table: a precursor beyond 256 or a sequence beyond 255 characters" % (int(left[0]) + 2))
+            stable = lines["stable_idx"].cpu().numpy()
+            for j in left.tolist():
+                retyped, at = host_line(j, int(src[j]))
+                arm = (int(state[j]) >> 4) & 3
+                if retyped and arm != 2:
+                    state[j] = (int(state[j]) & 0x0f) | 2 | (2 << 4)
+                stable[j] = at
+            lines["state"] = torch.from_numpy(state).to(self.device)
+            lines["stable_idx"] = torch.from_numpy(stable).to(self.device)
+        ents = self.predict_report_entries(d, lines)
+        cerr = ents["chunk_err"].cpu().numpy()
+        if cerr.any():
+            k = int(np.flatnonzero(cerr)[0])
+            refuse(cerr[k], ents["chunk_line"].cpu().numpy().view(np.uint32)[k])
+        E = ents["n_entries"]
+        prof = self.predict_report_profile(d, lines, ents)
+        u32 = lambda t: t.cpu().numpy().view(np.uint32)
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)
+        out = dict(src=src, state=state, pos_adj=lines["pos_adj"].cpu().numpy().reshape(n, 2), stable_idx=lines["stable_idx"].cpu().numpy(),
+                   gid=u32(lines["gid"]), ent_m=u32(ents["ent_m"])[:E].copy(), ent_p=ents["ent_p"].cpu().numpy()[:E].copy(),
+                   row_off=u64(ents["row_off"])[:E + 1].copy(), prof_off=u64(ents["prof_off"])[:E + 1].copy(), lead=prof["lead"].cpu().numpy(),
+                   trail=prof["trail"].cpu().numpy(), prof=u64(prof["prof"]), total=u64(prof["total"]), flag=prof["flag"].cpu().numpy(),
+                   n_entries=E, host_lines=int(left.size))
+        if E == 0:
+            out["row_off"], out["prof_off"] = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        if (out["flag"] & 4).any():
+            raise _native.MirgeAmdError(-1, "predict_report: entry %d: arrays that contradict each other" % (int(np.flatnonzero(out["flag"] & 4)[0]) + 1))
+        left_e = np.flatnonzero(out["flag"] & 2)
+        out["host_entries"] = int(left_e.size)
+        for e in left_e.tolist():
+            if host_entry is None:
+                raise ValueError("entry %d: a precursor beyond 256, a read beyond 255 characters or more than 65535 dashes" % (e + 1))
+            lead, trail, sums, total, ragged = host_entry(e, int(out["ent_m"][e]), int(out["ent_p"][e]), src, out["pos_adj"], out["stable_idx"])
+            r0, r1, p0, p1 = int(out["row_off"][e]), int(out["row_off"][e + 1]), int(out["prof_off"][e]), int(out["prof_off"][e + 1])
+            out["lead"][r0:r1], out["trail"][r0:r1], out["prof"][p0:p1] = lead, trail, sums
+            out["total"][e], out["flag"][e] = total, 1 if ragged else 0
+        return out
+
     def trf_peaks(self, off, codes, nmask, span, rpm, max_len, ktab):
         """Density peaks of `-trf` (W2C:417-533, :951-961) for every (sample, tRNA) group of a run, through
         mrg_trf_rho / _delta / _border.  Host arrays: off[G+1] row offsets, codes / nmask [W][n] uint64 (nmask

@@ -45,7 +45,15 @@ mrg_predict_svm; the model file read by mirge_amd/svm_model.py, before any devic
     predicted_<sample>_detailed.csv                                   label and probability of every refined row
     <sample>_novel_miRNAs_miRge2.0.csv                                the rows predicted 1 with a probability of 0.8 or more
 
-The report of write_novel_report (PDFs through matplotlib and forgi) is not built.
+With `report=True` / `--report` (needs the classification) the last call (miRge2.0.py:652, write_novel_report) runs over the novel
+list, the screened table and `_cluster.txt` (report_candidates: the native reader ReportInputs, Engine.predict_report =
+mrg_predict_report_correct / _entries / _profile, the native writers) and adds
+
+    <table>_corrected.tsv                              the screened table after the pair correction and the arm re-type
+    <sample>_novel_miRNAs_report.csv                   one line per novel miRNA, byte for byte the reference's
+    <sample>_novel_miRNAs_report_profiles.tsv          extension: per miRNA the padded read rows and the per-position coverage
+
+Only the drawing of write_novel_report is left out: precusorTmp.fa / .str, the RNAfold run per miRNA and the PDFs are not made.
 
 The device is $MIRGE_AMD_GPU (default 0).  Limits: reads up to 255 nt, fewer than 2^32 - 1 alignment rows, positions
 below 2^31; beyond them the call fails naming the limit and writes nothing.
@@ -909,7 +917,8 @@ def classify_candidates(engine, screened_path, model_dir, species, threads=None,
     device (Engine.predict_svm) and `predicted_<sample>_detailed.csv` / `<sample>_novel_miRNAs_miRge2.0.csv` by the native
     writer.  classifier: what classifier_files returned (None: read from model_dir now).  Returns a dict: table, dataset,
     refined (rows per filter), stray (selected names whose column holds a cell that is no number: 0 for every row),
-    predicted (rows predicted 1), kept (rows of the novel list), paths, and the device's pred, dec and prob.  timings gets
+    predicted (rows predicted 1), kept (rows of the novel list), paths, screened (the table's own path), and the device's pred, dec
+    and prob.  timings gets
     read_s, device_s and write_s."""
     import time
     model, namelist = classifier if classifier is not None else classifier_files(model_dir, species)
@@ -924,7 +933,172 @@ def classify_candidates(engine, screened_path, model_dir, species, threads=None,
         if timings is not None:
             timings.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2)
         return dict(table=table.rows[0], dataset=table.rows[1], refined=table.rows[2], stray=table.stray, predicted=predicted, kept=kept,
-                    paths=table.paths, pred=res["pred"], dec=res["dec"], prob=res["prob"])
+                    paths=table.paths, screened=screened_path, pred=res["pred"], dec=res["dec"], prob=res["prob"])
+
+
+# ------------------------------------------------------------------------------------------------ the report
+REPORT_ARRAYS = ("flags", "rank", "up", "down", "pos", "adj", "reads", "gid3", "t_off", "text", "blk", "r_off", "row_start", "row_end",
+                 "row_count", "row_soff", "row_text")   # include/mirge_amd.h: MRG_REPORT_*
+_REPORT_DTYPES = dict(flags=np.uint8, rank=np.uint32, up=np.int64, down=np.int64, pos=np.int64, adj=np.int32, reads=np.int64, gid3=np.uint32,
+                      t_off=np.uint64, text=np.uint8, blk=np.uint8, r_off=np.uint64, row_start=np.int64, row_end=np.int64, row_count=np.int64,
+                      row_soff=np.uint64, row_text=np.uint8)
+
+
+def report_paths(novel_path, table_path, cluster_path):
+    """The three files of the report by the reference's names: the table's `_corrected.tsv`; `<sample>_novel_miRNAs_report.csv` and
+    the extension `<sample>_novel_miRNAs_report_profiles.tsv` next to the cluster file, under the novel list's stem."""
+    stem = os.path.join(os.path.split(os.path.abspath(cluster_path))[0], "_".join(novel_path.split("_")[:-3]))
+    return dict(corrected=table_path[:-4] + "_corrected.tsv", report=stem + "_novel_miRNAs_report.csv",
+                profiles=stem + "_novel_miRNAs_report_profiles.tsv")
+
+
+def _report_cluster_path(table_path):
+    """`*_cluster.txt` next to a screened table `*_features_updated_stableClusterSeq_<n>.tsv`, by the reference's names."""
+    at = table_path.rfind("_features_updated_stableClusterSeq_")
+    if at < 0:
+        raise ValueError("report_candidates: %s is not a *_features_updated_stableClusterSeq_<n>.tsv; name the cluster file" % table_path)
+    return table_path[:at] + "_cluster.txt"
+
+
+class ReportInputs:
+    """mrg_predict_report_read: the novel list, the screened table and the cluster file read, validated and interned by the native
+    reader.  n, n_listed, n_rows; arrays: the reader's arrays as numpy copies (REPORT_ARRAYS).  write() is
+    mrg_predict_report_write.  A context manager: the native side is released on exit.  ValueError for files the reader refuses."""
+
+    def __init__(self, novel_path, table_path, cluster_path):
+        from . import _native
+        self._lib = _native.load()
+        self.paths = report_paths(novel_path, table_path, cluster_path)
+        counts, self._h = (C.c_uint64 * 3)(), C.c_void_p()
+        rc = self._lib.mrg_predict_report_read(os.fsencode(novel_path), os.fsencode(table_path), os.fsencode(cluster_path), counts,
+                                               C.byref(self._h))
+        if rc == _native.MRG_ERR_ARG:
+            raise ValueError(self._lib.mrg_last_error().decode("utf-8", "replace"))
+        _native.check(rc)
+        self.n, self.n_listed, self.n_rows = (int(c) for c in counts)
+        self.arrays = {}
+        for which, key in enumerate(REPORT_ARRAYS):
+            data, size = C.c_void_p(), C.c_uint64()
+            _native.check(self._lib.mrg_predict_report_array(self._h, which, C.byref(data), C.byref(size)))
+            raw = C.string_at(data, size.value) if size.value else b""
+            self.arrays[key] = np.frombuffer(raw, dtype=_REPORT_DTYPES[key]).copy()
+
+    def strings(self, j):
+        """(precursor, structure, clusterSeq, stableClusterSeq) of line j."""
+        o, text = self.arrays["t_off"], self.arrays["text"]
+        return tuple(text[int(o[4 * j + k]):int(o[4 * j + k + 1])].tobytes().decode("ascii", "replace") for k in range(4))
+
+    def rows(self, j):
+        """(RNA, start, end, count) of every read row of line j's block."""
+        a = self.arrays
+        return [(a["row_text"][int(a["row_soff"][r]):int(a["row_soff"][r + 1])].tobytes().decode("ascii", "replace"), int(a["row_start"][r]),
+                 int(a["row_end"][r]), int(a["row_count"][r])) for r in range(int(a["r_off"][j]), int(a["r_off"][j + 1]))]
+
+    def write(self, res, threads=None):
+        """The three files from Engine.predict_report's arrays."""
+        from . import _native
+        E = int(res["n_entries"])
+        c = lambda key, dt: np.ascontiguousarray(res[key], dtype=dt).reshape(-1)
+        src, state, pos_adj = c("src", np.uint32), c("state", np.uint8), c("pos_adj", np.int64)
+        if src.shape != (self.n,) or state.shape != (self.n,) or pos_adj.shape != (2 * self.n,):
+            raise ValueError("ReportInputs.write: src, state [n] and pos_adj [n, 2] for the table's %d lines" % self.n)
+        ent_m, ent_p, row_off, prof_off = c("ent_m", np.uint32), c("ent_p", np.int32), c("row_off", np.uint64), c("prof_off", np.uint64)
+        lead, trail, prof, total, flag = c("lead", np.int32), c("trail", np.int32), c("prof", np.uint64), c("total", np.uint64), c("flag", np.uint8)
+        if ent_m.shape != (E,) or ent_p.shape != (E,) or row_off.shape != (E + 1,) or prof_off.shape != (E + 1,) or total.shape != (E,) or \
+                flag.shape != (E,) or lead.shape != (int(row_off[E]),) or trail.shape != lead.shape or prof.shape != (int(prof_off[E]),):
+            raise ValueError("ReportInputs.write: the entries' arrays do not match each other")
+        with _writer_threads(threads):
+            rc = self._lib.mrg_predict_report_write(self._h, _ptr(src), _ptr(state), _ptr(pos_adj), E, _ptr(ent_m), _ptr(ent_p), _ptr(row_off),
+                                                    _ptr(lead), _ptr(trail), _ptr(prof_off), _ptr(prof), _ptr(total), _ptr(flag),
+                                                    os.fsencode(self.paths["corrected"]), os.fsencode(self.paths["report"]),
+                                                    os.fsencode(self.paths["profiles"]))
+        if rc == _native.MRG_ERR_ARG:
+            raise ValueError(self._lib.mrg_last_error().decode("utf-8", "replace"))
+        _native.check(rc)
+
+    def close(self):
+        if self._h:
+            self._lib.mrg_predict_report_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def host_report_line(seq, structure, cluster_seq, stable):
+    """The arm re-type and the stable index of one line, for lines beyond the kernel's limits: (True when the stretch of the
+    structure under clusterSeq (T as U) holds a `(` before a `)`, where the precursor holds stableClusterSeq (T as U) or -1)."""
+    rna = cluster_seq.replace("T", "U")
+    start = seq.find(rna)
+    stretch = structure[start:start + len(rna)]
+    first = stretch.find("(")
+    return first >= 0 and stretch.rfind(")") > first, seq.find(stable.replace("T", "U"))
+
+
+def host_report_entry(precursor, clusters):
+    """The padded rows and the profile of one entry, for entries beyond the kernel's limits.  clusters: per cluster (the mature's,
+    then the passenger's) (rows, stable index, stable length, start, end, minus).  Returns (lead, trail, sums, total, ragged)."""
+    L = len(precursor)
+    lead, trail, sums, total, ragged = [], [], [0] * L, 0, False
+    for rows, at, stable_len, start, end, minus in clusters:
+        head, tail = at, L - at - stable_len
+        p_head, p_tail = (start - tail, end + head) if minus else (start - head, end + tail)
+        for seq, r_start, r_end, count in rows:
+            before, behind = max(0, r_start - p_head), max(0, p_tail - r_end)
+            ld, tr = (behind, before) if minus else (before, behind)
+            lead.append(ld)
+            trail.append(tr)
+            total += count
+            ragged = ragged or ld + len(seq) + tr != L
+            for q in range(min(L, ld + len(seq) + tr)):
+                ch = seq[q - ld] if ld <= q < ld + len(seq) else "-"
+                if ch == precursor[q]:
+                    sums[q] += count
+    return lead, trail, sums, total, ragged
+
+
+def report_candidates(engine, source, threads=None, timings=None):
+    """The reference's miRge2.0.py:652 (write_novel_report) without its drawing.  source: classify_candidates' result, or a dict
+    with the paths `novel` (`<sample>_novel_miRNAs_miRge2.0.csv`), `table` (`*_features_updated_stableClusterSeq_15.tsv`) and
+    `cluster` (`*_modified_selected_sorted_cluster.txt`; default: next to the table under the reference's name).  The native
+    reader (ReportInputs), the pair correction, the arm re-type, the entries and the coverage profiles on the device
+    (Engine.predict_report) and the native writers: the table's `_corrected.tsv` and `<sample>_novel_miRNAs_report.csv`, byte for
+    byte the reference's, and the extension `<sample>_novel_miRNAs_report_profiles.tsv` (what the PDFs plot).  The PDFs are not
+    drawn.  Returns a dict: entries, lines, listed, host_lines and host_entries (worked out by the Python restatement: a precursor
+    beyond 256 characters, a clusterSeq or read beyond 255), paths, and the device's arrays.  timings gets read_s, device_s and
+    write_s.  ValueError, naming the line and the reason, where the reference raises; no file is written then."""
+    import time
+    paths = source.get("paths", source)
+    novel, table = paths["novel"], paths.get("table", source.get("screened"))
+    if table is None:
+        raise ValueError("report_candidates: the path of the screened table is missing")
+    cluster = paths.get("cluster") or _report_cluster_path(table)
+    clock = time.perf_counter
+    t0 = clock()
+    with ReportInputs(novel, table, cluster) as inputs:
+        a = inputs.arrays
+        t1 = clock()
+
+        def host_line(j, src):
+            seq, structure = inputs.strings(src)[:2]
+            _, _, cluster_seq, stable = inputs.strings(j)
+            return host_report_line(seq, structure, cluster_seq, stable)
+
+        def host_entry(e, m, p, src, pos_adj, stable_idx):
+            clusters = [(inputs.rows(x), int(stable_idx[x]), len(inputs.strings(x)[3]), int(pos_adj[x][0]), int(pos_adj[x][1]),
+                         bool(a["flags"][x] & 32)) for x in ((m,) if p < 0 else (m, p))]
+            return host_report_entry(inputs.strings(int(src[m]))[0], clusters)
+        res = engine.predict_report(a, host_line=host_line, host_entry=host_entry)
+        t2 = clock()
+        inputs.write(res, threads)
+        t3 = clock()
+        if timings is not None:
+            timings.update(read_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2)
+        return dict(res, entries=res["n_entries"], lines=inputs.n, listed=inputs.n_listed, paths=dict(inputs.paths, novel=novel, table=table,
+                                                                                                         cluster=cluster))
 
 
 def _partners(structure):
@@ -1085,11 +1259,14 @@ def _check_policy(mapping_loc, seedLength, overlapLenCutoff):
 
 
 def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
-                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False, screen=False, fold=None, classifier=None):
+                       sam, timings, trim=None, remap=False, numbers=None, features=False, precursors=False, screen=False, fold=None, classifier=None,
+                       report=False):
     """The body map_and_cluster and map_and_cluster_reads share: rs = the reads as a ReadSet (None: no read), names / seqs
     as write_clusters / write_sorted_sam take them; numbers: the reads' (None: read from the list `names`); classifier: what
-    classifier_files returned (None: no classification)."""
+    classifier_files returned (None: no classification); report: also the report of the classified candidates."""
     from .engine import STRATUM_ALL
+    if report and classifier is None:
+        raise ValueError("report needs classify: the report is built from the novel list")
     if remap and trim is None:
         raise ValueError("remap needs trim: the reads are mapped to the clusters the trim retains")
     if features and not remap:
@@ -1141,6 +1318,8 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
                     cl["screen"] = screen_precursors(engine, cl["features"], cl["precursors"], fold, out_stem)
                     if classifier is not None:
                         cl["classify"] = classify_candidates(engine, cl["screen"]["path"], None, None, classifier=classifier)
+                        if report:
+                            cl["report"] = report_candidates(engine, cl["classify"])
                 cl["features"].pop("device", None)
                 cl["features"].pop("index", None)
             cl["remap"].pop("device", None)
@@ -1150,7 +1329,7 @@ def _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_l
 
 def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem, sam=True,
                     timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None, classify=False,
-                    models=None, species=None):
+                    models=None, species=None, report=False):
     """The reference's miRge2.0.py:538-548 for one reads file: bowtie `-f -n 0 -m mapping_loc -l seedLength -S -a --best`
     against the genome, samtools sort, cluster_basedon_location(<sorted.sam>, overlapLenCutoff).  Writes
     `<out_stem>_vs_genome_sorted_clusters.tsv` and (sam=True) `<out_stem>_vs_genome_sorted.sam`; returns the cluster
@@ -1166,7 +1345,9 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
     directory of miRge2.0's model files and species: human and mouse have a model of their own, every other name takes
     `others`) adds :647-648 (classify_candidates: the three filter files, `predicted_<sample>_detailed.csv` and
     `<sample>_novel_miRNAs_miRge2.0.csv`; the return value gains "classify").  The model file and the namelist are opened and
-    validated before any device work."""
+    validated before any device work.  report=True (needs classify) adds :652 without its drawing (report_candidates: the table's
+    `_corrected.tsv`, `<sample>_novel_miRNAs_report.csv` and `<sample>_novel_miRNAs_report_profiles.tsv`; the return value gains
+    "report")."""
     from .engine import ReadSet
     if precursors and not features:
         raise ValueError("precursors needs features: the windows are cut around the stable part the feature table found")
@@ -1174,6 +1355,8 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         raise ValueError("screen needs precursors: the candidates it folds are the windows cut there")
     if classify and not screen:
         raise ValueError("classify needs screen: the SVM reads the screened table")
+    if report and not classify:
+        raise ValueError("report needs classify: the report is built from the novel list")
     classifier = classifier_files(models, species) if classify else None
     names, seqs = bowtie.read_fasta(reads_fa)
     longest = max((len(s) for s in seqs), default=0)
@@ -1187,17 +1370,17 @@ def map_and_cluster(engine, reads_fa, genome_prefix, mapping_loc, seedLength, ov
         rs = ReadSet(words, lens, nmask, device=engine.device)
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
                               out_stem, sam, timings, trim, remap, features=features, precursors=precursors, screen=screen, fold=fold,
-                              classifier=classifier)
+                              classifier=classifier, report=report)
 
 
 def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping_loc, seedLength, overlapLenCutoff, out_stem,
                           sam=True, timings=None, trim=None, remap=False, features=False, precursors=False, screen=False, fold=None,
-                          classifier=None):
+                          classifier=None, report=False):
     """map_and_cluster from arrays: reads = (words [W, k], lens [k], nmask [W, k] or None) of Engine.predict_gather (device
     tensors, or host arrays), numbers / counts [k] = the `mir<number>_<count>` of every read (uint32; device tensors or
     host arrays).  The same policy, files and return value as map_and_cluster on the FASTA file of those reads under those
     names; no FASTA is parsed and no Python string is made per read.  trim / remap / features / precursors / screen / fold: as
-    map_and_cluster's; classifier: what classifier_files returned (None: no classification)."""
+    map_and_cluster's; classifier: what classifier_files returned (None: no classification); report: as map_and_cluster's."""
     import torch
     from .engine import ReadSet
     if precursors and not features:
@@ -1230,7 +1413,7 @@ def map_and_cluster_reads(engine, reads, numbers, counts, genome_prefix, mapping
                                     None if nmask is None else nmask.cpu().numpy().view(np.uint64))
     return _map_cluster_write(engine, rs, counts, names, seqs, genome_prefix, mapping_loc, seedLength, overlapLenCutoff,
                               out_stem, sam, timings, trim, remap, numbers, features=features, precursors=precursors, screen=screen,
-                              fold=fold, classifier=classifier)
+                              fold=fold, classifier=classifier, report=report)
 
 
 def sample_stem(sample):
@@ -1347,6 +1530,8 @@ def clusters_main(argv):
     ap.add_argument("--classify", action="store_true", help="with --screen: also classify the screened candidates with the SVM "
                     "(predicted_<sample>_detailed.csv, <sample>_novel_miRNAs_miRge2.0.csv); needs --models")
     ap.add_argument("--models", metavar="DIR", help="the directory of miRge2.0's model files (<species>_svc_model.pkl, total_features_namelist.txt)")
+    ap.add_argument("--report", action="store_true", help="with --classify: also the report of the novel list (the table's _corrected.tsv, "
+                    "<sample>_novel_miRNAs_report.csv, <sample>_novel_miRNAs_report_profiles.tsv); the PDFs are not drawn")
     ap.add_argument("-sp", dest="species", default="human", help="the species: human and mouse have a model of their own, every other takes `others`")
     a = ap.parse_args(argv)
     if a.screen and not a.precursors:
@@ -1355,6 +1540,8 @@ def clusters_main(argv):
         ap.error("--classify needs --screen")
     if a.classify and not a.models:
         ap.error("--classify needs --models")
+    if a.report and not a.classify:
+        ap.error("--report needs --classify")
     classifier = None
     if a.classify:   # (before any device work, as -pr is checked)
         try:
@@ -1382,7 +1569,7 @@ def clusters_main(argv):
             cl = map_and_cluster(eng, a.reads, a.genome_prefix, a.mapping_loc, a.seed_len, a.overlap, a.out_stem,
                                  sam=not a.no_sam, trim=(a.repeats, a.cluster_len_cutoff) if a.trim else None, remap=a.remap,
                                  features=a.features, precursors=a.precursors, screen=a.screen, fold=fold, classify=a.classify,
-                                 models=a.models, species=a.species)
+                                 models=a.models, species=a.species, report=a.report)
         finally:
             eng.close()
     except (OSError, ValueError, MirgeAmdError) as e:
@@ -1405,6 +1592,9 @@ def clusters_main(argv):
     if a.classify:
         sys.stderr.write("# classified: %d rows, %d after the count filter, %d with a structure, %d predicted 1, %d kept\n" % tuple(
             cl["classify"][k] for k in ("table", "dataset", "refined", "predicted", "kept")))
+    if a.report:
+        sys.stderr.write("# report: %d novel miRNAs from %d listed names, %d lines and %d entries worked out on the host; the PDFs are not drawn\n" % tuple(
+            cl["report"][k] for k in ("entries", "listed", "host_lines", "host_entries")))
     return 0
 
 
@@ -1413,7 +1603,7 @@ def main(argv=None):
     if not argv or argv[0] != "clusters":
         sys.stderr.write("usage: python -m mirge_amd.predict clusters <genome_prefix> <reads.fa> [-m 3] [-l 25] [--overlap 14] "
                          "-o <out_stem> [--no-sam] [--trim [--repeats FILE] [-clc 30] [--remap [--features [--precursors [--screen -pr DIR | "
-                         "--fold-cmd EXECUTABLE [--classify --models DIR [-sp SPECIES]]]]]]]\n")
+                         "--fold-cmd EXECUTABLE [--classify --models DIR [-sp SPECIES] [--report]]]]]]]\n")
         return 1
     return clusters_main(argv[1:])
 
