@@ -582,6 +582,26 @@ int mrg_list_valid_fill(mrg_ctx *ctx, const uint64_t *d_reads, uint32_t words_pe
                         uint8_t *d_strand, uint8_t *d_mm, void *stream);
 
 /*
+ * The same listing for reads of ANY length, in the ragged form of mrg_cascade_run_long (read r =
+ * d_words[d_word_off[r] .. d_word_off[r + 1]), 32 bases per word; d_nmask the same shape or NULL;
+ * d_lens uint32): what the bowtie front end lists the reads beyond 255 nt with.  One wave per read
+ * and the library's superblock table from global memory, so no library is too large for it; meant
+ * for the handful of such reads a sample holds.  Same rule, same two sweeps, same asynchrony and
+ * the same refusals as mrg_list_valid_count / _fill; within a read the fill sweep writes in the
+ * fixed order (strand, seed piece, suffix-array row).
+ */
+int mrg_list_valid_long_count(mrg_ctx *ctx, const uint64_t *d_words, const uint64_t *d_nmask,
+                              const uint64_t *d_word_off, const uint32_t *d_lens, uint64_t n,
+                              int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                              int32_t max_mm_total, uint32_t *d_counts, void *stream);
+int mrg_list_valid_long_fill(mrg_ctx *ctx, const uint64_t *d_words, const uint64_t *d_nmask,
+                             const uint64_t *d_word_off, const uint32_t *d_lens, uint64_t n,
+                             int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                             int32_t max_mm_total, int32_t stratum_mode, const uint8_t *d_best_mm,
+                             const uint64_t *d_offsets, uint64_t cap, int32_t *d_ref, int32_t *d_pos,
+                             uint8_t *d_strand, uint8_t *d_mm, void *stream);
+
+/*
  * Host-buffer convenience for a caller without its own device allocator (the
  * ctypes stub of INTEGRATION.md): H2D, cascade, tally, D2H in one call.
  * counts may be NULL (then quant/n_samples are ignored).

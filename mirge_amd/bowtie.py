@@ -8,8 +8,10 @@ miRge2.0 reaches its aligner only through `os.system("<-pb dir>/bowtie ...")`, `
     python -m mirge_amd.bowtie inspect [-n] <prefix>
 
 `align` accepts exactly the options the reference passes (see OPTIONS below and INTEGRATION.md section 3); the
-alignments come from the GPU (Engine.list_valid = mrg_list_valid_count / _fill) and the text from mrg_write_bowtie.
-The device is $MIRGE_AMD_GPU (default 0).
+alignments come from the GPU (Engine.list_valid = mrg_list_valid_count / _fill; reads beyond 255 nt:
+Engine.list_valid_long = mrg_list_valid_long_count / _fill) and the text from mrg_write_bowtie.
+The device is $MIRGE_AMD_GPU (default 0); $MIRGE_AMD_LONG_READS=1 admits reads beyond 255 nt, which `align` refuses
+otherwise.
 """
 import collections
 import ctypes as C
@@ -23,7 +25,8 @@ from ._native import MirgeAmdError
 
 USAGE = ("usage: bowtie [--threads N] [--phred64-quals] [-f] [-S] [-n N | -v V] [-l L] [-5 N] [-3 N] [-a] [--best] "
          "[--strata] [-m M] [--norc] <index prefix> <reads.fa> [<out>]")
-MAX_READ_LEN = 255
+MAX_READ_LEN = 255      # the packed listing's bound (one length byte); longer reads take the ragged listing,
+LONG_READS_ENV = "MIRGE_AMD_LONG_READS"   # ... when this is 1 in the environment (miRge2.0 fixes bowtie's argv); else exit 1
 V_MODE_SEED = 1024      # `-v`: the whole read is seed (engine.V_MODE_SEED)
 DEFAULT_SEED_LEN = 28   # bowtie's -l default
 N_MODE_MAX_TOTAL = 2    # -e 70 at the rounded FASTA quality 30
@@ -187,13 +190,41 @@ def keep_one(offsets, arrays):
     return new_off, [a[pick] for a in arrays]
 
 
+def merge_listings(n, idx_a, listing_a, idx_b, listing_b):
+    """Two listings (offsets[k+1], entry, offset, strand, mm, suppressed[k]: Engine.list_valid's tuple) of disjoint
+    subsets of n reads, read i of listing x being read idx_x[i] of the file, as ONE listing in file order: every read's
+    rows unchanged and in their order.  A read in neither subset has no rows and is not suppressed."""
+    counts = np.zeros(n, dtype=np.int64)
+    supp = np.zeros(n, dtype=bool)
+    for idx, lst in ((idx_a, listing_a), (idx_b, listing_b)):
+        idx = np.asarray(idx, dtype=np.int64)
+        counts[idx] = np.diff(np.asarray(lst[0], dtype=np.int64))
+        supp[idx] = np.asarray(lst[5], dtype=bool)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    total = int(offsets[n])
+    rows = [np.zeros(total, dtype=dt) for dt in (np.int32, np.int32, np.uint8, np.uint8)]
+    for idx, lst in ((idx_a, listing_a), (idx_b, listing_b)):
+        idx = np.asarray(idx, dtype=np.int64)
+        src = np.asarray(lst[0], dtype=np.int64)
+        k = np.diff(src)
+        # row t of the listing, t in [src[i], src[i + 1]), goes to offsets[idx[i]] + (t - src[i])
+        to = np.repeat(offsets[idx] - src[:-1], k) + np.arange(int(src[-1]) if len(src) else 0, dtype=np.int64)
+        for dst, a in zip(rows, lst[1:5]):
+            dst[to] = np.asarray(a)[:len(to)]
+    return (offsets,) + tuple(rows) + (supp,)
+
+
 def align(opt, cmdline, device=None):
     from .engine import Engine, ReadSet, STRATUM_ALL, STRATUM_BEST
     names, raw = read_fasta(opt.reads)
     seqs = [trim(s, *opt.trims) for s in raw]
-    longest = max((len(s) for s in seqs), default=0)
-    if longest > MAX_READ_LEN:
-        raise UsageError("reads longer than %d nt (after -5/-3) are not supported; got %d" % (MAX_READ_LEN, longest))
+    lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
+    # what one length byte describes goes through the packed listing, in one call; the rest through the ragged one
+    short, long_ = np.nonzero(lens <= MAX_READ_LEN)[0], np.nonzero(lens > MAX_READ_LEN)[0]
+    if len(long_) and os.environ.get(LONG_READS_ENV, "0") != "1":
+        raise UsageError("reads longer than %d nt (after -5/-3) are not supported unless %s=1 is set (it lists them with the "
+                         "wave-per-read kernel); got %d" % (MAX_READ_LEN, LONG_READS_ENV, int(lens.max())))
     parts = open_index(opt.index)
     dev = int(os.environ.get("MIRGE_AMD_GPU", "0")) if device is None else int(device)
     eng = Engine(dev)
@@ -203,18 +234,22 @@ def align(opt, cmdline, device=None):
             keys.append("part%03d" % k)
             eng.add_library(keys[-1], ix, exact_dict=False)
         n = len(seqs)
-        if n:
-            words, lens, nmask = pack.pack_reads(seqs, pack.words_for(max(longest, 1)))
-            rs = ReadSet(words, lens, nmask, device=eng.device)
-            seed_len, mm_seed, mm_total = opt.seed
-            off, entry, offset, strand, mm, supp = eng.list_valid(
-                rs, keys, strands=opt.strands, stratum_mode=STRATUM_BEST if opt.stratum_mode == "best" else STRATUM_ALL,
-                m=opt.m, seed_len=seed_len, max_mm_seed=mm_seed, max_mm_total=mm_total)
-        else:
-            off = np.zeros(1, dtype=np.int64)
-            entry = offset = np.zeros(0, np.int32)
-            strand = mm = np.zeros(0, np.uint8)
-            supp = np.zeros(0, bool)
+        seed_len, mm_seed, mm_total = opt.seed
+        how = dict(strands=opt.strands, stratum_mode=STRATUM_BEST if opt.stratum_mode == "best" else STRATUM_ALL, m=opt.m,
+                   max_mm_seed=mm_seed, max_mm_total=mm_total)
+        empty = (np.zeros(1, dtype=np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8),
+                 np.zeros(0, np.uint8), np.zeros(0, bool))
+        listing = empty
+        if len(short):
+            sub = seqs if not len(long_) else [seqs[i] for i in short]
+            words, lens8, nmask = pack.pack_reads(sub, pack.words_for(max(int(lens[short].max()), 1)))
+            listing = eng.list_valid(ReadSet(words, lens8, nmask, device=eng.device), keys, seed_len=seed_len, **how)
+        if len(long_):
+            # (`-v`: the whole read is seed, however long it is)
+            long_seed = max(seed_len, int(lens.max())) if opt.mode == "v" else seed_len
+            listing = merge_listings(n, short, listing, long_,
+                                     eng.list_valid_long([seqs[i] for i in long_], keys, seed_len=long_seed, **how))
+        off, entry, offset, strand, mm, supp = listing
         if opt.k1:
             off, (entry, offset, strand, mm) = keep_one(off, (entry, offset, strand, mm))
         s = write_bowtie(opt.out, opt.sam, cmdline, parts, names, seqs, off, entry, offset, strand, mm, supp, opt.m)

@@ -2251,6 +2251,18 @@ int mrg_cascade_stats(mrg_ctx* ctx, mrg_pass_stats* out, uint32_t n_pass) {
 }
 
 // ------------------------------------------------------- reads of any length
+namespace {
+
+// the library half of a long-read descriptor (the policy half is its caller's): everything from global memory
+void fill_long_lib(mrg::LongPass& q, const mrg_ctx& ctx, const DevLib& l) {
+  std::memset(&q, 0, sizeof q);
+  fill_lib(q, l);
+  if (!ctx.use_ftab || !l.ftab) q.tabs.k[0] = 0u;
+  q.simple_segs = l.simple ? 1u : 0u;
+}
+
+}  // namespace
+
 int mrg_cascade_run_long(mrg_ctx* ctx, const uint64_t* d_words, const uint64_t* d_nmask, const uint64_t* d_word_off,
                          const uint32_t* d_lens, uint64_t n, const mrg_pass_cfg* passes, uint32_t n_pass, int8_t* d_pass_id,
                          int32_t* d_ref_id, int32_t* d_pos, uint8_t* d_mm, uint64_t* d_pass_counts, mrg_pass_stats* stats,
@@ -2269,12 +2281,8 @@ int mrg_cascade_run_long(mrg_ctx* ctx, const uint64_t* d_words, const uint64_t* 
     if (c.max_mm_seed < 0 || c.max_mm_seed > 3 || c.max_mm_total < c.max_mm_seed || c.max_mm_total > 255 || c.trim5 < 0 ||
         c.trim3 < 0 || c.seed_len < 1)
       return fail(MRG_ERR_ARG, "mrg_cascade_run_long: pass %u has an invalid policy", i);
-    const DevLib& l = ctx->libs[c.lib];
     mrg::LongPass& q = host[i];
-    std::memset(&q, 0, sizeof q);
-    fill_lib(q, l);
-    if (!ctx->use_ftab || !l.ftab) q.tabs.k[0] = 0u;
-    q.simple_segs = l.simple ? 1u : 0u;
+    fill_long_lib(q, *ctx, ctx->libs[c.lib]);
     fill_policy(q, c);
     q.max_mm_seed = c.max_mm_seed;
   }
@@ -2791,6 +2799,81 @@ int mrg_list_valid_fill(mrg_ctx* ctx, const uint64_t* d_reads, uint32_t words_pe
   p.out_strand = d_strand;
   p.out_mm = d_mm;
   HIP_TRY(mrg::launch_valid(p, true, words_per_read, grid, lds, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+namespace {
+
+// the checks and the parameter block the two sweeps of the ragged listing share
+int fill_long_valid_params(mrg_ctx* ctx, const char* who, const uint64_t* d_words, const uint64_t* d_nmask, const uint64_t* d_word_off,
+                           const uint32_t* d_lens, uint64_t n, int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                           int32_t max_mm_total, mrg::LongValidParams* p, uint32_t* grid) {
+  if (!ctx) return fail(MRG_ERR_ARG, "%s: null argument", who);
+  if (n && (!d_words || !d_word_off || !d_lens)) return fail(MRG_ERR_ARG, "%s: null buffers", who);
+  if (lib < 0 || (size_t)lib >= ctx->libs.size()) return fail(MRG_ERR_ARG, "%s: unknown library %d", who, lib);
+  if (strands != 1 && strands != 2) return fail(MRG_ERR_ARG, "%s: strands must be 1 (forward) or 2 (both)", who);
+  if (max_mm_seed < 0 || max_mm_seed > 2 || max_mm_total < max_mm_seed || seed_len < 1) return fail(MRG_ERR_ARG, "%s: invalid policy", who);
+  if (max_mm_total > 3) return fail(MRG_ERR_ARG, "%s: at most 3 mismatches", who);
+  if (n >= 0x7fffffffull) return fail(MRG_ERR_ARG, "%s: too many reads for one call", who);
+  std::memset(p, 0, sizeof(*p));
+  fill_long_lib(p->lib, *ctx, ctx->libs[lib]);
+  p->lib.seed_len = seed_len;
+  p->lib.max_mm_seed = max_mm_seed;
+  p->lib.max_mm_total = max_mm_total;
+  p->words = d_words;
+  p->nmask = d_nmask;
+  p->word_off = d_word_off;
+  p->lens = d_lens;
+  p->n = (uint32_t)n;
+  p->wstop = (uint32_t)ctx->wstop;
+  p->strands = (uint32_t)strands;
+  // one wave per read, four per workgroup; more reads than resident waves: the kernel strides
+  *grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t)ctx->n_cu * 8u));
+  return MRG_OK;
+}
+
+}  // namespace
+
+int mrg_list_valid_long_count(mrg_ctx* ctx, const uint64_t* d_words, const uint64_t* d_nmask, const uint64_t* d_word_off,
+                              const uint32_t* d_lens, uint64_t n, int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                              int32_t max_mm_total, uint32_t* d_counts, void* stream) {
+  mrg::LongValidParams p;
+  uint32_t grid = 0;
+  int rc = fill_long_valid_params(ctx, "mrg_list_valid_long_count", d_words, d_nmask, d_word_off, d_lens, n, lib, strands, seed_len,
+                                  max_mm_seed, max_mm_total, &p, &grid);
+  if (rc != MRG_OK) return rc;
+  if (n && !d_counts) return fail(MRG_ERR_ARG, "mrg_list_valid_long_count: null buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (n == 0) return MRG_OK;
+  p.counts = d_counts;
+  HIP_TRY(mrg::launch_long_valid(p, false, grid, (hipStream_t)stream));
+  return MRG_OK;
+}
+
+int mrg_list_valid_long_fill(mrg_ctx* ctx, const uint64_t* d_words, const uint64_t* d_nmask, const uint64_t* d_word_off,
+                             const uint32_t* d_lens, uint64_t n, int32_t lib, int32_t strands, int32_t seed_len, int32_t max_mm_seed,
+                             int32_t max_mm_total, int32_t stratum_mode, const uint8_t* d_best_mm, const uint64_t* d_offsets,
+                             uint64_t cap, int32_t* d_ref, int32_t* d_pos, uint8_t* d_strand, uint8_t* d_mm, void* stream) {
+  mrg::LongValidParams p;
+  uint32_t grid = 0;
+  int rc = fill_long_valid_params(ctx, "mrg_list_valid_long_fill", d_words, d_nmask, d_word_off, d_lens, n, lib, strands, seed_len,
+                                  max_mm_seed, max_mm_total, &p, &grid);
+  if (rc != MRG_OK) return rc;
+  if (stratum_mode != MRG_STRATUM_BEST && stratum_mode != MRG_STRATUM_ALL)
+    return fail(MRG_ERR_ARG, "mrg_list_valid_long_fill: stratum_mode must be MRG_STRATUM_BEST or MRG_STRATUM_ALL");
+  if (n && (!d_best_mm || !d_offsets)) return fail(MRG_ERR_ARG, "mrg_list_valid_long_fill: null buffers");
+  if (cap && (!d_ref || !d_pos || !d_strand || !d_mm)) return fail(MRG_ERR_ARG, "mrg_list_valid_long_fill: null output buffers");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (n == 0 || cap == 0) return MRG_OK;
+  p.all = stratum_mode == MRG_STRATUM_ALL ? 1u : 0u;
+  p.best_mm = d_best_mm;
+  p.offsets = d_offsets;
+  p.cap = cap;
+  p.out_ref = d_ref;
+  p.out_pos = d_pos;
+  p.out_strand = d_strand;
+  p.out_mm = d_mm;
+  HIP_TRY(mrg::launch_long_valid(p, true, grid, (hipStream_t)stream));
   return MRG_OK;
 }
 

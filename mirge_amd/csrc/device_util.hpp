@@ -30,6 +30,12 @@ __device__ __forceinline__ uint32_t lex_code(uint64_t code, uint32_t k) {
   return (uint32_t)(((r >> 1) & kOddBits) | ((r & kOddBits) << 1));
 }
 
+// the 32 two-bit groups of v in reverse order (kernels.hip: reverse_pairs)
+__device__ __forceinline__ uint64_t reverse_pairs(uint64_t v) {
+  const uint64_t r = __brevll(v);  // groups reversed, the two bits of each group swapped back below
+  return ((r >> 1) & kOddBits) | ((r & kOddBits) << 1);
+}
+
 // The kernel's (single, by-value) parameter block where it sits, in the kernel-argument segment, through
 // a pointer laundered by an empty asm: fields read through it are scalar loads issued HERE, every time --
 // for values a loop needs once per trip but that, kept in registers across it, are spilled (to VGPR

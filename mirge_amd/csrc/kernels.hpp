@@ -444,6 +444,29 @@ struct LongParams {
 };
 hipError_t launch_long_reads(const LongParams& p, uint32_t grid, hipStream_t stream);
 
+// long_valid_kernel (mrg_list_valid_long_count / _fill): valid_kernel's listing for ragged reads of any length, one
+// wave per read.  lib: the library and the policy (seed_len, max_mm_seed, max_mm_total; the window fields are unused).
+struct LongValidParams {
+  LongPass lib;
+  const uint64_t* words;  // ragged, as in LongParams
+  const uint64_t* nmask;
+  const uint64_t* word_off;
+  const uint32_t* lens;
+  uint32_t n;
+  uint32_t wstop;
+  uint32_t strands;  // 1 = forward only (--norc), 2 = forward, then the reverse complement
+  uint32_t all;      // fill sweep: 1 = every valid alignment, 0 = only those with best_mm[r] mismatches
+  uint32_t* counts;  // count sweep: [4][n] alignments with exactly 0..3 mismatches
+  const uint8_t* best_mm;   // fill sweep: 255 = the read writes nothing
+  const uint64_t* offsets;  // first slot of every read
+  uint64_t cap;             // slots >= cap are not written
+  int32_t* out_ref;
+  int32_t* out_pos;
+  uint8_t* out_strand;  // 0 = +, 1 = -
+  uint8_t* out_mm;
+};
+hipError_t launch_long_valid(const LongValidParams& p, bool fill, uint32_t grid, hipStream_t stream);
+
 constexpr uint32_t kCountThreads = 256u;
 
 struct CountParams {

@@ -978,21 +978,62 @@ class Engine:
         Returns host arrays (offsets[n+1], entry, offset, strand (0 = +, 1 = -), mm, suppressed[n] bool); read r owns
         [offsets[r], offsets[r+1]), ordered by mismatches ascending, then (entry, offset, strand) DESCENDING.
         timings: a dict, or None; gets the synchronised wall seconds of the count and of the fill sweeps."""
+        nm = reads.nmask.data_ptr() if reads.nmask is not None else None
+        args = (reads.words.data_ptr(), reads.W, reads.lens.data_ptr(), nm, reads.n)
+        policy = (int(seed_len), int(max_mm_seed), int(max_mm_total))
+
+        def count(lid, cnt):
+            check(self._lib.mrg_list_valid_count(self._h, *args, lid, int(strands), *policy, cnt.data_ptr(), self._stream_ptr()))
+
+        def fill(lid, best_d, off_d, t, ref, pos, strand, mm):
+            check(self._lib.mrg_list_valid_fill(self._h, *args, lid, int(strands), int(stratum_mode), *policy, best_d.data_ptr(),
+                                                off_d.data_ptr(), t, ref.data_ptr(), pos.data_ptr(), strand.data_ptr(),
+                                                mm.data_ptr(), self._stream_ptr()))
+        return self._list_valid_host(reads.n, libs, stratum_mode, m, count, fill, timings)
+
+    def list_valid_long(self, seqs, libs, strands=2, stratum_mode=STRATUM_ALL, m=0, seed_len=28, max_mm_seed=0,
+                        max_mm_total=2, timings=None):
+        """list_valid for reads of ANY length (mrg_list_valid_long_count / _fill, one wave per read): `seqs` = ASCII reads
+        the packed form cannot describe (beyond 255 nt; any length works), packed into the ragged form as cascade_long
+        packs them.  Same libraries, policy, `-m` and stratum rules, and exactly list_valid's return tuple and row order."""
+        torch = _torch()
+        from . import pack
+        n = len(seqs)
+        words, nmask, word_off, lens = pack.pack_ragged(list(seqs))
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(self.device) if a is not None else None
+        d_words = up(np.append(words, np.uint64(0)), np.int64)   # (one word of padding: an empty batch still has a buffer)
+        d_nmask = up(None if nmask is None else np.append(nmask, np.uint64(0)), np.int64)
+        d_off, d_lens = up(word_off, np.int64), up(lens, np.int32)
+        args = (d_words.data_ptr(), d_nmask.data_ptr() if d_nmask is not None else None, d_off.data_ptr(), d_lens.data_ptr(), n)
+        policy = (int(strands), int(seed_len), int(max_mm_seed), int(max_mm_total))
+
+        def count(lid, cnt):
+            check(self._lib.mrg_list_valid_long_count(self._h, *args, lid, *policy, cnt.data_ptr(), self._stream_ptr()))
+
+        def fill(lid, best_d, off_d, t, ref, pos, strand, mm):
+            check(self._lib.mrg_list_valid_long_fill(self._h, *args, lid, *policy, int(stratum_mode), best_d.data_ptr(),
+                                                     off_d.data_ptr(), t, ref.data_ptr(), pos.data_ptr(), strand.data_ptr(),
+                                                     mm.data_ptr(), self._stream_ptr()))
+        return self._list_valid_host(n, libs, stratum_mode, m, count, fill, timings)
+
+    def _list_valid_host(self, n, libs, stratum_mode, m, count, fill, timings=None):
+        """The host half of a listing, whatever form its reads have: count(lid, cnt [4, n] int32) per part -> the best
+        stratum, what is reportable and what `-m` suppresses, decided over all parts from the summed counts -> per-part
+        offsets -> fill(lid, best_mm, offsets, rows, ref, pos, strand, mm) per part -> the parts' rows merged, entries
+        numbered on across `libs`, ordered by mismatches ascending, then (entry, offset, strand) descending."""
         import time
         torch = _torch()
-        n = reads.n
         dev = self.device
         lids = [self.libs[k] if isinstance(k, str) else int(k) for k in libs]
         keys = {v: k for k, v in self.libs.items()}
         bases = np.cumsum([0] + [self.indexes[keys[l]].n_ref for l in lids])
-        nm = reads.nmask.data_ptr() if reads.nmask is not None else None
-        args = (reads.W, reads.lens.data_ptr(), nm, n)
         per_lib = []
         t0 = time.perf_counter()
         for lid in lids:
             cnt = torch.zeros((4, max(n, 1)), dtype=torch.int32, device=dev)
-            check(self._lib.mrg_list_valid_count(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(seed_len),
-                                                 int(max_mm_seed), int(max_mm_total), cnt.data_ptr(), self._stream_ptr()))
+            count(lid, cnt)
             per_lib.append(cnt.cpu().numpy()[:, :n].view(np.uint32).astype(np.int64))
         if timings is not None:
             timings["count_s"] = time.perf_counter() - t0
@@ -1024,10 +1065,7 @@ class Engine:
             strand = torch.empty(t, dtype=torch.uint8, device=dev)
             mm = torch.empty(t, dtype=torch.uint8, device=dev)
             t0 = time.perf_counter()
-            check(self._lib.mrg_list_valid_fill(self._h, reads.words.data_ptr(), *args, lid, int(strands), int(stratum_mode),
-                                                int(seed_len), int(max_mm_seed), int(max_mm_total), best_d.data_ptr(),
-                                                off_d.data_ptr(), t, ref.data_ptr(), pos.data_ptr(), strand.data_ptr(),
-                                                mm.data_ptr(), self._stream_ptr()))
+            fill(lid, best_d, off_d, t, ref, pos, strand, mm)
             torch.cuda.current_stream(dev).synchronize()
             t_fill += time.perf_counter() - t0
             got.append((np.repeat(np.arange(n, dtype=np.int64), k), ref.cpu().numpy().astype(np.int64) + int(base),
